@@ -19,6 +19,12 @@ N > 1 (launched by torch.distributed.run): validators are range-sharded -- stron
 configs[3]: the 1 048 576-validator registry over N GPUs), --scaling weak for a full registry per GPU; the
 exchange steps are one RCCL all-gather of G1 XYZZ partials (192 B per committee) and one all-reduce of per-block weights.
 
+A plain run does what the headline needs and nothing else: set-up, warm-up, the timed steps, the line (`metric`, `value`,
+`ms_per_step` ...).  --full adds everything else the line has carried: the CPU baselines and the oracle check, the replay
+that verifies every timed step, the with-shuffle / with-signatures / per-slot legs, get_head latency, per-kernel averages
+and the rooflines (whose event brackets run inside the timed region).  --dump-outputs DIR writes what the last timed step
+returned as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -40,7 +46,7 @@ from bench_legs.sharded import (ReplayCollectives, _SoloDist, committee_step_che
                                 run_step_sharded, run_step_sharded_pipelined, sharded_step_check)
 from bench_legs.signed import signed_steps, unaggregated_signatures  # noqa: E402,F401
 from bench_legs.slots import slot_cadence  # noqa: E402,F401
-from bench_legs.verify import replay_and_verify, step_digest, whole_step_check  # noqa: E402,F401
+from bench_legs.verify import replay_and_verify, step_digest, step_outputs, whole_step_check  # noqa: E402,F401
 from bench_legs.workload import _BREAKDOWN, build_workload, load_registry, run_step_single, state_ctx  # noqa: E402,F401
 
 
@@ -57,6 +63,38 @@ SHAPES = {
     "configs4": dict(validators=1 << 22, committees=2048, blocks=8192, mixed_balances=True, tree_kind="bushy",
                      equivocating_frac=0.01),
 }
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as <path>/<name>.npy in a float type that holds its integers exactly -- bytes and u16 as
+    float32, 32-bit words as float64, u64 / i64 as their (low, high) 32-bit words (a trailing axis of 2), structured rows
+    as their bytes.  Beyond `limit` bytes in all, an array larger than its share keeps a fixed sample of its rows (seed 0,
+    sorted), whose indices go to <name>__rows.npy."""
+    conv = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype.fields is not None:
+            a = a.view(np.uint8).reshape(a.shape + (a.dtype.itemsize,))
+        elif a.dtype == np.bool_:
+            a = a.astype(np.uint8)
+        if a.dtype.kind in "iu" and a.dtype.itemsize == 8:
+            a = a.view(np.uint32 if a.dtype.kind == "u" else np.int32).reshape(a.shape + (2,))
+        conv[name] = a.astype(np.float32 if a.dtype.itemsize <= 2 and a.dtype.kind in "iu" else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > limit:
+        share = limit // max(len(conv), 1)
+        for name, a in list(conv.items()):
+            if a.nbytes > share and a.ndim and a.shape[0] > 1:
+                k = max(1, share // max(a.nbytes // a.shape[0], 1) - 1)
+                rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=k, replace=False))
+                conv[name] = a[rows]
+                conv[name + "__rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def main():
@@ -128,7 +166,17 @@ def main():
     ap.add_argument("--lag", type=int, default=4,
                     help="lag depth of the streaming pipelines (pe_pipeline_set_lag): a step's outputs are complete when "
                          "the lag-th next step has been enqueued")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: CPU baselines, oracle checks, the replay of every timed step, the "
+                         "with-shuffle / with-signatures / per-slot legs, get_head latency, per-kernel averages and rooflines "
+                         "(their event brackets run inside the timed region).  Off: set-up, warm-up, timed steps, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (head, statuses, counts, reward numerators, aggregate rows, "
+                         "bits and pubkeys, grouping) as DIR/<name>.npy, float32 / float64 holding the exact integers")
     args = ap.parse_args()
+    if not args.full:   # a plain run: none of the legs, checks or profiles that --full adds
+        args.no_cpu_baseline = args.no_oracle_check = args.no_verify_steps = True
+        args.no_shuffle_variant = args.no_signed_steps = args.no_slot_cadence = True
     for key, val in SHAPES[args.shape].items():   # what the shape fixes, unless given explicitly
         if getattr(args, key) is None:
             setattr(args, key, val)
@@ -281,7 +329,8 @@ def main():
             # idle GPU in front of a 6 ms timed region is a cold start, which is not what W warm-up steps are for.
             gc.collect()
             gc.disable()
-            e.profile_enable(True)
+            if args.full:
+                e.profile_enable(True)
 
         for s in range(args.warmup):
             if s == 1:
@@ -302,10 +351,11 @@ def main():
         # Inside the timed region only the roofline's kernel is bracketed (k_g1_accumulate, one launch in four): every bracket
         # is two event packets on a stream of latency-sized kernels plus host time, and twelve more of them per step were
         # charged to the engine (round 6: profiles/NOTES_r06.md).  The other kernels' averages are those of the warm-up steps.
-        prof_warm = e.profile() if args.warmup >= 3 else None
+        prof_warm = e.profile() if (args.full and args.warmup >= 3) else None
         if prof_warm is not None:
             e.profile_enable(3)
-        e.profile_reset()   # the warm-up launches are not part of the timed region's averages
+        if args.full:
+            e.profile_reset()   # the warm-up launches are not part of the timed region's averages
         barrier()
         t0 = time.perf_counter()
         inflight = []
@@ -329,9 +379,12 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
         gc.enable()
-        acc_mhz = e.profile_accumulate_mhz()   # the clock every timed step's dominant kernel ran at
-        prof = e.profile()
-        e.profile_enable(False)
+        outputs = step_outputs(last) if args.dump_outputs else None   # before any later step reuses its buffers
+        acc_mhz = prof = None
+        if args.full:
+            acc_mhz = e.profile_accumulate_mhz()   # the clock every timed step's dominant kernel ran at
+            prof = e.profile()
+            e.profile_enable(False)
         if prof_warm is not None:
             prof = {k: (v if k == "g1_accumulate" or v["launches"] else prof_warm[k]) for k, v in prof.items()}
         assert n_rejected == 0, "synthetic attestations were rejected"
@@ -350,7 +403,7 @@ def main():
             if verify:
                 kept.extend(more)
         return dict(dt=dt, stamps=stamps, n_att_local=n_att_local, last=last, prof=prof, kept=kept, verify=verify,
-                    sharded_chk=sharded_chk, dt_var=dt_var, acc_mhz=acc_mhz)
+                    sharded_chk=sharded_chk, dt_var=dt_var, acc_mhz=acc_mhz, outputs=outputs)
 
     e, w, ex, engine_rccl, exchange_how = setup(single_comm=False)
     dist_fallback = None
@@ -372,11 +425,13 @@ def main():
     dt, stamps, n_att_local, last, prof, kept, verify = (R[k] for k in ("dt", "stamps", "n_att_local", "last", "prof",
                                                                         "kept", "verify"))
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, R["outputs"])
     # get_head latency: full recomputation from the vote table, after the timed region
     lat = []
-    for _ in range(20):
+    for _ in range(20 if args.full else 0):
         e.get_head() if (ex is None or args.by_committee) else ex.get_head()
-    for _ in range(args.head_calls):
+    for _ in range(args.head_calls if args.full else 0):
         t = time.perf_counter()
         e.get_head() if (ex is None or args.by_committee) else ex.get_head()
         lat.append((time.perf_counter() - t) * 1e6)
@@ -384,7 +439,7 @@ def main():
     # k_votes / k_tree alone (in the timed steps they run as halves of paired launches, engine_pair.cpp): their own durations
     # from a few more synchronous heads under the engine's event brackets, after the latency calls
     prof_head = None
-    if ex is None or args.by_committee:
+    if args.full and (ex is None or args.by_committee):
         e.profile_enable(True)
         e.profile_reset()
         for _ in range(50):
@@ -427,52 +482,53 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- roofline of the dominant kernel: k_g1_accumulate, algorithmic bytes per launch ----
     C = args.committees
     VL = args.validators_local
-    att_per_launch = n_att_local / args.steps
-    alg_bytes = 100.125 * att_per_launch + C * (96 + (VL / C) / 8)
-    acc = prof["g1_accumulate"]
-    acc_ms = acc["total_ms"] / max(acc["launches"], 1)
-    achieved = alg_bytes / (acc_ms * 1e-3) / 1e9 if acc_ms else 0.0
-    # HBM bytes per launch from the PMC passes (tools/profile_round.sh): recorded per shape, quoted only for the shape
-    # that was measured
-    traffic, traffic_src = None, None
-    tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-    if os.path.exists(tpath):
-        try:
-            ent = json.load(open(tpath)).get("shapes", {}).get(f"{VL},{C},{args.blocks}")
-            if ent:
-                traffic, traffic_src = ent.get("k_g1_accumulate_bytes_per_launch"), ent.get("source")
-        except Exception:
-            traffic = None
-    # VALU view of the same kernel (round 4: the S29 field form, fp381_s29.h).  A lane takes its first point as it is and
-    # adds the others with the general mixed add: 8 products of 392 multiply-adds + 2 squarings of 301 = 3738
-    # v_mad_[iu]64_[iu]32 and nothing that carries; the hand-over to the tree's words costs 4 products per lane.  Lanes as the
-    # engine plans them in streaming steps: one wave per SIMD, k = max(4, ceil(members / 65536)) members per lane.
-    MACS_MUL, MACS_SQR = 392, 301
-    MACS_ADD = 8 * MACS_MUL + 2 * MACS_SQR
-    k_run = max(4, -(-VL // 65536))
-    lane_runs = C * -(-(VL // C) // k_run)
-    mixed_adds = max(att_per_launch - lane_runs, 0.0)
-    macs = mixed_adds * MACS_ADD   # (until round 6 + 4 products per lane: the hand-over's conversion, now the tree's, per group)
-    # the multiplier's issue rate (tools/ubench_valu, profiles/r01_ubench_valu_fpmul.log: v_mad_u64_u32 every 2.496 ns per SIMD
-    # at two waves, 2.454 at four; v_mad_i64_i32 is the same unit): 1024 SIMDs x 64 lanes
-    MAC_PEAK = 1024 * 64 / 2.496e-9
-    valu_peak = MAC_PEAK / MACS_ADD              # mixed adds per second if the SIMDs issued nothing but multiply-adds
-    valu_ach = mixed_adds / (acc_ms * 1e-3) if acc_ms else 0.0
-    # the tree over the lanes' partials (S29 form since round 6: 12 products + 2 squarings per full add, one add per lane but one
-    # per committee, + 4 products per committee for the hand-over to k_g1_finish's words); beside the NEXT accumulation
-    tree_macs = (12.0 * MACS_MUL + 2.0 * MACS_SQR) * max(lane_runs - C, 0) + 4.0 * MACS_MUL * C
-    # the clock the timed steps' accumulations ran at (pe_profile_accumulate_mhz); the multiplier's rate above is one multiply-add
-    # per SIX shader cycles and SIMD, which is 2.496 ns at 2.404 GHz -- the sustained clock; a run of a few milliseconds from an
-    # idle device sees ~2.05 GHz (tools/clockramp.hip)
-    acc_mhz = [float(x) for x in R["acc_mhz"] if x > 0]
-    mhz_mean = sum(acc_mhz) / len(acc_mhz) if acc_mhz else None
-    votes = prof_head["votes"] if prof_head is not None and prof_head["votes"]["launches"] else prof["votes"]
-    votes_ms = votes["total_ms"] / max(votes["launches"], 1)
-    votes_bytes = 13.0 * VL + 32.0 * args.blocks
-    kernel_ms = {k: (v["total_ms"] / v["launches"] if v["launches"] else None) for k, v in prof.items()}
+    if args.full:
+        # ---- roofline of the dominant kernel: k_g1_accumulate, algorithmic bytes per launch ----
+        att_per_launch = n_att_local / args.steps
+        alg_bytes = 100.125 * att_per_launch + C * (96 + (VL / C) / 8)
+        acc = prof["g1_accumulate"]
+        acc_ms = acc["total_ms"] / max(acc["launches"], 1)
+        achieved = alg_bytes / (acc_ms * 1e-3) / 1e9 if acc_ms else 0.0
+        # HBM bytes per launch from the PMC passes (tools/profile_round.sh): recorded per shape, quoted only for the shape
+        # that was measured
+        traffic, traffic_src = None, None
+        tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+        if os.path.exists(tpath):
+            try:
+                ent = json.load(open(tpath)).get("shapes", {}).get(f"{VL},{C},{args.blocks}")
+                if ent:
+                    traffic, traffic_src = ent.get("k_g1_accumulate_bytes_per_launch"), ent.get("source")
+            except Exception:
+                traffic = None
+        # VALU view of the same kernel (round 4: the S29 field form, fp381_s29.h).  A lane takes its first point as it is and
+        # adds the others with the general mixed add: 8 products of 392 multiply-adds + 2 squarings of 301 = 3738
+        # v_mad_[iu]64_[iu]32 and nothing that carries; the hand-over to the tree's words costs 4 products per lane.  Lanes as the
+        # engine plans them in streaming steps: one wave per SIMD, k = max(4, ceil(members / 65536)) members per lane.
+        MACS_MUL, MACS_SQR = 392, 301
+        MACS_ADD = 8 * MACS_MUL + 2 * MACS_SQR
+        k_run = max(4, -(-VL // 65536))
+        lane_runs = C * -(-(VL // C) // k_run)
+        mixed_adds = max(att_per_launch - lane_runs, 0.0)
+        macs = mixed_adds * MACS_ADD   # (until round 6 + 4 products per lane: the hand-over's conversion, now the tree's, per group)
+        # the multiplier's issue rate (tools/ubench_valu, profiles/r01_ubench_valu_fpmul.log: v_mad_u64_u32 every 2.496 ns per SIMD
+        # at two waves, 2.454 at four; v_mad_i64_i32 is the same unit): 1024 SIMDs x 64 lanes
+        MAC_PEAK = 1024 * 64 / 2.496e-9
+        valu_peak = MAC_PEAK / MACS_ADD              # mixed adds per second if the SIMDs issued nothing but multiply-adds
+        valu_ach = mixed_adds / (acc_ms * 1e-3) if acc_ms else 0.0
+        # the tree over the lanes' partials (S29 form since round 6: 12 products + 2 squarings per full add, one add per lane but one
+        # per committee, + 4 products per committee for the hand-over to k_g1_finish's words); beside the NEXT accumulation
+        tree_macs = (12.0 * MACS_MUL + 2.0 * MACS_SQR) * max(lane_runs - C, 0) + 4.0 * MACS_MUL * C
+        # the clock the timed steps' accumulations ran at (pe_profile_accumulate_mhz); the multiplier's rate above is one multiply-add
+        # per SIX shader cycles and SIMD, which is 2.496 ns at 2.404 GHz -- the sustained clock; a run of a few milliseconds from an
+        # idle device sees ~2.05 GHz (tools/clockramp.hip)
+        acc_mhz = [float(x) for x in R["acc_mhz"] if x > 0]
+        mhz_mean = sum(acc_mhz) / len(acc_mhz) if acc_mhz else None
+        votes = prof_head["votes"] if prof_head is not None and prof_head["votes"]["launches"] else prof["votes"]
+        votes_ms = votes["total_ms"] / max(votes["launches"], 1)
+        votes_bytes = 13.0 * VL + 32.0 * args.blocks
+        kernel_ms = {k: (v["total_ms"] / v["launches"] if v["launches"] else None) for k, v in prof.items()}
     per_step = np.diff(np.array(stamps)) * 1e3
     V_total = VL if args.by_committee else VL * world   # committee shards: one registry, on every rank
     named = {(sh["validators"], sh["committees"], sh["blocks"], sh["mixed_balances"], sh["tree_kind"], sh["equivocating_frac"]):
@@ -540,65 +596,68 @@ def main():
         "step_ms_p90": float(np.percentile(per_step, 90)),
         "aggregation_budget": {"seconds": 4.0, "source": "pe:1536 (the last third of a 12 s slot)",
                                "step_fraction_of_budget": dt / args.steps / 4.0},
-        "get_head_p50_us": float(lat[len(lat) // 2]),
-        "get_head_p99_us": float(lat[min(len(lat) - 1, int(len(lat) * 0.99))]),
-        "roofline": {
-            "kernel": "k_g1_accumulate", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-            "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": acc_ms, "launches": acc["launches"],
-            "launches_detail": "launches bracketed with HIP events on the kernel's own stream inside the timed region: one in "
-                               "four (every event record on that stream is step time since the accumulation paces the step)",
-            "note": "integer-VALU bound (3738 multiply-adds per 100 B gathered), not HBM bound: "
-                    "see roofline_valu and DESIGN.md; the votes kernel below is the HBM-streaming one",
-        },
-        "shader_mhz": ({"k_g1_accumulate_first_timed_launch": round(acc_mhz[0], 1), "last_timed_launch": round(acc_mhz[-1], 1),
-                        "mean": round(mhz_mean, 1), "min": round(min(acc_mhz), 1), "max": round(max(acc_mhz), 1),
-                        "launches": len(acc_mhz),
-                        "how": "workgroup 0 of every timed k_g1_accumulate launch counts shader cycles against the fixed 100 MHz "
-                               "counter (pe_profile_accumulate_mhz)",
-                        "why": "the step is bound by the integer multiplier, so it follows the power management's clock one to "
-                               "one: ~2.05 GHz for the first milliseconds of heavy load after an idle moment, ~2.4 GHz after ~35 ms "
-                               "of it (tools/clockramp.hip, profiles/r06_clockramp.txt) -- most of the distance between "
-                               "--steps 20 and --steps 200"} if acc_mhz else None),
-        "roofline_valu": {
-            "kernel": "k_g1_accumulate", "bound": "integer VALU: v_mad_i64_i32 / v_mad_u64_u32 issue (S29 field form)",
-            "achieved": valu_ach / 1e9, "peak": valu_peak / 1e9, "unit": "G mixed adds/s", "frac": valu_ach / valu_peak,
-            "mixed_adds_per_launch": mixed_adds, "multiply_adds_per_mixed_add": MACS_ADD,
-            "multiply_adds_per_launch": macs,
-            "peak_source": "instruction ceiling: one 32 x 32 -> 64 multiply-add per 2.496 ns and SIMD (tools/ubench_valu, "
-                           "profiles/r01_ubench_valu_fpmul.log) x 1024 SIMDs x 64 lanes / 3738 multiply-adds per mixed add = "
-                           "7.0 G/s; the same adds in a loop without loads reach 6.96 G/s (tools/icbench, "
-                           "profiles/r04_icbench.txt), the kernel alone 5.8 G/s (tools/accbench, profiles/r04_accbench.txt)",
-            "at_measured_clock": ({"mean_shader_mhz": round(mhz_mean, 1), "peak": 1024 * 64 * mhz_mean * 1e6 / 6.0 / MACS_ADD / 1e9,
-                                   "frac": valu_ach / (1024 * 64 * mhz_mean * 1e6 / 6.0 / MACS_ADD),
-                                   "note": "the same ceiling at the clock the timed launches ran at (six cycles per multiply-add "
-                                           "and SIMD): what the kernel makes of the cycles it was given"}
-                                  if mhz_mean else None),
-            "step_view": {
-                "tree_multiply_adds_per_step": tree_macs,
-                "multiply_adds_per_step": macs + tree_macs,
-                "frac_of_multiplier_over_the_step": (macs + tree_macs) / (dt / args.steps) / MAC_PEAK,
-                "note": "multiply-adds of the accumulation + the tree of one step over the whole step period: the fraction of "
-                        "the period the chip's multipliers spend on this algorithm; the rest is the tree's carry adds, the "
-                        "in-situ efficiency of the two kernels and the chain of small kernels that paces the step "
-                        "(DESIGN.md 8)",
-            },
-        },
-        "roofline_votes": {
-            "kernel": "k_votes", "bound": "hbm", "achieved": votes_bytes / (votes_ms * 1e-3) / 1e9 if votes_ms else 0.0,
-            "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": (votes_bytes / (votes_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if votes_ms else 0.0,
-            "avg_launch_ms": votes_ms, "launches": votes["launches"],
-            "measured": ("stand-alone launches of 50 synchronous pe_get_head calls after the timed region (in the streaming steps "
-                         "k_votes runs as one half of a paired launch: kernel_avg_ms.pair_members_votes)"
-                         if votes is not prof["votes"] else "the timed steps' own launches"),
-        },
-        "kernel_avg_ms": kernel_ms,
-        "kernel_avg_ms_detail": ("g1_accumulate: HIP events inside the timed region (one launch in four); every other kernel: the "
-                                 "warm-up steps' launches (nothing but the roofline's kernel is bracketed while the clock runs)"
-                                 if args.warmup >= 3 else "HIP events inside the timed region"),
-        "kernel_launches": {k: v["launches"] for k, v in prof.items()},
     }
+    if args.full:
+        out.update({
+            "get_head_p50_us": float(lat[len(lat) // 2]),
+            "get_head_p99_us": float(lat[min(len(lat) - 1, int(len(lat) * 0.99))]),
+            "roofline": {
+                "kernel": "k_g1_accumulate", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": acc_ms, "launches": acc["launches"],
+                "launches_detail": "launches bracketed with HIP events on the kernel's own stream inside the timed region: one in "
+                                   "four (every event record on that stream is step time since the accumulation paces the step)",
+                "note": "integer-VALU bound (3738 multiply-adds per 100 B gathered), not HBM bound: "
+                        "see roofline_valu and DESIGN.md; the votes kernel below is the HBM-streaming one",
+            },
+            "shader_mhz": ({"k_g1_accumulate_first_timed_launch": round(acc_mhz[0], 1), "last_timed_launch": round(acc_mhz[-1], 1),
+                            "mean": round(mhz_mean, 1), "min": round(min(acc_mhz), 1), "max": round(max(acc_mhz), 1),
+                            "launches": len(acc_mhz),
+                            "how": "workgroup 0 of every timed k_g1_accumulate launch counts shader cycles against the fixed 100 MHz "
+                                   "counter (pe_profile_accumulate_mhz)",
+                            "why": "the step is bound by the integer multiplier, so it follows the power management's clock one to "
+                                   "one: ~2.05 GHz for the first milliseconds of heavy load after an idle moment, ~2.4 GHz after ~35 ms "
+                                   "of it (tools/clockramp.hip, profiles/r06_clockramp.txt) -- most of the distance between "
+                                   "--steps 20 and --steps 200"} if acc_mhz else None),
+            "roofline_valu": {
+                "kernel": "k_g1_accumulate", "bound": "integer VALU: v_mad_i64_i32 / v_mad_u64_u32 issue (S29 field form)",
+                "achieved": valu_ach / 1e9, "peak": valu_peak / 1e9, "unit": "G mixed adds/s", "frac": valu_ach / valu_peak,
+                "mixed_adds_per_launch": mixed_adds, "multiply_adds_per_mixed_add": MACS_ADD,
+                "multiply_adds_per_launch": macs,
+                "peak_source": "instruction ceiling: one 32 x 32 -> 64 multiply-add per 2.496 ns and SIMD (tools/ubench_valu, "
+                               "profiles/r01_ubench_valu_fpmul.log) x 1024 SIMDs x 64 lanes / 3738 multiply-adds per mixed add = "
+                               "7.0 G/s; the same adds in a loop without loads reach 6.96 G/s (tools/icbench, "
+                               "profiles/r04_icbench.txt), the kernel alone 5.8 G/s (tools/accbench, profiles/r04_accbench.txt)",
+                "at_measured_clock": ({"mean_shader_mhz": round(mhz_mean, 1), "peak": 1024 * 64 * mhz_mean * 1e6 / 6.0 / MACS_ADD / 1e9,
+                                       "frac": valu_ach / (1024 * 64 * mhz_mean * 1e6 / 6.0 / MACS_ADD),
+                                       "note": "the same ceiling at the clock the timed launches ran at (six cycles per multiply-add "
+                                               "and SIMD): what the kernel makes of the cycles it was given"}
+                                      if mhz_mean else None),
+                "step_view": {
+                    "tree_multiply_adds_per_step": tree_macs,
+                    "multiply_adds_per_step": macs + tree_macs,
+                    "frac_of_multiplier_over_the_step": (macs + tree_macs) / (dt / args.steps) / MAC_PEAK,
+                    "note": "multiply-adds of the accumulation + the tree of one step over the whole step period: the fraction of "
+                            "the period the chip's multipliers spend on this algorithm; the rest is the tree's carry adds, the "
+                            "in-situ efficiency of the two kernels and the chain of small kernels that paces the step "
+                            "(DESIGN.md 8)",
+                },
+            },
+            "roofline_votes": {
+                "kernel": "k_votes", "bound": "hbm", "achieved": votes_bytes / (votes_ms * 1e-3) / 1e9 if votes_ms else 0.0,
+                "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": (votes_bytes / (votes_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if votes_ms else 0.0,
+                "avg_launch_ms": votes_ms, "launches": votes["launches"],
+                "measured": ("stand-alone launches of 50 synchronous pe_get_head calls after the timed region (in the streaming steps "
+                             "k_votes runs as one half of a paired launch: kernel_avg_ms.pair_members_votes)"
+                             if votes is not prof["votes"] else "the timed steps' own launches"),
+            },
+            "kernel_avg_ms": kernel_ms,
+            "kernel_avg_ms_detail": ("g1_accumulate: HIP events inside the timed region (one launch in four); every other kernel: the "
+                                     "warm-up steps' launches (nothing but the roofline's kernel is bracketed while the clock runs)"
+                                     if args.warmup >= 3 else "HIP events inside the timed region"),
+            "kernel_launches": {k: v["launches"] for k, v in prof.items()},
+        })
     if emulate:
         g0 = kept[0]["gx"]
         att_epoch = int(np.asarray(g0["count"]).sum())

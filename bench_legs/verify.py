@@ -62,6 +62,23 @@ def step_digest(r):
     return h.digest()
 
 
+def step_outputs(r):
+    """What one step hands its caller, by name: the arrays step_digest hashes, copied out of the engine's output ring (a
+    streaming caller's buffers are reused `lag` + 2 steps later).  Per-group arrays are cut to the groups formed."""
+    agg = r["agg"]
+    g = int(agg["n_groups"])
+    out = {"head": np.frombuffer(bytes(r["head"]), dtype=np.uint8).copy()}
+    for name, val, cut in (("status", r["status"], True), ("count", r["count"], True), ("pstatus", r["pstatus"], True),
+                           ("numerators", r["numerators"], True), ("aggregate_rows", agg["atts"], True),
+                           ("aggregate_bits", agg["out_arena"], False), ("aggregate_pubkeys", agg["aggpk96"], True),
+                           ("aggregate_count", agg["count"], True), ("group_of", agg["group_of"], False)):
+        val = val.fn() if hasattr(val, "fn") else val   # bench_legs.sharded._Lazy
+        if val is None:
+            continue
+        out[name] = np.array(val[:g] if cut else val)
+    return out
+
+
 def replay_and_verify(pea, w, device, results, total):
     """Every step of the run (warm-up included: the store state carries over) again on a fresh engine with SYNCHRONOUS
     calls over HOST rows -- the path the -m gpu tests hold against the oracle call by call -- and the digest of each

@@ -1,5 +1,6 @@
 """The synthetic workload of bench.py (BASELINE.json's configs) and one step of it through the C ABI."""
 import functools
+import math
 import os
 import time
 
@@ -51,9 +52,9 @@ def build_workload(e, args, rank, n_steps_total):
         ep_seed = hashlib.sha256(b"bench-seed" + seed.to_bytes(8, "little") + ep.to_bytes(8, "little")).digest()
         off, mem = e.compute_committees(ep, ep_seed, V, C, 90)   # every validator active: the identity index set
         comm = synth.Committees(off, mem)
-        atts, arena, _ = synth.epoch_attestations(comm, tree, ep, spe, seed=seed, density=0.99, parts=args.parts,
-                                                  source=(0, tree.roots[0].tobytes()), vote_recent=64,
-                                                  vote_seed=4)  # committee c votes the same block on every shard
+        atts, arena = epoch_attestations(comm, tree, ep, spe, seed=seed, density=0.99, parts=args.parts,
+                                         source=(0, tree.roots[0].tobytes()), vote_recent=64,
+                                         vote_seed=4)  # committee c votes the same block on every shard
         st = dict(epoch=ep, comm=comm, atts=atts, arena=arena, ep_seed=ep_seed)
         if getattr(args, "boost", False):
             # SURVEY 8(d) "boost {unset, set on a leaf}": proposer_boost_root (pe:896) set after the step's on_tick (which
@@ -111,6 +112,67 @@ def build_workload(e, args, rank, n_steps_total):
                 st["rows_in"] = DeviceRows(r.data_ptr(), len(rows), keep=r)
         torch.cuda.synchronize()
     return w
+
+
+def epoch_attestations(comm, tree, epoch, slots_per_epoch, seed, density=0.99, parts=1, source=(0, None), vote_recent=8,
+                       vote_seed=None):
+    """synth.epoch_attestations -> (atts, arena), byte for byte, in whole-array numpy: one epoch of the workload is built
+    before the clock for every step, and the per-committee loop (~0.1 s per configs[3] epoch) made the set-up grow with
+    --steps.  The random streams are consumed as synth consumes them: per committee `size` doubles (rng.random: the top 53
+    bits of one u64 each) then `size` bounded u32 draws (rng.integers(0, parts): Lemire, two per u64, low half first; for
+    a power-of-two `parts` the top log2(parts) bits, never rejected), and one head vote per committee from the separate
+    vote stream.  Shapes outside that case (unequal or odd committee sizes, a shared vote stream, other `parts`) go
+    through synth itself.  tests/test_bench_contract.py holds the two against each other."""
+    import pos_evolution_amd.synth as synth
+
+    sizes = np.diff(comm.offsets.astype(np.int64))
+    n_comm = sizes.size
+    cps = n_comm // slots_per_epoch if slots_per_epoch else 0
+    size = int(sizes[0]) if n_comm else 0
+    if (vote_seed is None or n_comm == 0 or cps * slots_per_epoch != n_comm or (sizes != size).any() or size % 2
+            or parts < 1 or parts & (parts - 1)):
+        atts, arena, _ = synth.epoch_attestations(comm, tree, epoch, slots_per_epoch, seed, density=density, parts=parts,
+                                                  source=source, vote_recent=vote_recent, vote_seed=vote_seed)
+        return atts, arena
+    rng = np.random.Generator(np.random.PCG64(seed + 5000 + epoch))
+    vrng = np.random.Generator(np.random.PCG64(vote_seed + 7000 + epoch))
+    n_int = size // 2 if parts > 1 else 0          # rng.integers(0, 1, n) draws nothing
+    raw = rng.bit_generator.random_raw(n_comm * (size + n_int)).reshape(n_comm, size + n_int)
+    if density >= 1.0:
+        on = np.ones((n_comm, size), dtype=bool)
+    else:   # (u >> 11) * 2**-53 < density  <=>  u < ceil(density * 2**53) << 11
+        on = raw[:, :size] < np.uint64(max(math.ceil(density * 2.0 ** 53), 0) << 11)
+    part_of = np.zeros((n_comm, size), dtype=np.uint8)
+    if parts > 1:
+        b = parts.bit_length() - 1
+        words = raw[:, size:]
+        part_of[:, 0::2] = (words >> np.uint64(32 - b)) & np.uint64(parts - 1)
+        part_of[:, 1::2] = words >> np.uint64(64 - b)
+    slots = epoch * slots_per_epoch + np.arange(n_comm) // cps
+    order = np.argsort(tree.slot, kind="stable")
+    hi = np.searchsorted(tree.slot[order], slots, side="right")
+    lo = np.maximum(0, hi - vote_recent)
+    if not (hi > lo).all():   # a committee without a candidate block: synth's own rule
+        atts, arena, _ = synth.epoch_attestations(comm, tree, epoch, slots_per_epoch, seed, density=density, parts=parts,
+                                                  source=source, vote_recent=vote_recent, vote_seed=vote_seed)
+        return atts, arena
+    blk = order[lo + vrng.integers(0, hi - lo)]
+    anc = {}
+    target = np.array([anc.setdefault(int(x), synth.ancestor_at(tree, int(x), epoch * slots_per_epoch)) for x in blk])
+    n = n_comm * parts
+    atts = np.zeros(n, dtype=synth.ATT_DTYPE)
+    atts["slot"] = np.repeat(slots, parts)
+    atts["index"] = np.repeat(np.arange(n_comm) % cps, parts)
+    atts["beacon_block_root"] = np.repeat(tree.roots[blk], parts, axis=0)
+    atts["source_epoch"] = source[0]
+    atts["source_root"] = tree.roots[0] if source[1] is None else np.frombuffer(source[1], dtype=np.uint8)
+    atts["target_epoch"] = epoch
+    atts["target_root"] = np.repeat(tree.roots[target], parts, axis=0)
+    atts["flags"] = 1
+    bits = on[:, None, :] & (part_of[:, None, :] == np.arange(parts, dtype=np.uint8)[None, :, None])
+    atts["bits_offset"] = np.arange(n, dtype=np.uint32) * ((size + 7) // 8)
+    atts["n_bits"] = size
+    return atts, np.ascontiguousarray(np.packbits(bits, axis=-1, bitorder="little").reshape(-1))
 
 
 def state_ctx(w, ep):

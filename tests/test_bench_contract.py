@@ -87,3 +87,31 @@ def test_stdout_carries_nothing_but_the_line():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert src.index("os.dup2(2, 1)") < src.index("import torch"), "descriptor 1 is claimed before the first library loads"
     assert "os.write(json_fd" in src and "print(json.dumps(out))" not in src
+
+
+def test_workload_epochs_are_synth_byte_for_byte():
+    """bench_legs.workload.epoch_attestations builds the bench's epochs in whole-array numpy; what it returns must be
+    synth.epoch_attestations' rows and bit arena byte for byte, in the bench's shapes and in shapes that make it take other
+    branches (parts 1 / 2 / 3, density 1.0, epochs inside the tree's slots where committees see different candidate counts,
+    unequal committee sizes)."""
+    import numpy as np
+
+    import pos_evolution_amd.synth as synth
+    from bench_legs.workload import epoch_attestations
+
+    cases = [(1 << 16, 2048, 2048, "branchy", 4, 0.99, None), (65536, 256, 512, "bushy", 4, 0.99, None),
+             (65536, 256, 512, "bushy", 2, 1.0, None), (65536, 256, 512, "bushy", 1, 0.5, None),
+             (65536, 256, 512, "bushy", 3, 0.99, None), (20000, 64, 300, "chain", 4, 0.99, None),
+             (32768, 256, 4096, "bushy", 4, 0.9, 3)]
+    for V, C, B, kind, parts, density, epoch in cases:
+        tree = synth.random_tree(B, 4, kind)
+        comm = synth.random_committees(V, C, 1)
+        ep0 = int(tree.slot.max()) // 32 + 1 if epoch is None else epoch
+        for ep in (ep0, ep0 + 5):
+            src = (0, tree.roots[0].tobytes())
+            a, ar, _ = synth.epoch_attestations(comm, tree, ep, 32, seed=4, density=density, parts=parts, source=src,
+                                                vote_recent=64, vote_seed=4)
+            b, br = epoch_attestations(comm, tree, ep, 32, seed=4, density=density, parts=parts, source=src,
+                                       vote_recent=64, vote_seed=4)
+            assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), (V, C, B, kind, parts, density, ep)
+            assert ar.dtype == br.dtype and ar.tobytes() == br.tobytes(), (V, C, B, kind, parts, density, ep)

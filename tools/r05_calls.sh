@@ -32,7 +32,7 @@ call_c() {
 call_d() {
   O=gpurun_out/r05d; mkdir -p $O
   timeout 1200 python -m pytest tests/test_gpu_dist_custom.py tests/test_gpu_sharded.py tests/test_gpu_pairing.py tests/test_gpu_g2.py -x -q > $O/pytest_sharded.log 2>&1; echo "[r05d] sharded/pairing/g2 tests rc $?"; tail -12 $O/pytest_sharded.log
-  POSEVO_SLOT_TIMELINE=$O/slot_timeline.txt POSEVO_HOST_TRACE=1 timeout 600 python bench.py --steps 60 --warmup 6 --no-cpu-baseline > $O/bench_legs.json 2> $O/bench_legs.err; echo "[r05d] bench legs rc $?"
+  POSEVO_SLOT_TIMELINE=$O/slot_timeline.txt POSEVO_HOST_TRACE=1 timeout 600 python bench.py --full --steps 60 --warmup 6 --no-cpu-baseline > $O/bench_legs.json 2> $O/bench_legs.err; echo "[r05d] bench legs rc $?"
   python - <<'PY'
 import json
 d=json.load(open("gpurun_out/r05d/bench_legs.json"))
@@ -43,7 +43,7 @@ PY
   grep "posevo host" $O/bench_legs.err | cut -c1-120 | tail -40
   sed -n 1,4p $O/slot_timeline.txt; awk 'NR>400 && NR<470' $O/slot_timeline.txt
   for pair in 1 0; do for shape in "configs3 131072" "configs4 524288"; do set -- $shape
-    POSEVO_PAIR=$pair POSEVO_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --shape $1 --validators $2 --steps 100 --warmup 6 --no-cpu-baseline --no-signed-steps --no-slot-cadence --no-shuffle-variant > $O/rank_${1}_pair$pair.json 2> $O/rank_${1}_pair$pair.err
+    POSEVO_PAIR=$pair POSEVO_FORCE_DIST=1 timeout 600 python bench.py --full --gpus 1 --shape $1 --validators $2 --steps 100 --warmup 6 --no-cpu-baseline --no-signed-steps --no-slot-cadence --no-shuffle-variant > $O/rank_${1}_pair$pair.json 2> $O/rank_${1}_pair$pair.err
     echo "[r05d] per-rank step of an 8-way range shard, $1, pair=$pair: rc $? $(timeout 20 python tools/benchline.py < $O/rank_${1}_pair$pair.json 2>/dev/null | cut -c1-150)"; done; done
   bash tools/gpu.sh r05d label:all tests
 }
@@ -68,7 +68,7 @@ call_f() {
     timeout 400 python -m pytest tests/test_gpu_pairing.py tests/test_gpu_pipeline.py tests/test_gpu_pipeline_robust.py tests/test_gpu_g1_accumulate.py tests/test_gpu_shapes.py -x -q > $O/pytest_knobs.log 2>&1
     echo "[r05f] streaming tests with every knob on: rc $?"; tail -5 $O/pytest_knobs.log )
   for shape in configs3 configs4; do
-    timeout 300 python bench.py --emulate-ranks 8 --shape $shape --steps 100 --warmup 6 --no-signed-steps --no-slot-cadence > $O/emulate8_$shape.json 2> $O/emulate8_$shape.err
+    timeout 300 python bench.py --full --emulate-ranks 8 --shape $shape --steps 100 --warmup 6 --no-signed-steps --no-slot-cadence > $O/emulate8_$shape.json 2> $O/emulate8_$shape.err
     echo "[r05f] committee shards, per-rank step of 8, $shape: rc $? $(timeout 20 python tools/benchline.py < $O/emulate8_$shape.json 2>/dev/null | cut -c1-160)"
   done
 }
@@ -88,7 +88,7 @@ call_h() {
   timeout 200 python tools/engine_timeline.py --steps 30 --show 4 > $O/engine_timeline.txt 2>&1; tail -16 $O/engine_timeline.txt
   timeout 200 python tools/engine_timeline.py --cold 20 --steps 26 > $O/engine_timeline_cold20.txt 2>&1; head -26 $O/engine_timeline_cold20.txt
   for b in 1 0; do
-    POSEVO_SIG_BEHIND=$b timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant > $O/bench_sig_behind$b.json 2> $O/bench_sig_behind$b.err
+    POSEVO_SIG_BEHIND=$b timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant > $O/bench_sig_behind$b.json 2> $O/bench_sig_behind$b.err
     python - <<PY
 import json
 d=json.load(open("$O/bench_sig_behind$b.json"))
@@ -116,7 +116,7 @@ call_j() {
   timeout 120 tools/accbench > $O/accbench.txt 2>&1; echo "[r05j] accbench rc $?"; tail -8 $O/accbench.txt
   bash tools/gpu.sh r05j label:box5 quick driver
   for spec in "configs3 131072 engine" "configs4 524288 engine" "configs3 1048576 committee"; do set -- $spec
-    POSEVO_FORCE_DIST=1 timeout 300 python bench.py --gpus 1 --shape $1 --validators $2 --sharded-mode $3 --steps 100 --warmup 6 --no-cpu-baseline --no-signed-steps --no-slot-cadence --no-shuffle-variant > $O/rank_${1}_$3.json 2> $O/rank_${1}_$3.err
+    POSEVO_FORCE_DIST=1 timeout 300 python bench.py --full --gpus 1 --shape $1 --validators $2 --sharded-mode $3 --steps 100 --warmup 6 --no-cpu-baseline --no-signed-steps --no-slot-cadence --no-shuffle-variant > $O/rank_${1}_$3.json 2> $O/rank_${1}_$3.err
     echo "[r05j] one rank over the engine's RCCL, $1 x $2 validators, $3 shards: rc $? $(timeout 20 python tools/benchline.py < $O/rank_${1}_$3.json 2>/dev/null | cut -c1-170)"; tail -2 $O/rank_${1}_$3.err | cut -c1-200
   done
 }
@@ -127,7 +127,7 @@ call_k() {
   O=gpurun_out/r05k; mkdir -p $O
   export RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517
   for spec in "configs3 131072 engine" "configs4 524288 engine" "configs3 1048576 committee"; do set -- $spec
-    POSEVO_FORCE_DIST=1 timeout 300 python bench.py --gpus 1 --shape $1 --validators $2 --sharded-mode $3 --steps 100 --warmup 6 --no-cpu-baseline --no-signed-steps --no-slot-cadence --no-shuffle-variant > $O/rank_${1}_$3.json 2> $O/rank_${1}_$3.err
+    POSEVO_FORCE_DIST=1 timeout 300 python bench.py --full --gpus 1 --shape $1 --validators $2 --sharded-mode $3 --steps 100 --warmup 6 --no-cpu-baseline --no-signed-steps --no-slot-cadence --no-shuffle-variant > $O/rank_${1}_$3.json 2> $O/rank_${1}_$3.err
     echo "[r05k] one rank over the engine's RCCL, $1 x $2 validators, $3 shards: rc $? $(timeout 20 python tools/benchline.py < $O/rank_${1}_$3.json 2>/dev/null | cut -c1-170)"; tail -2 $O/rank_${1}_$3.err | cut -c1-200
   done
 }
@@ -137,8 +137,8 @@ call_k() {
 call_l() {
   O=gpurun_out/r05l; mkdir -p $O
   timeout 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver.out 2> $O/driver.err; echo "[r05l] driver command rc $? stdout lines $(wc -l < $O/driver.out)"; timeout 20 python tools/benchline.py < $O/driver.out | cut -c1-120
-  timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-slot-cadence --no-signed-steps > $O/launcher.out 2> $O/launcher.err; echo "[r05l] launcher rc $? stdout lines $(wc -l < $O/launcher.out)"; timeout 20 python tools/benchline.py < $O/launcher.out | cut -c1-120
-  POSEVO_FORCE_DIST=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29542 bench.py --gpus 1 --validators 131072 --steps 20 --warmup 5 > $O/dist.out 2> $O/dist.err; echo "[r05l] N > 1 path, one rank: rc $? stdout lines $(wc -l < $O/dist.out)"; timeout 20 python tools/benchline.py < $O/dist.out | cut -c1-120; grep -c "Gloo\|RCCL version" $O/dist.err
+  timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-slot-cadence --no-signed-steps > $O/launcher.out 2> $O/launcher.err; echo "[r05l] launcher rc $? stdout lines $(wc -l < $O/launcher.out)"; timeout 20 python tools/benchline.py < $O/launcher.out | cut -c1-120
+  POSEVO_FORCE_DIST=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29542 bench.py --full --gpus 1 --validators 131072 --steps 20 --warmup 5 > $O/dist.out 2> $O/dist.err; echo "[r05l] N > 1 path, one rank: rc $? stdout lines $(wc -l < $O/dist.out)"; timeout 20 python tools/benchline.py < $O/dist.out | cut -c1-120; grep -c "Gloo\|RCCL version" $O/dist.err
 }
 
 "call_${1:?letter b..l}"

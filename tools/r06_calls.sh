@@ -50,7 +50,7 @@ call_d() {
   O=gpurun_out/r06d; mkdir -p $O
   timeout 900 python -m pytest tests/test_gpu_pairing.py tests/test_gpu_g2.py -x -q > $O/pytest_sig.log 2>&1; echo "[r06d] pairing + g2 tests rc $?"; tail -6 $O/pytest_sig.log
   for b in 4 1 8; do
-    POSEVO_SIG_BATCH=$b timeout 300 python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant > $O/bench_sig$b.json 2> $O/bench_sig$b.err
+    POSEVO_SIG_BATCH=$b timeout 300 python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant > $O/bench_sig$b.json 2> $O/bench_sig$b.err
     echo "[r06d] sig batch $b: rc $? $(python - <<PY
 import json
 d=json.loads(open("$O/bench_sig$b.json").read().strip().splitlines()[-1])
@@ -60,11 +60,11 @@ PY
 )"
   done
   cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-  rm -rf $O/prof; timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o b -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant --no-verify-steps --no-oracle-check > $O/bench_rocprof.json 2> $O/bench_rocprof.err
+  rm -rf $O/prof; timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof -o b -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant --no-verify-steps --no-oracle-check > $O/bench_rocprof.json 2> $O/bench_rocprof.err
   timeout 120 python tools/rocpd_stats.py $O/prof/b_results.db $O/bench_kernel_stats.txt > /dev/null 2>&1; cut -c1-150 $O/bench_kernel_stats.txt | head -30; rm -rf $O/prof
   export POSEVO_LIB_PATH=$PWD/pos_evolution_amd/libposevo_dbg.so
   for k in 0 1 2; do
-    rm -rf $O/prof; POSEVO_DBG_SKIP=$k timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof -o s -- python bench.py --steps 40 --warmup 6 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant --no-signed-steps --no-verify-steps --no-oracle-check > $O/bench_skip$k.json 2> $O/bench_skip$k.err
+    rm -rf $O/prof; POSEVO_DBG_SKIP=$k timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof -o s -- python bench.py --full --steps 40 --warmup 6 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant --no-signed-steps --no-verify-steps --no-oracle-check > $O/bench_skip$k.json 2> $O/bench_skip$k.err
     timeout 120 python tools/rocpd_stats.py $O/prof/s_results.db $O/skip${k}_kernel_stats.txt > /dev/null 2>&1; echo "== skip $k"; cut -c1-150 $O/skip${k}_kernel_stats.txt | head -12; rm -rf $O/prof
   done
   unset POSEVO_LIB_PATH
@@ -79,7 +79,7 @@ call_e() {
   timeout 1200 python -m pytest tests/test_gpu_shapes.py -x -q -k "timed_path or signed_steps" > $O/pytest_shapes.log 2>&1; echo "[r06e] shapes tests rc $?"; tail -6 $O/pytest_shapes.log
   timeout 300 python tools/sig_epoch.py --calls 3 > $O/sig_epoch_plain.txt 2>&1; cat $O/sig_epoch_plain.txt
   for b in 4 1 8; do
-    POSEVO_SIG_BATCH=$b timeout 300 python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant > $O/bench_sig$b.json 2> $O/bench_sig$b.err
+    POSEVO_SIG_BATCH=$b timeout 300 python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant > $O/bench_sig$b.json 2> $O/bench_sig$b.err
     echo "[r06e] sig batch $b: rc $? $(python - <<PY
 import json
 d=json.loads(open("$O/bench_sig$b.json").read().strip().splitlines()[-1])
@@ -91,7 +91,7 @@ PY
   cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
   export POSEVO_LIB_PATH=$PWD/pos_evolution_amd/libposevo_dbg.so
   for k in 0 1 2 3; do
-    rm -rf $O/prof; POSEVO_DBG_SKIP=$k timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof -o s -- python bench.py --steps 40 --warmup 6 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant --no-signed-steps --no-verify-steps --no-oracle-check > $O/bench_skip$k.json 2> $O/bench_skip$k.err
+    rm -rf $O/prof; POSEVO_DBG_SKIP=$k timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof -o s -- python bench.py --full --steps 40 --warmup 6 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant --no-signed-steps --no-verify-steps --no-oracle-check > $O/bench_skip$k.json 2> $O/bench_skip$k.err
     timeout 120 python tools/rocpd_stats.py $O/prof/s_results.db $O/skip${k}_kernel_stats.txt > /dev/null 2>&1; echo "== skip $k: $(timeout 20 python tools/benchline.py < $O/bench_skip$k.json | cut -c1-60)"; grep -E "k_g1_accumulate|k_g1_finish|k_g1_tree|k_dbg|k_pair" $O/skip${k}_kernel_stats.txt | cut -c1-150; rm -rf $O/prof
   done
   unset POSEVO_LIB_PATH
@@ -110,7 +110,7 @@ call_f() {
   cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
   export POSEVO_LIB_PATH=$PWD/pos_evolution_amd/libposevo_dbg.so
   for k in 0 1 3 2; do
-    rm -rf $O/prof; POSEVO_DBG_SKIP=$k timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof -o s -- python bench.py --steps 40 --warmup 6 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant --no-signed-steps --no-verify-steps --no-oracle-check > $O/bench_skip$k.json 2> $O/bench_skip$k.err
+    rm -rf $O/prof; POSEVO_DBG_SKIP=$k timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof -o s -- python bench.py --full --steps 40 --warmup 6 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant --no-signed-steps --no-verify-steps --no-oracle-check > $O/bench_skip$k.json 2> $O/bench_skip$k.err
     timeout 120 python tools/rocpd_stats.py $O/prof/s_results.db $O/skip${k}_kernel_stats.txt > /dev/null 2>&1; echo "== skip $k: $(timeout 20 python tools/benchline.py < $O/bench_skip$k.json | cut -c1-60)"; grep -E "k_g1_accumulate|k_g1_finish|k_g1_tree|k_dbg" $O/skip${k}_kernel_stats.txt | cut -c1-150; rm -rf $O/prof
   done
   unset POSEVO_LIB_PATH
@@ -124,7 +124,7 @@ call_g() {
   timeout 900 python -m pytest tests/test_gpu_pairing.py tests/test_gpu_g2.py tests/test_gpu_keyvalidate.py -x -q > $O/pytest_sig.log 2>&1; echo "[r06g] pairing + g2 tests rc $?"; tail -6 $O/pytest_sig.log
   timeout 300 python tools/engine_timeline.py --signed --lag 7 --steps 30 --show 8 > $O/engine_timeline_signed.txt 2>&1; tail -24 $O/engine_timeline_signed.txt | cut -c1-70; grep -c g2_decompress $O/engine_timeline_signed.txt
   for b in 4 8; do
-    POSEVO_SIG_BATCH=$b timeout 300 python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant > $O/bench_sig$b.json 2> $O/bench_sig$b.err
+    POSEVO_SIG_BATCH=$b timeout 300 python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant > $O/bench_sig$b.json 2> $O/bench_sig$b.err
     echo "[r06g] sig batch $b: rc $? $(python - <<PY
 import json
 d=json.loads(open("$O/bench_sig$b.json").read().strip().splitlines()[-1])
@@ -133,7 +133,7 @@ print("ms/step", round(d["ms_per_step"],4), "signed", d.get("ms_per_step_with_si
 PY
 )"
   done
-  POSEVO_LIB_PATH=$PWD/build/variants/libposevo_pownoinline.so timeout 300 python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant > $O/bench_pownoinline.json 2> $O/bench_pownoinline.err
+  POSEVO_LIB_PATH=$PWD/build/variants/libposevo_pownoinline.so timeout 300 python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant > $O/bench_pownoinline.json 2> $O/bench_pownoinline.err
   python - <<PY
 import json
 d=json.loads(open("$O/bench_pownoinline.json").read().strip().splitlines()[-1])
@@ -167,7 +167,7 @@ call_i() {
   timeout 900 python -m pytest tests/test_gpu_pairing.py tests/test_gpu_g2.py tests/test_gpu_pipeline.py tests/test_gpu_pipeline_robust.py -x -q > $O/pytest_sig.log 2>&1; echo "[r06i] pairing + g2 + pipeline tests rc $?"; tail -6 $O/pytest_sig.log
   timeout 300 python tools/engine_timeline.py --signed --lag 15 --steps 44 --show 12 > $O/engine_timeline_signed.txt 2>&1; tail -22 $O/engine_timeline_signed.txt | cut -c1-70
   for b in 8 4; do
-    POSEVO_SIG_BATCH=$b POSEVO_HOST_TRACE=1 POSEVO_SLOT_TIMELINE=$O/slot_timeline_$b.txt timeout 300 python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-shuffle-variant > $O/bench_sig$b.json 2> $O/bench_sig$b.err
+    POSEVO_SIG_BATCH=$b POSEVO_HOST_TRACE=1 POSEVO_SLOT_TIMELINE=$O/slot_timeline_$b.txt timeout 300 python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-shuffle-variant > $O/bench_sig$b.json 2> $O/bench_sig$b.err
     echo "[r06i] sig batch $b: rc $? $(python - <<PY
 import json
 d=json.loads(open("$O/bench_sig$b.json").read().strip().splitlines()[-1])
@@ -187,7 +187,7 @@ call_j() {
   timeout 900 python -m pytest tests/test_gpu_pairing.py tests/test_gpu_g2.py tests/test_gpu_pipeline.py tests/test_gpu_pipeline_robust.py -x -q > $O/pytest_sig.log 2>&1; echo "[r06j] pairing + g2 + pipeline tests rc $?"; tail -6 $O/pytest_sig.log
   timeout 300 python tools/engine_timeline.py --signed --lag 15 --steps 44 --show 12 > $O/engine_timeline_signed.txt 2>&1; tail -22 $O/engine_timeline_signed.txt | cut -c1-70
   for b in 8 4 1; do
-    POSEVO_SIG_BATCH=$b POSEVO_HOST_TRACE=1 timeout 300 python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-shuffle-variant --no-slot-cadence > $O/bench_sig$b.json 2> $O/bench_sig$b.err
+    POSEVO_SIG_BATCH=$b POSEVO_HOST_TRACE=1 timeout 300 python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-shuffle-variant --no-slot-cadence > $O/bench_sig$b.json 2> $O/bench_sig$b.err
     echo "[r06j] sig batch $b: rc $? $(python - <<PY
 import json
 d=json.loads(open("$O/bench_sig$b.json").read().strip().splitlines()[-1])
@@ -213,7 +213,7 @@ print("slot p50", sc.get("slot_step_us_p50"), "tick->head", sc.get("tick_to_head
 print("unagg", u.get("ms_per_epoch"), u.get("ms_per_call"), u.get("warmup_ms_per_call"), u.get("roofline_valu",{}).get("frac"))
 PY
   for shape in "configs3 131072" "configs4 524288"; do set -- $shape
-    POSEVO_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --shape $1 --validators $2 --steps 100 --warmup 6 --no-cpu-baseline --no-signed-steps --no-slot-cadence --no-shuffle-variant > $O/rank_$1.json 2> $O/rank_$1.err
+    POSEVO_FORCE_DIST=1 timeout 600 python bench.py --full --gpus 1 --shape $1 --validators $2 --steps 100 --warmup 6 --no-cpu-baseline --no-signed-steps --no-slot-cadence --no-shuffle-variant > $O/rank_$1.json 2> $O/rank_$1.err
     echo "[r06k] per-rank step of an 8-way range shard, $1: rc $? $(timeout 20 python tools/benchline.py < $O/rank_$1.json 2>/dev/null | cut -c1-200)"; done
   bash tools/gpu.sh r06k label:final driver
 }
@@ -225,7 +225,7 @@ call_l() {
   for i in 1 2 3; do bash tools/gpu.sh r06l label:d$i driver; done
   bash tools/gpu.sh r06l label:q quick
   for shape in "configs3 131072" "configs4 524288"; do set -- $shape
-    POSEVO_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --shape $1 --validators $2 --steps 100 --warmup 6 --no-cpu-baseline --no-signed-steps --no-slot-cadence --no-shuffle-variant > $O/rank_$1.json 2> $O/rank_$1.err
+    POSEVO_FORCE_DIST=1 timeout 600 python bench.py --full --gpus 1 --shape $1 --validators $2 --steps 100 --warmup 6 --no-cpu-baseline --no-signed-steps --no-slot-cadence --no-shuffle-variant > $O/rank_$1.json 2> $O/rank_$1.err
     echo "[r06l] per-rank step of an 8-way range shard, $1: rc $? $(timeout 20 python tools/benchline.py < $O/rank_$1.json 2>/dev/null | cut -c1-200)"; done
   timeout 900 python -m pytest tests/test_gpu_shapes.py tests/test_gpu_pairing.py -x -q -k "signed or bench or knobs" > $O/pytest.log 2>&1; echo "[r06l] tests rc $?"; tail -4 $O/pytest.log
 }
@@ -262,7 +262,7 @@ call_q() {
   POSEVO_HOST_TRACE=1 timeout 300 python tools/sig_epoch.py --calls 4 2>&1 | grep "call\|usig" | cut -c1-120
   timeout 300 python tools/engine_timeline.py --steps 24 --show 3 > $O/engine_timeline.txt 2>&1; tail -12 $O/engine_timeline.txt
   timeout 300 python tools/engine_timeline.py --cold 20 --steps 26 > $O/engine_timeline_cold20.txt 2>&1; head -4 $O/engine_timeline_cold20.txt | cut -c1-150
-  timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant > $O/bench.json 2> $O/bench.err
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-slot-cadence --no-shuffle-variant > $O/bench.json 2> $O/bench.err
   python - <<PY
 import json
 d=json.loads(open("$O/bench.json").read().strip().splitlines()[-1]); u=d["with_unaggregated_signatures"]

@@ -14,7 +14,7 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-QUICK = ["--no-cpu-baseline", "--no-slot-cadence", "--no-signed-steps", "--no-shuffle-variant"]
+QUICK = ["--full", "--no-cpu-baseline", "--no-slot-cadence", "--no-signed-steps", "--no-shuffle-variant"]
 
 # name -> (environment, extra arguments, exclusive group)
 KNOBS = {
