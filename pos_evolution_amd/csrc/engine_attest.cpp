@@ -602,7 +602,7 @@ int aggregate_impl(pe_engine* h, const pe_attestation* atts, uint32_t n, const u
         for (uint32_t g = 0; g < ng; ++g) total_pk += gres[g].size;
         uint32_t target = G1_TARGET_LANES;
         if (total_pk >= (1ull << 19)) {
-            // Streaming pipelines: ONE wave per SIMD (65 536 lanes, k = 16 at 1 M validators): the S29 accumulation loses 3 %
+            // Streaming pipelines: ONE wave per SIMD (65 536 lanes, k = 16 at 1 M validators): the accumulation lost 3 % (S29)
             // to its two-wave shape alone (tools/accbench) and leaves every SIMD the registers the guests of a streaming
             // step need -- k_g1_tree, k_g1_finish, k_att_plan, the fork-choice chain all run beside it.  Synchronous calls:
             // the shape the first four large calls measured faster.

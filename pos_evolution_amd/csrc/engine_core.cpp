@@ -512,7 +512,7 @@ void pe_engine_destroy(pe_engine* h)
     if (h->prep_stream) { (void)hipStreamSynchronize(h->prep_stream); (void)hipStreamDestroy(h->prep_stream); }
     if (h->prof_base) (void)hipEventDestroy(h->prof_base);
     h->d_shuffle_scratch.release();
-    h->d_points29.release();
+    h->d_points30.release();
     if (h->comm && rccl().ok) (void)rccl().CommDestroy(h->comm);
     if (h->comm_g1 && rccl().ok) (void)rccl().CommDestroy(h->comm_g1);
     h->d_xchg.release();
@@ -543,7 +543,7 @@ void pe_engine_destroy(pe_engine* h)
                       &h->d_part_cur, &h->d_part_prev, &h->d_tsize, &h->d_tparent, &h->d_trank, &h->d_tleaf,
                       &h->d_tpos, &h->d_tidx, &h->d_direct, &h->d_weights, &h->d_totals, &h->d_head,
                       &h->d_broot_tab, &h->d_broots, &h->d_bslot_pos,
-                      &h->d_partials, &h->d_lane_partials, &h->d_out96, &h->d_tmp_points, &h->d_tmp_be, &h->d_tmp_points29})
+                      &h->d_partials, &h->d_lane_partials, &h->d_out96, &h->d_tmp_points, &h->d_tmp_be, &h->d_tmp_points30})
         b->release();
     for (auto& t : h->tables) {
         t.d_members.release(); t.d_offsets.release(); t.d_inv_comm.release(); t.d_inv_pos.release();

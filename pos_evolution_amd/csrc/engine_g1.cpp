@@ -15,16 +15,16 @@ void g1_stream_guard(pe_engine* h, hipStream_t s)
     if (h->side_ever && s != h->side_stream && s != h->fin_stream && s != h->norm_stream) (void)hipStreamWaitEvent(s, h->ev_join, 0);
 }
 
-// The registry table in the accumulation's field form (k_g1_table_s29), built where the registry is loaded -- on the
+// The registry table in the accumulation's field form (k_g1_table_s30), built where the registry is loaded -- on the
 // engine's stream, which every G1 launch is ordered behind.  (Built lazily inside the first G1 launch -- round 3's S29
 // experiment -- the allocation ran ensure_quiesced INSIDE a streaming pipeline's deferred launch: it completed the
 // current arena, copying the aggregate pubkeys out before k_g1_finish had written them.)
-int build_points29(pe_engine* h, uint64_t n)
+int build_points30(pe_engine* h, uint64_t n)
 {
-    HIP_TRY(h, h->d_points29.ensure(std::max<size_t>(128, 4ull * G1_ROW_WORDS * n)));
-    launch_g1_table_s29(h->stream, h->d_points.as<uint32_t>(), h->d_points29.as<uint32_t>(), n);
+    HIP_TRY(h, h->d_points30.ensure(std::max<size_t>(128, 4ull * G1_ROW_WORDS * n)));
+    launch_g1_table_s30(h->stream, h->d_points.as<uint32_t>(), h->d_points30.as<uint32_t>(), n);
     HIP_TRY(h, hipGetLastError());
-    h->points29_valid = true;
+    h->points30_valid = true;
     return PE_OK;
 }
 
@@ -47,12 +47,12 @@ int launch_g1_planned(pe_engine* h, const uint32_t* d_points, const uint32_t* d_
                            std::max<size_t>(PE_G1_PARTIAL_BYTES, (size_t)PE_G1_PARTIAL_BYTES * plan.n_partials)));
     const size_t lane_bytes = (size_t)G1_LANE_PARTIAL_BYTES * G1_WG * ((plan.n_slots + G1_WG - 1) / G1_WG);
     PE_TRY(ensure_quiesced(h, *lane_partials, std::max<size_t>(PE_G1_PARTIAL_BYTES, lane_bytes)));
-    // the table in the accumulation's field form (S29): the registry's is built at the first use after the registry
+    // the table in the accumulation's field form (S30): the registry's is built at the first use after the registry
     // changed; caller-supplied points (pe_g1_sum, the G1-flavoured signature leg: d_tmp_points) are converted per call
-    const uint32_t* d_points29;
+    const uint32_t* d_points30;
     if (d_points == h->d_points.as<uint32_t>()) {
-        if (!h->points29_valid) return fail(h, PE_ERR_STATE, "the registry's table of the accumulation's field form was not built");
-        d_points29 = h->d_points29.as<uint32_t>();
+        if (!h->points30_valid) return fail(h, PE_ERR_STATE, "the registry's table of the accumulation's field form was not built");
+        d_points30 = h->d_points30.as<uint32_t>();
     } else {
         // caller_rows: the rows of d_tmp_points this call's conversion filled, handed down by the caller (not a
         // side channel on the handle, which another user of that scratch buffer would leave stale)
@@ -61,9 +61,9 @@ int launch_g1_planned(pe_engine* h, const uint32_t* d_points, const uint32_t* d_
             return fail(h, PE_ERR_STATE, "G1 sum over an unknown point table");
         // sized like d_tmp_points, by its callers' rule: engine-owned scratch of calls that complete before they return (a
         // flush from here could complete the current arena in the middle of the call that is filling it)
-        HIP_TRY(h, h->d_tmp_points29.ensure(std::max<size_t>(128, 4ull * G1_ROW_WORDS * n_rows)));
-        launch_g1_table_s29(s, d_points, h->d_tmp_points29.as<uint32_t>(), n_rows);
-        d_points29 = h->d_tmp_points29.as<uint32_t>();
+        HIP_TRY(h, h->d_tmp_points30.ensure(std::max<size_t>(128, 4ull * G1_ROW_WORDS * n_rows)));
+        launch_g1_table_s30(s, d_points, h->d_tmp_points30.as<uint32_t>(), n_rows);
+        d_points30 = h->d_tmp_points30.as<uint32_t>();
     }
     // A side-stream chain of a streaming run: the accumulation may be made the only one of its kind on a CU (Tune::exclusive:
     // the LDS it asks for leaves 78 KB, enough for the fork-choice tree up to 4096 blocks beside it -- an 8192-block tree's
@@ -89,7 +89,7 @@ int launch_g1_planned(pe_engine* h, const uint32_t* d_points, const uint32_t* d_
                 clock_rec[0] = clock_rec[1] = 0;
             }
         }
-        launch_g1_accumulate(s, d_points29, d_members, d_bits, d_groups, plan.n_groups, plan.n_slots,
+        launch_g1_accumulate(s, d_points30, d_members, d_bits, d_groups, plan.n_groups, plan.n_slots,
                              lane_partials->as<uint32_t>(), partials->as<uint32_t>(), plan_dev, d_members1, exclusive, clock_rec);
     }
     hipStream_t ts = fin;  // (on the accumulation's own stream the tree measured 0.433 vs 0.338 ms per step, round 3)
@@ -349,13 +349,13 @@ int pe_set_pubkeys_compressed(pe_engine* h, uint64_t n, const uint8_t* pubkeys48
     if (n == 0) return PE_OK;
     HIP_TRY(h, h->d_points.ensure(4ull * G1_ROW_WORDS * n));
     h->have_points = false;
-    h->points29_valid = false;
+    h->points30_valid = false;
     uint64_t n_bad = 0;
     int rc = g1_decompress_common(h, pubkeys48, n, h->d_points.as<uint32_t>(), nullptr, status, &n_bad);
     if (rc) return rc;
     if (n_bad) return fail(h, PE_ERR_INVALID_ARG, std::to_string(n_bad) + " pubkeys do not decode to curve points (see status[])");
     h->have_points = true;
-    PE_TRY(build_points29(h, n));
+    PE_TRY(build_points30(h, n));
     return PE_OK;
 }
 

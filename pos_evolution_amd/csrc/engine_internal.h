@@ -390,10 +390,10 @@ struct pe_engine {
     float g1_tune_best[2] = {1e30f, 1e30f};
     uint32_t g1_target_slots = 0;   // 0 = undecided
     hipEvent_t g1_tune_ev[2] = {nullptr, nullptr};
-    // k_g1_accumulate reads the registry in the S29 field form: d_points29, built from d_points where the registry is loaded
-    // (build_points29); d_tmp_points29: the same for caller-supplied points (d_tmp_points, `caller_rows` rows), per call
-    bool points29_valid = false;
-    DevBuf d_points29, d_tmp_points29;
+    // k_g1_accumulate reads the registry in the S30 field form: d_points30, built from d_points where the registry is loaded
+    // (build_points30); d_tmp_points30: the same for caller-supplied points (d_tmp_points, `caller_rows` rows), per call
+    bool points30_valid = false;
+    DevBuf d_points30, d_tmp_points30;
 
     // ---- RCCL inside the engine (pe_dist_*): one communicator per handle, collectives on the engine's stream ----
     ncclComm_t comm = nullptr, comm_g1 = nullptr;  // get_head's all-reduce (engine stream) | the G1 partials' all-gather
@@ -728,7 +728,7 @@ void plan_g1(uint32_t n_groups, SizeFn size_of, G1Group* out, G1Plan* plan, uint
 }
 
 void g1_stream_guard(pe_engine* h, hipStream_t s);
-int build_points29(pe_engine* h, uint64_t n);  // after the registry's points changed (n rows)
+int build_points30(pe_engine* h, uint64_t n);  // after the registry's points changed (n rows)
 int launch_g1_planned(pe_engine* h, const uint32_t* d_points, const uint32_t* d_members, const uint32_t* d_bits,
                       const G1Group* d_groups, const G1Plan& plan, uint8_t* d_out96, uint32_t* dev_jac,
                       hipStream_t s = nullptr, hipStream_t fin = nullptr, DevBuf* partials = nullptr,

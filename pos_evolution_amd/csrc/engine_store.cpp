@@ -377,7 +377,7 @@ int pe_set_validators(pe_engine* h, uint64_t n, const uint8_t* pubkeys96, const 
     }
     if (pubkeys96 && n) {
         HIP_TRY(h, h->d_points.ensure(4ull * G1_ROW_WORDS * n));
-        h->points29_valid = false;
+        h->points30_valid = false;
         // convert in chunks through a bounded device staging buffer
         const uint64_t chunk = std::min<uint64_t>(n, 1u << 20);
         HIP_TRY(h, h->d_tmp_be.ensure(96ull * chunk));
@@ -390,7 +390,7 @@ int pe_set_validators(pe_engine* h, uint64_t n, const uint8_t* pubkeys96, const 
         }
         HIP_TRY(h, hipGetLastError());
         h->have_points = true;
-        PE_TRY(build_points29(h, n));  // the registry in the accumulation's field form, now: never inside a G1 launch
+        PE_TRY(build_points30(h, n));  // the registry in the accumulation's field form, now: never inside a G1 launch
     } else if (!pubkeys96) {
         h->have_points = h->have_points && n <= old_n;
     }

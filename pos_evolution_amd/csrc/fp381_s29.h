@@ -13,7 +13,10 @@
 // Round 4 measured (tools/fpbench29, tools/icbench, tools/accbench): 14 % more dependent products per second,
 // 25 % more mixed adds (the squaring is 301 multiply-adds), and the accumulation kernel 158 us against 183 for a million
 // points -- a mixed add of 3 738 multiply-adds runs at the multiplier's issue rate, the simple instructions around them are
-// free and carries are not.  It is the accumulation's form and, since round 6, the tree's; finish and the wire formats stay in fp381.h.
+// free and carries are not.  It was the accumulation's form in rounds 4-6 and the tree's in round 6; since round 7 both compute in
+// S30 (fp381_s30.h: 13 balanced limbs of 30 bits, 338 multiply-adds per product).  What remains on S29: the square roots of
+// the decompression kernels (fp_sqrt.h, fq_pow_pm3d4 below) and the tools that measure this form; finish and the wire formats
+// stay in fp381.h.
 //
 // Lazy, signed values.  R' / p > 2^25, so a product of operands of magnitude < 2^386 (32 p) comes out in (-eps, p + eps)
 // with no final subtraction; a - b is a plain limb-wise subtraction (limbs of both signs are fine in the next product as

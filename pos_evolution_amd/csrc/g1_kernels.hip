@@ -6,24 +6,26 @@
 //
 // Kernels
 //   k_g1_convert     96-B big-endian affine -> Montgomery limbs (registry load, once)
-//   k_g1_table_s29   the registry in the accumulation's field form (14 x 29-bit limbs, fp381_s29.h), once per registry
-//   k_g1_accumulate  HOT: per-lane XYZZ accumulation of k gathered points (mixed adds over the S29 form), one
+//   k_g1_table_s30   the registry in the accumulation's field form (13 x 30-bit balanced digits, fp381_s30.h), once per
+//                    registry
+//   k_g1_accumulate  HOT: per-lane XYZZ accumulation of k gathered points (mixed adds over the S30 form), one
 //                    partial per lane slot
 //   k_g1_tree        the compacting pairwise tree over a workgroup's 256 partials staged in LDS (limb-major), one XYZZ
 //                    partial out per (group, workgroup)
 //   k_g1_finish      per group: add the few workgroup (or rank) partials, normalise
 //                    to canonical affine, store big-endian
 //
-// Bound: integer VALU (a mixed add = 8 products + 2 squarings = 3 738 v_mad_[iu]64_[iu]32 per 100 bytes gathered), not
-// HBM and not MFMA -- see DESIGN.md "G1 roofline".  Two field forms live here: the accumulation computes in S29 (one
-// multiply-add per limb product, no carry instructions: 25 % faster per mixed add); tree, finish, wire formats and key
-// validation compute in 12 x 32-bit limbs (fp381.h) -- latency-bound guests whose products are CALLS to one copy of the
-// code, so that what they cost the accumulation is not a 64 KB instruction cache full of their unrolled products.
+// Bound: integer VALU (a mixed add = 8 products + 2 squarings = 3 224 v_mad_i64_i32 per 100 bytes gathered), not HBM and
+// not MFMA -- see DESIGN.md "G1 roofline".  Three field forms live here: accumulation and tree compute in S30 (fp381_s30.h,
+// 13 balanced limbs of 30 bits: one multiply-add per limb product, no carry instructions; round 7, 3 224 multiply-adds per
+// mixed add where S29 took 3 738); the square roots of the decompression compute in S29 (fp_sqrt.h, fp381_s29.h); finish,
+// wire formats and key validation in 12 x 32-bit limbs (fp381.h) -- latency-bound guests whose products are CALLS to one copy
+// of the code, so that what they cost the accumulation is not a 64 KB instruction cache full of their unrolled products.
 #define POSEVO_FP_MUL_CALLED 1  // every 12 x 32-bit product of this file's kernels is a call (see fp381.h)
 #include <algorithm>
 #include <hip/hip_ext.h>
 #include "g1.h"
-#include "g1_s29.h"
+#include "g1_s30.h"
 #include "fp_sqrt.h"
 #include "kernels.h"
 
@@ -294,23 +296,24 @@ __device__ unsigned long long g1_wave_info[3 * 4 * 4096];  // per wave: HW_ID | 
 #define G1_STAMP(i) do { } while (0)
 #endif
 
+namespace s30 {
 // ONE copy of the product and of the squaring for everything that is not the loop body (the hand-over of a finished
-// accumulator, the complete add of the rare path): called, arguments and result in registers.
+// accumulator, the complete add of the rare path, the tree's cooperative adds): called, arguments and result in registers.
 __device__ __noinline__ fq fq_mul_nc(int32_t a0, int32_t a1, int32_t a2, int32_t a3, int32_t a4, int32_t a5, int32_t a6,
-                                     int32_t a7, int32_t a8, int32_t a9, int32_t a10, int32_t a11, int32_t a12, int32_t a13,
+                                     int32_t a7, int32_t a8, int32_t a9, int32_t a10, int32_t a11, int32_t a12,
                                      int32_t b0, int32_t b1, int32_t b2, int32_t b3, int32_t b4, int32_t b5, int32_t b6,
-                                     int32_t b7, int32_t b8, int32_t b9, int32_t b10, int32_t b11, int32_t b12, int32_t b13)
+                                     int32_t b7, int32_t b8, int32_t b9, int32_t b10, int32_t b11, int32_t b12)
 {
-    const fq a = {{a0, a1, a2, a3, a4, a5, a6, a7, a8, a9, a10, a11, a12, a13}};
-    const fq b = {{b0, b1, b2, b3, b4, b5, b6, b7, b8, b9, b10, b11, b12, b13}};
+    const fq a = {{a0, a1, a2, a3, a4, a5, a6, a7, a8, a9, a10, a11, a12}};
+    const fq b = {{b0, b1, b2, b3, b4, b5, b6, b7, b8, b9, b10, b11, b12}};
     fq r;
     fq_mul(r, a, b);
     return r;
 }
 __device__ __noinline__ fq fq_sqr_nc(int32_t a0, int32_t a1, int32_t a2, int32_t a3, int32_t a4, int32_t a5, int32_t a6,
-                                     int32_t a7, int32_t a8, int32_t a9, int32_t a10, int32_t a11, int32_t a12, int32_t a13)
+                                     int32_t a7, int32_t a8, int32_t a9, int32_t a10, int32_t a11, int32_t a12)
 {
-    const fq a = {{a0, a1, a2, a3, a4, a5, a6, a7, a8, a9, a10, a11, a12, a13}};
+    const fq a = {{a0, a1, a2, a3, a4, a5, a6, a7, a8, a9, a10, a11, a12}};
     fq r;
     fq_sqr(r, a);
     return r;
@@ -319,24 +322,23 @@ struct FqCalled {
     __device__ __forceinline__ static void mul(fq& r, const fq& a, const fq& b)
     {
         r = fq_mul_nc(a.l[0], a.l[1], a.l[2], a.l[3], a.l[4], a.l[5], a.l[6], a.l[7], a.l[8], a.l[9], a.l[10], a.l[11],
-                      a.l[12], a.l[13], b.l[0], b.l[1], b.l[2], b.l[3], b.l[4], b.l[5], b.l[6], b.l[7], b.l[8], b.l[9],
-                      b.l[10], b.l[11], b.l[12], b.l[13]);
+                      a.l[12], b.l[0], b.l[1], b.l[2], b.l[3], b.l[4], b.l[5], b.l[6], b.l[7], b.l[8], b.l[9], b.l[10],
+                      b.l[11], b.l[12]);
     }
     __device__ __forceinline__ static void sqr(fq& r, const fq& a)
     {
         r = fq_sqr_nc(a.l[0], a.l[1], a.l[2], a.l[3], a.l[4], a.l[5], a.l[6], a.l[7], a.l[8], a.l[9], a.l[10], a.l[11],
-                      a.l[12], a.l[13]);
+                      a.l[12]);
     }
 };
 
-
-// ---------------------------------------------------------------- the tree's S29 helpers (round 6)
-// The lanes' partials reach the tree in the accumulation's own field form: X | Y | ZZ | ZZZ as 14 limbs each (56 words, X and
-// Y carry-passed, ZZ and ZZZ products; all limbs zero = infinity).  Round 4-5 converted every lane's accumulator to the 12 x 32
-// form first (four products + four exact reductions per LANE, inside the kernel that paces the step); now the tree adds in
-// S29 and converts once per GROUP, at the block's last level.  Same formulas as g1.h's two- and four-lane cooperative adds;
-// what differs is the lazy form's bookkeeping: a difference of two balanced values goes into the next product as it is,
-// X3 = RR - PPP - 2 Q (three terms) and Y3 (stored) take one carry pass each.
+// ---------------------------------------------------------------- the tree's S30 helpers
+// The lanes' partials reach the tree in the accumulation's own field form: X | Y | ZZ | ZZZ as 13 limbs each (52 words, X and
+// Y carry-passed or a table row, ZZ and ZZZ products; all limbs zero = infinity).  Round 4-5 converted every lane's
+// accumulator to the 12 x 32 form first (four products + four exact reductions per LANE, inside the kernel that paces the
+// step); since round 6 the tree adds in the accumulation's form and converts once per GROUP, at the block's last level.  Same
+// formulas as g1.h's two- and four-lane cooperative adds; what differs is the lazy form's bookkeeping (g1_s30.h): every
+// difference that feeds a product, X3 = RR - PPP - 2 Q and Y3 take one carry pass each.
 constexpr int G1S_WORDS = 4 * FQ_N;
 __device__ __forceinline__ void fq_select(fq& r, bool c, const fq& a, const fq& b)  // r = c ? a : b
 {
@@ -383,7 +385,7 @@ __device__ __forceinline__ void global_store_fq_as_mont32(uint32_t* __restrict__
     d[1] = make_uint4(w[4], w[5], w[6], w[7]);
     d[2] = make_uint4(w[8], w[9], w[10], w[11]);
 }
-// p += q, both XYZZ in S29, every case of the group law (g1_s29.h: g1q_add) over the called products: the rare path of the
+// p += q, both XYZZ in S30, every case of the group law (g1_s30.h: g1q_add) over the called products: the rare path of the
 // cooperative adds (an infinity operand, P1 = +-P2)
 __device__ __noinline__ void g1q_add_full(g1q& p, const g1q& q) { g1q_add<FqCalled>(p, q); }
 // two lanes per pair (g1.h: g1x_add_pair).  role 0 owns P1, role 1 owns P2; neither is infinity (caller).  false: P1 = +-P2.
@@ -403,8 +405,8 @@ __device__ __forceinline__ bool g1s_add_pair(fq& out_a, fq& out_b, bool role, co
         fq_select(U2, role, m1, o1);
         fq_select(S1, role, o2, m2);
         fq_select(S2, role, m2, o2);
-        fq_sub(P, U2, U1);
-        fq_sub(R, S2, S1);
+        fq_sub_norm(P, U2, U1);
+        fq_sub_norm(R, S2, S1);
     }
     if (fq_is_zero_modp(P)) return false;  // identical in both lanes of the pair
     fq a, b, m3, x3, m4, x4, m5;
@@ -420,7 +422,7 @@ __device__ __forceinline__ bool g1s_add_pair(fq& out_a, fq& out_b, bool role, co
     FqCalled::mul(m5, a, b);  // Q | ZZZ1*ZZZ2
     fq X3, T, t;
     fq_sub_sub2_norm(X3, x3, m4, m5);  // role 0: RR - PPP - 2 Q   (role 1 computes don't-cares of the same magnitudes)
-    fq_sub(T, m5, X3);
+    fq_sub_norm(T, m5, X3);
     fq m6, m7;
     fq_select(a, role, m4, R);   // ZZ1*ZZ2   | R
     fq_select(b, role, x3, T);   // PP        | Q - X3
@@ -443,7 +445,7 @@ __device__ __forceinline__ bool g1s_add_quad(fq& out_a, fq& out_b, int q, const 
     FqCalled::mul(m1, a, b);          // U1 | U2 | S1 | S2
     fq_select(send, even, b, m1);     // q0: ZZ2, q1: U2, q2: ZZZ2, q3: S2
     fq_xchg(t, send);                 // q0: U2,  q1: ZZ2, q2: S2,  q3: ZZZ2
-    fq_sub(d, t, m1);                 // q0: P,   q2: R   (odd lanes: unused)
+    fq_sub_norm(d, t, m1);            // q0: P,   q2: R   (odd lanes: unused)
     const int p_zero = __shfl((int)fq_is_zero_modp(d), base, 64);
     if (p_zero) return false;         // identical in the four lanes
     fq x, y, m2;
@@ -463,7 +465,7 @@ __device__ __forceinline__ bool g1s_add_quad(fq& out_a, fq& out_b, int q, const 
     fq_from_lane(s1, m1, base + 2);   // S1 to everyone (q0 needs it)
     fq X3, T, tmp;
     fq_sub_sub2_norm(X3, m2, ppp, m3);  // q2: X3 = RR - PPP - 2 Q
-    fq_sub(T, m3, X3);                  // q2: Q - X3
+    fq_sub_norm(T, m3, X3);             // q2: Q - X3
     fq m4;
     fq_select(sel, q == 2, d, m2);
     fq_select(x, q == 0, s1, sel);    // q0: S1, q2: R, q3: B (q1: A, unused)
@@ -480,9 +482,9 @@ __device__ __forceinline__ bool g1s_add_quad(fq& out_a, fq& out_b, int q, const 
 }
 
 // The sum of one launch runs in THREE kernels since round 2:
-//   k_g1_accumulate  per-lane XYZZ accumulation of k gathered points (mixed adds, S29 form since round 4): throughput-
-//                    bound, at the multiplier's issue floor; writes one partial per lane slot, limb-major per workgroup
-//                    (coalesced), already in the 12 x 32-bit words the tree reads;
+//   k_g1_accumulate  per-lane XYZZ accumulation of k gathered points (mixed adds, S29 form in rounds 4-6, S30 since round 7):
+//                    throughput-bound, at the multiplier's issue floor; writes one partial per lane slot, limb-major per
+//                    workgroup (coalesced), in its own field form;
 //   k_g1_tree        the compacting pairwise tree over each workgroup's 256 partials (LDS, two- and four-lane
 //                    cooperative adds): latency-bound, a level is one full add deep;
 //   k_g1_finish      adds the few workgroup partials of a wide group and normalises.
@@ -511,17 +513,17 @@ __device__ __forceinline__ void g1_slot_block(const G1Group* __restrict__ groups
     }
 }
 
-// lane partials in HBM: word k of lane `tid` of workgroup `wg` at ((wg * 56 + k) * 256 + tid): a wave's 64 lanes write
-// 256 contiguous bytes per word (k_g1_accumulate's hand-over writes them -- S29 limbs, round 6 --, k_g1_tree reads them into LDS)
+// lane partials in HBM: word k of lane `tid` of workgroup `wg` at ((wg * 52 + k) * 256 + tid): a wave's 64 lanes write
+// 256 contiguous bytes per word (k_g1_accumulate's hand-over writes them -- S30 limbs --, k_g1_tree reads them into LDS)
 
 // Two waves per SIMD: the shape that fits beside ONE wave of the next aggregate's k_g1_accumulate (<= 256 VGPRs) on every SIMD,
 // which is how streaming steps run it (round 4).
 //
 // The body is shared by two kernels that differ in their resource signature only (launch_g1_tree):
 //   k_g1_tree       <= 256 registers: two of its workgroups fit a CU's register file; the 84 KB LDS request keeps them apart;
-//   k_g1_tree_solo  the same code + eight accumulation registers nobody reads (264 in all): two of ITS workgroups never share
-//                   a SIMD whatever the LDS says, while one still fits beside an accumulation wave (232 + 264 <= 512).  That
-//                   frees the LDS for the accumulation's own exclusion (launch_g1_accumulate, `exclusive`).
+//   k_g1_tree_solo  the same code + accumulation registers nobody reads (more than 256 in all): two of ITS workgroups never
+//                   share a SIMD whatever the LDS says, while one still fits beside an accumulation wave.  That frees the LDS
+//                   for the accumulation's own exclusion (launch_g1_accumulate, `exclusive`).
 template <bool SOLO>
 __device__ __forceinline__ void g1_tree_body(const uint32_t* __restrict__ lane_partials, const G1Group* __restrict__ groups,
                                              uint32_t n_groups, uint32_t n_slots, uint32_t* __restrict__ wg_partials,
@@ -532,7 +534,7 @@ __device__ __forceinline__ void g1_tree_body(const uint32_t* __restrict__ lane_p
         n_groups = plan_dev->n_groups;
         n_slots = plan_dev->n_slots;
     }
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];  // 56*256 partial words + 2*256 block info
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];  // 52*256 partial words + 2*256 block info
     uint32_t* lds_out = lds + G1S_WORDS * G1_WG;  // output slot of the block a partial belongs to
     uint32_t* lds_sz = lds_out + G1_WG;           // current block size (0 = empty / retired)
     const int tid = threadIdx.x;
@@ -681,69 +683,74 @@ __device__ __forceinline__ void g1_tree_body(const uint32_t* __restrict__ lane_p
     }
     }  // slabs (the level loop ends behind a barrier: the next slab may overwrite the LDS)
 }
+}  // namespace s30
 
 __global__ void __launch_bounds__(G1_WG) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_g1_tree(const uint32_t* __restrict__ lane_partials, const G1Group* __restrict__ groups, uint32_t n_groups,
           uint32_t n_slots, uint32_t* __restrict__ wg_partials, const AttPlan* __restrict__ plan_dev)
 {
-    g1_tree_body<false>(lane_partials, groups, n_groups, n_slots, wg_partials, plan_dev);
+    s30::g1_tree_body<false>(lane_partials, groups, n_groups, n_slots, wg_partials, plan_dev);
 }
 __global__ void __launch_bounds__(G1_WG) __attribute__((amdgpu_waves_per_eu(1, 1), amdgpu_num_vgpr(256)))
 k_g1_tree_solo(const uint32_t* __restrict__ lane_partials, const G1Group* __restrict__ groups, uint32_t n_groups,
                uint32_t n_slots, uint32_t* __restrict__ wg_partials, const AttPlan* __restrict__ plan_dev)
 {
-    g1_tree_body<true>(lane_partials, groups, n_groups, n_slots, wg_partials, plan_dev);
+    s30::g1_tree_body<true>(lane_partials, groups, n_groups, n_slots, wg_partials, plan_dev);
 }
 
-// ---------------------------------------------------------------- the accumulation (S29 field form)
-// (fp381_s29.h / g1_s29.h: 14 signed limbs of 29 bits, one v_mad_i64_i32 per limb product, no carry instructions.)
-// Tree and finish read 12 x 32-bit words: a lane converts its finished accumulator (four products + four exact
-// reductions per lane).  Round 3 kept a 12 x 32-bit accumulation kernel beside this one (inline-asm columns of
-// v_mad_u64_u32 + v_addc_co_u32: 288 multiply-adds AND 288 carry adds per product); measured back to back on one box by
-// tools/accbench.hip at 1 M points it took 183 us where this kernel takes 158 (170 at one wave per SIMD, where the other
-// took 219) -- identical lane partials, word for word -- and it was deleted.
-// The registry table of this form: one 128-byte row per validator like the 32-bit table -- x limbs in words 0..13,
-// y limbs in words 14..27 (canonical, Montgomery constant 2^406), word 28 = 1 when the row holds a point.
+// ---------------------------------------------------------------- the accumulation (S30 field form)
+// (fp381_s30.h / g1_s30.h: 13 signed limbs of 30 bits, one v_mad_i64_i32 per limb product, no carry instructions; every
+// product operand a balanced digit, so a mixed add is 3 224 multiply-adds -- S29, rounds 4-6: 14 limbs of 29 bits, 3 738.)
+// Round 3 kept a 12 x 32-bit accumulation kernel beside the S29 one (inline-asm columns of v_mad_u64_u32 + v_addc_co_u32:
+// 288 multiply-adds AND 288 carry adds per product); measured back to back by tools/accbench.hip at 1 M points it took 183
+// us where the S29 kernel took 158 -- identical lane partials, word for word -- and it was deleted.
+// The registry table of this form: one 128-byte row per validator like the 32-bit table -- x in words 0..12, y in words
+// 13..25 (balanced digits of the canonical residue, Montgomery constant 2^390), word 26 = 1 when the row holds a point.
 __global__ void __launch_bounds__(256)
-k_g1_table_s29(const uint32_t* __restrict__ pts32, uint32_t* __restrict__ pts29, uint64_t n)
+k_g1_table_s30(const uint32_t* __restrict__ pts32, uint32_t* __restrict__ pts30, uint64_t n)
 {
+    using s30::FQ_N;
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const uint32_t* src = pts32 + (uint64_t)G1_ROW_WORDS * i;
     uint32_t w[24], any = 0;
 #pragma unroll
     for (int k = 0; k < 24; ++k) { w[k] = src[k]; any |= w[k]; }
-    uint32_t* dst = pts29 + (uint64_t)G1_ROW_WORDS * i;
-    fq x, y;
-    fq_set_zero(x);
-    fq_set_zero(y);
+    uint32_t* dst = pts30 + (uint64_t)G1_ROW_WORDS * i;
+    s30::fq x, y;
+    s30::fq_set_zero(x);
+    s30::fq_set_zero(y);
     if (any) {
-        fq_from_mont32(x, w);
-        fq_from_mont32(y, w + 12);
+        s30::fq_from_mont32(x, w);
+        s30::fq_from_mont32(y, w + 12);
     }
 #pragma unroll
     for (int k = 0; k < FQ_N; ++k) { dst[k] = (uint32_t)x.l[k]; dst[FQ_N + k] = (uint32_t)y.l[k]; }
-    dst[28] = any ? 1u : 0u;
-    dst[29] = dst[30] = dst[31] = 0;
+    dst[2 * FQ_N] = any ? 1u : 0u;
+#pragma unroll
+    for (int k = 2 * FQ_N + 1; k < G1_ROW_WORDS; ++k) dst[k] = 0;
 }
 
-__device__ __forceinline__ bool load_point_s29(fq& x, fq& y, const uint32_t* __restrict__ pts29, uint32_t idx)
+namespace s30 {
+static_assert(2 * FQ_N + 1 <= 28, "a row of the S30 table is read as seven 16-byte vectors");
+__device__ __forceinline__ bool load_point_s30(fq& x, fq& y, const uint32_t* __restrict__ pts30, uint32_t idx)
 {
-    const uint4* p = reinterpret_cast<const uint4*>(pts29 + (uint64_t)G1_ROW_WORDS * idx);  // one 128-byte line per point
-    const uint4 v0 = p[0], v1 = p[1], v2 = p[2], v3 = p[3], v4 = p[4], v5 = p[5], v6 = p[6], v7 = p[7];
+    const uint4* p = reinterpret_cast<const uint4*>(pts30 + (uint64_t)G1_ROW_WORDS * idx);  // one 128-byte line per point
+    const uint4 v0 = p[0], v1 = p[1], v2 = p[2], v3 = p[3], v4 = p[4], v5 = p[5], v6 = p[6];
     x.l[0] = v0.x; x.l[1] = v0.y; x.l[2] = v0.z; x.l[3] = v0.w;
     x.l[4] = v1.x; x.l[5] = v1.y; x.l[6] = v1.z; x.l[7] = v1.w;
     x.l[8] = v2.x; x.l[9] = v2.y; x.l[10] = v2.z; x.l[11] = v2.w;
-    x.l[12] = v3.x; x.l[13] = v3.y;
-    y.l[0] = v3.z; y.l[1] = v3.w;
-    y.l[2] = v4.x; y.l[3] = v4.y; y.l[4] = v4.z; y.l[5] = v4.w;
-    y.l[6] = v5.x; y.l[7] = v5.y; y.l[8] = v5.z; y.l[9] = v5.w;
-    y.l[10] = v6.x; y.l[11] = v6.y; y.l[12] = v6.z; y.l[13] = v6.w;
-    return v7.x != 0;  // the row holds a point
+    x.l[12] = v3.x;
+    y.l[0] = v3.y; y.l[1] = v3.z; y.l[2] = v3.w;
+    y.l[3] = v4.x; y.l[4] = v4.y; y.l[5] = v4.z; y.l[6] = v4.w;
+    y.l[7] = v5.x; y.l[8] = v5.y; y.l[9] = v5.z; y.l[10] = v5.w;
+    y.l[11] = v6.x; y.l[12] = v6.y;
+    return v6.z != 0;  // the row holds a point
 }
+}  // namespace s30
 
 // The accumulation.  What shapes it (round 4, tools/icbench.hip): the instruction cache.  A lane's loop holds ONE
-// straight-line body -- the general mixed add, g1q_madd_fast: eight products + two squarings, ~38 KB -- and nothing else:
+// straight-line body -- the general mixed add, g1q_madd_fast: eight products + two squarings -- and nothing else:
 //   * a lane's first point becomes the accumulator (x, y, 1, 1) as it is, and its first add is a general one (ten products
 //     instead of the six of an affine + affine add: +5 % products, against a second 27 KB body that every wave fetched
 //     once per run of eight);
@@ -755,12 +762,13 @@ __device__ __forceinline__ bool load_point_s29(fq& x, fq& y, const uint32_t* __r
 // Round 3's version of this kernel (three inlined bodies + doubling twice + an unrolled hand-over: 214 KB of code) ran its
 // 1 M-point launch in 0.273 ms where the 12 x 32-bit kernel took 0.226 -- with a product that is 14 % and a mixed add that
 // is 25 % FASTER in a loop that fits the cache (tools/fpbench29).
-__global__ void __launch_bounds__(G1_WG) __attribute__((amdgpu_waves_per_eu(2, 2)))
-k_g1_accumulate(const uint32_t* __restrict__ pts29, const uint32_t* __restrict__ members,
-                    const uint32_t* __restrict__ bit_arena, const G1Group* __restrict__ groups, uint32_t n_groups,
-                    uint32_t n_slots, uint32_t* __restrict__ lane_partials, uint32_t* __restrict__ wg_partials,
-                    const AttPlan* __restrict__ plan_dev, const uint32_t* __restrict__ members1,
-                    unsigned long long* __restrict__ clock_rec)
+namespace s30 {
+__device__ __forceinline__ void g1_accumulate_body(const uint32_t* __restrict__ pts30, const uint32_t* __restrict__ members,
+                                                   const uint32_t* __restrict__ bit_arena, const G1Group* __restrict__ groups,
+                                                   uint32_t n_groups, uint32_t n_slots, uint32_t* __restrict__ lane_partials,
+                                                   uint32_t* __restrict__ wg_partials, const AttPlan* __restrict__ plan_dev,
+                                                   const uint32_t* __restrict__ members1,
+                                                   unsigned long long* __restrict__ clock_rec)
 {
     const int tid = threadIdx.x;
     if (plan_dev) {
@@ -807,7 +815,7 @@ k_g1_accumulate(const uint32_t* __restrict__ pts29, const uint32_t* __restrict__
     auto fetch = [&](uint32_t j, fq& ox, fq& oy) -> bool {  // complete, for the rare path
         uint32_t idx;
         if (!want(j, idx)) return false;
-        return load_point_s29(ox, oy, pts29, idx);
+        return load_point_s30(ox, oy, pts30, idx);
     };
     {
         fq qx, qy, nx, ny;
@@ -815,14 +823,14 @@ k_g1_accumulate(const uint32_t* __restrict__ pts29, const uint32_t* __restrict__
         uint32_t i1 = 0, i2 = 0;
         if (count > 0) {
             uint32_t i0;
-            if (want(0, i0)) have = load_point_s29(qx, qy, pts29, i0);
+            if (want(0, i0)) have = load_point_s30(qx, qy, pts30, i0);
         }
         if (count > 1) w1 = want(1, i1);
         for (uint32_t j = 0; j < count; ++j) {
             w2 = false;
             if (j + 2 < count) w2 = want(j + 2, i2);
             nhave = false;
-            if (w1) nhave = load_point_s29(nx, ny, pts29, i1);
+            if (w1) nhave = load_point_s30(nx, ny, pts30, i1);
             if (have) {
                 if (acc.inf) g1q_set_first(acc, qx, qy);
                 else g1q_madd_fast(acc, qx, qy, exc);
@@ -840,9 +848,9 @@ k_g1_accumulate(const uint32_t* __restrict__ pts29, const uint32_t* __restrict__
             if (fetch(j, qx, qy)) g1q_add_affine<FqCalled>(acc, qx, qy, false);
         }
     }
-    // hand-over: the accumulator as it is -- X | Y | ZZ | ZZZ, 14 limbs each, limb-major per workgroup; all limbs zero for
+    // hand-over: the accumulator as it is -- X | Y | ZZ | ZZZ, 13 limbs each, limb-major per workgroup; all limbs zero for
     // infinity.  (Rounds 4-5 converted every lane's accumulator to the 12 x 32 words here: four products and four exact
-    // reductions per lane inside the kernel that paces the step; k_g1_tree adds in S29 now and converts once per group.)
+    // reductions per lane inside the kernel that paces the step; k_g1_tree adds in the same form and converts once per group.)
     uint32_t* b = lane_partials + (size_t)blockIdx.x * G1S_WORDS * G1_WG + tid;
     const bool inf = acc.inf;
 #pragma unroll
@@ -870,13 +878,25 @@ k_g1_accumulate(const uint32_t* __restrict__ pts29, const uint32_t* __restrict__
         clock_rec[1] = clock64() - rec_c0;
     }
 }
+}  // namespace s30
 
-void launch_g1_table_s29(hipStream_t s, const uint32_t* points_mont24, uint32_t* points_s29, uint64_t n)
+__global__ void __launch_bounds__(G1_WG) __attribute__((amdgpu_waves_per_eu(2, 2)))
+k_g1_accumulate(const uint32_t* __restrict__ pts30, const uint32_t* __restrict__ members,
+                const uint32_t* __restrict__ bit_arena, const G1Group* __restrict__ groups, uint32_t n_groups,
+                uint32_t n_slots, uint32_t* __restrict__ lane_partials, uint32_t* __restrict__ wg_partials,
+                const AttPlan* __restrict__ plan_dev, const uint32_t* __restrict__ members1,
+                unsigned long long* __restrict__ clock_rec)
+{
+    s30::g1_accumulate_body(pts30, members, bit_arena, groups, n_groups, n_slots, lane_partials, wg_partials, plan_dev,
+                            members1, clock_rec);
+}
+
+void launch_g1_table_s30(hipStream_t s, const uint32_t* points_mont24, uint32_t* points_s30, uint64_t n)
 {
     if (n == 0) return;
-    hipLaunchKernelGGL(k_g1_table_s29, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, points_mont24, points_s29, n);
+    hipLaunchKernelGGL(k_g1_table_s30, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, points_mont24, points_s30, n);
 }
-void launch_g1_accumulate(hipStream_t s, const uint32_t* points_s29, const uint32_t* members,
+void launch_g1_accumulate(hipStream_t s, const uint32_t* points_s30, const uint32_t* members,
                               const uint32_t* bit_arena, const G1Group* groups, uint32_t n_groups, uint32_t n_slots,
                               uint32_t* lane_partials, uint32_t* wg_partials48, const AttPlan* plan_dev,
                               const uint32_t* members1, int exclusive, unsigned long long* clock_rec)
@@ -888,7 +908,7 @@ void launch_g1_accumulate(hipStream_t s, const uint32_t* points_s29, const uint3
     // dispatcher does double workgroups up on a CU whenever it finds the others busy for a moment (k_g1_tree of the previous
     // step arriving in the same microsecond; the first CUs to retire a predecessor's workgroup): those eight waves then run
     // at half speed for the whole launch, 330-370 us instead of 205-240 in up to six steps of twenty
-    // (profiles/r05_engine_timeline_cold20_before_exclusive.txt).  78 KB stay for the guests: k_g1_tree_solo (58 KB), the fork-choice
+    // (profiles/r05_engine_timeline_cold20_before_exclusive.txt).  78 KB stay for the guests: k_g1_tree_solo (54 KB), the fork-choice
     // tree up to 4096 blocks (66 KB), the vote histograms (32 KB each).
     size_t lds_bytes = 0;
     if (exclusive) {
@@ -897,11 +917,11 @@ void launch_g1_accumulate(hipStream_t s, const uint32_t* points_s29, const uint3
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_g1_accumulate), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)G1_ACC_EXCLUSIVE_LDS);
     }
-    hipLaunchKernelGGL(k_g1_accumulate, dim3(blocks), dim3(G1_WG), lds_bytes, s, points_s29, members, bit_arena,
+    hipLaunchKernelGGL(k_g1_accumulate, dim3(blocks), dim3(G1_WG), lds_bytes, s, points_s30, members, bit_arena,
                        groups, n_groups, n_slots, lane_partials, wg_partials48, plan_dev, members1, clock_rec);
 }
 
-// one_per_cu (the tree of a streaming step, on its own stream): ask for 84 KB of LDS instead of the 58 KB the kernel uses,
+// one_per_cu (the tree of a streaming step, on its own stream): ask for 84 KB of LDS instead of the 54 KB the kernel uses,
 // so that a CU (160 KB) never holds two of its workgroups.  Two reasons, one per round:
 //  * round 2: the tree of step N runs when the accumulation of step N retires -- which is when the fork-choice kernels of step
 //    N+1 arrive, and k_tree's single workgroup (82 KB of LDS at 4096 blocks) found no CU with room until this kernel had
@@ -920,16 +940,16 @@ void launch_g1_accumulate(hipStream_t s, const uint32_t* points_s29, const uint3
 //  * round 5 (`solo`, the default of streaming steps): the padding moved to the ACCUMULATION, which asks for 82 KB it never
 //    touches (launch_g1_accumulate, `exclusive`) -- that rules its doubling-up out whatever arrives when, which the 84 KB here
 //    only made rarer (6 steps of 20 at 340-370 us on one box, profiles/r05_engine_timeline_cold20_before_exclusive.txt); this kernel then
-//    keeps its workgroups apart by registers instead (k_g1_tree_solo: 264 + 264 > 512) and asks for the 58 KB it uses.
+//    keeps its workgroups apart by registers instead (k_g1_tree_solo: more than 256 registers) and asks for the 54 KB it uses.
 void launch_g1_tree(hipStream_t s, const uint32_t* lane_partials, const G1Group* groups, uint32_t n_groups,
                     uint32_t n_slots, uint32_t* wg_partials48, int one_per_cu, const AttPlan* plan_dev, int solo)
 {
     if (n_groups == 0 || n_slots == 0) return;
     const unsigned blocks = (n_slots + G1_WG - 1) / G1_WG;
-    size_t lds_bytes = (G1S_WORDS + 2) * G1_WG * sizeof(uint32_t);
+    size_t lds_bytes = (s30::G1S_WORDS + 2) * G1_WG * sizeof(uint32_t);
     if (solo) {
         // beside an accumulation that asks for G1_ACC_EXCLUSIVE_LDS: one workgroup per CU by registers (264), the LDS request
-        // is what the kernel uses (58 KB)
+        // is what the kernel uses (54 KB)
         hipLaunchKernelGGL(k_g1_tree_solo, dim3(blocks), dim3(G1_WG), lds_bytes, s, lane_partials, groups, n_groups, n_slots,
                            wg_partials48, plan_dev);
         return;

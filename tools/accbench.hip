@@ -29,7 +29,7 @@ int main(int argc, char** argv)
         members[i] = (uint32_t)i;
     }
     std::shuffle(members.begin(), members.end(), rng);
-    uint32_t *d_pts, *d_pts29, *d_mem, *d_lane, *d_lane2, *d_wg, *d_bits;
+    uint32_t *d_pts, *d_pts30, *d_mem, *d_lane, *d_lane2, *d_wg, *d_bits;
     const int with_bits = argc > 2 ? atoi(argv[2]) : 0;   // 1: every group has a bitfield (99 % of the bits set)
     {
         std::vector<uint32_t> bits((size_t)NG * ((SIZE + 31) / 32));
@@ -39,11 +39,11 @@ int main(int argc, char** argv)
     }
     G1Group* d_groups;
     CHECK(hipMalloc(&d_pts, pts.size() * 4));
-    CHECK(hipMalloc(&d_pts29, pts.size() * 4));
+    CHECK(hipMalloc(&d_pts30, pts.size() * 4));
     CHECK(hipMalloc(&d_mem, members.size() * 4));
     CHECK(hipMemcpy(d_pts, pts.data(), pts.size() * 4, hipMemcpyHostToDevice));
     CHECK(hipMemcpy(d_mem, members.data(), members.size() * 4, hipMemcpyHostToDevice));
-    launch_g1_table_s29(0, d_pts, d_pts29, NV);
+    launch_g1_table_s30(0, d_pts, d_pts30, NV);
     CHECK(hipDeviceSynchronize());
     const size_t lane_words = (size_t)(G1_LANE_PARTIAL_BYTES / 4) * 131072 * 2;
     CHECK(hipMalloc(&d_lane, lane_words * 4));
@@ -69,7 +69,7 @@ int main(int argc, char** argv)
             std::vector<float> ms;
             for (int rep = 0; rep < 24; ++rep) {
                 CHECK(hipEventRecord(e0));
-                launch_g1_accumulate(0, d_pts29, d_mem, with_bits ? d_bits : nullptr, d_groups, NG, n_slots, d_lane2, d_wg, nullptr, nullptr);
+                launch_g1_accumulate(0, d_pts30, d_mem, with_bits ? d_bits : nullptr, d_groups, NG, n_slots, d_lane2, d_wg, nullptr, nullptr);
                 CHECK(hipEventRecord(e1));
                 CHECK(hipEventSynchronize(e1));
                 float t; CHECK(hipEventElapsedTime(&t, e0, e1));
@@ -78,14 +78,14 @@ int main(int argc, char** argv)
             // and 24 launches in one go: the per-launch time with nothing between them
             CHECK(hipEventRecord(e0));
             for (int rep = 0; rep < 24; ++rep) {
-                launch_g1_accumulate(0, d_pts29, d_mem, with_bits ? d_bits : nullptr, d_groups, NG, n_slots, d_lane2, d_wg, nullptr, nullptr);
+                launch_g1_accumulate(0, d_pts30, d_mem, with_bits ? d_bits : nullptr, d_groups, NG, n_slots, d_lane2, d_wg, nullptr, nullptr);
             }
             CHECK(hipEventRecord(e1));
             CHECK(hipEventSynchronize(e1));
             float tot; CHECK(hipEventElapsedTime(&tot, e0, e1));
             std::sort(ms.begin(), ms.end());
             printf("%-6s k=%2u slots=%6u: first-by-one min %.1f med %.1f max %.1f us | back-to-back %.1f us/launch | %.2f G adds/s\n",
-                   form ? "S29" : "12x32", k, n_slots, ms[0] * 1e3, ms[12] * 1e3, ms[23] * 1e3, tot / 24 * 1e3,
+                   form ? "S30" : "12x32", k, n_slots, ms[0] * 1e3, ms[12] * 1e3, ms[23] * 1e3, tot / 24 * 1e3,
                    (double)(NV - n_slots) / (tot / 24) / 1e6);
         }
         {   // the tree over these partials, alone

@@ -33,7 +33,7 @@ int main(int argc, char** argv)
         d.slot_base = g << l2; d.out_base = g; d.bits_word = NONE32;
     }
     const uint32_t n_slots = n_groups << l2;
-    uint32_t *d_pts, *d_pts29, *d_members, *d_partials, *d_lane;
+    uint32_t *d_pts, *d_pts30, *d_members, *d_partials, *d_lane;
     G1Group* d_groups;
     CHECK(hipMalloc(&d_pts, pts.size() * 4));
     CHECK(hipMalloc(&d_members, members.size() * 4));
@@ -41,8 +41,8 @@ int main(int argc, char** argv)
     CHECK(hipMalloc(&d_partials, 192ull * n_groups));
     CHECK(hipMalloc(&d_lane, 192ull * G1_WG * ((n_slots + G1_WG - 1) / G1_WG)));
     CHECK(hipMemcpy(d_pts, pts.data(), pts.size() * 4, hipMemcpyHostToDevice));
-    CHECK(hipMalloc(&d_pts29, pts.size() * 4));
-    launch_g1_table_s29(0, d_pts, d_pts29, n_pts);  // the accumulation reads the table in its own field form
+    CHECK(hipMalloc(&d_pts30, pts.size() * 4));
+    launch_g1_table_s30(0, d_pts, d_pts30, n_pts);  // the accumulation reads the table in its own field form
     CHECK(hipMemcpy(d_members, members.data(), members.size() * 4, hipMemcpyHostToDevice));
     CHECK(hipMemcpy(d_groups, groups.data(), sizeof(G1Group) * n_groups, hipMemcpyHostToDevice));
     hipEvent_t e0, e1;
@@ -53,7 +53,7 @@ int main(int argc, char** argv)
     float ms = 0, ms_acc = 0;
     for (int rep = 0; rep < 5; ++rep) {  // the two kernels of a sum, back to back (k_g1_finish is not part of this tool)
         CHECK(hipEventRecord(e0, 0));
-        launch_g1_accumulate(0, d_pts29, d_members, nullptr, d_groups, n_groups, n_slots, d_lane, d_partials);
+        launch_g1_accumulate(0, d_pts30, d_members, nullptr, d_groups, n_groups, n_slots, d_lane, d_partials);
         CHECK(hipEventRecord(em, 0));
         launch_g1_tree(0, d_lane, d_groups, n_groups, n_slots, d_partials);
         CHECK(hipEventRecord(e1, 0));
