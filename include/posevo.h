@@ -494,8 +494,20 @@ int pe_get_store_scalars(const pe_engine* h, uint64_t* time, uint64_t* genesis_t
  * PE_ATT_FLAG_SIGNATURE_VALID (the handlers then reject it with PE_ATT_BAD_SIGNATURE): an aggregate over an invalid
  * signature can never verify.  Members with overlapping bits: the row carries PE_ATT_FLAG_OVERLAPPING_BITS as with
  * pe_aggregate, and its signature is the plain sum (which counts a validator twice -- such an aggregate does not verify
- * either, Appendix A.8).  Rows in host or device memory, synchronous or inside a pipeline, exactly as pe_aggregate; the
- * signature sums run on the engine's state-transition stream beside the aggregate pubkeys and the fork-choice kernels. */
+ * either, Appendix A.8).  Rows in host or device memory, synchronous or inside a pipeline, exactly as pe_aggregate.
+ * The signature leg (decode, per-group sums, compression, statuses) runs on a stream of its own that is joined into no
+ * other: whoever completes the pipeline waits for it.  In a streaming pipeline (pe_pipeline_begin_streaming) over
+ * compressed signatures the leg is not launched by the call but COLLECTED: the legs of POSEVO_SIG_BATCH steps (default
+ * 8) share one decompression launch, which goes out with the call that fills the batch -- or when one of the collected
+ * pipelines completes (a drain, a synchronous call, a lag depth shorter than the batch).  That launch and the sums behind
+ * it last 4-5 steps: with a lag depth (pe_pipeline_set_lag) of at least the batch plus those steps the host never waits
+ * for a leg (bench.py's signed steps run at depth 15); a shallower lag gives the same outputs, its lagged end launches
+ * what its arena still holds collected and waits for it.  Uncompressed signatures are never collected.
+ * Several signed aggregates inside ONE pipeline: the leg's device scratch is one set of buffers per pipeline, so every
+ * further signed call first launches the leg the pipeline still holds collected and orders its own signature copy and leg
+ * behind that leg's end.  The legs of one pipeline therefore run one after the other, each with a decompression launch
+ * of its own (~1 ms for up to 64 Ki signatures), and the engine's stream waits for the earlier leg: correct, but without
+ * the batching a streaming caller gets from one signed call per pipeline. */
 #define PE_SIG_G2_COMPRESSED   1u
 #define PE_SIG_G2_UNCOMPRESSED 2u
 #define PE_SIG_CHECK_SUBGROUP  0x100u

@@ -647,11 +647,17 @@ int pe_aggregate_signed(pe_engine* h, const pe_attestation* atts, uint32_t n, co
     HostLap lap(&h->trace);
     {   // the arena's signature scratch, sized while nothing of this call is in flight
         if (!h->pipelining) PE_TRY(flush_pending(h));
-        pe_engine::PipeArena& A = h->A();
-        (void)A;
         PE_TRY(ensure_quiesced_arenas(h, &pe_engine::PipeArena::d_sig_in, sig_bytes * n));
         PE_TRY(ensure_quiesced_arenas(h, &pe_engine::PipeArena::d_sig_pts, 192ull * n));
         PE_TRY(ensure_quiesced_arenas(h, &pe_engine::PipeArena::d_sig_status, 4ull * n));
+        // That scratch is ONE set per arena, not a cursor-allocated region: an earlier signed aggregate of THIS pipeline decodes
+        // from / into the very words this call is about to fill.  Its leg goes out now if it is still collected (a streaming
+        // pipeline), and everything of this call that touches the scratch -- the host signatures' copy below, this call's own
+        // leg through the fork event of sig_batch_flush -- is ordered behind that leg's end.  Legs of one pipeline are thereby
+        // serialised, each with a decompression launch of its own; a pipeline with one signed aggregate never gets here.
+        pe_engine::PipeArena& A = h->A();
+        if (sig_batch_holds(h, h->cur)) PE_TRY(sig_batch_flush(h));
+        if (A.leg_used) HIP_TRY(h, hipStreamWaitEvent(h->stream, A.ev_leg, 0));
     }
     bool sig_on_device = false;
     {

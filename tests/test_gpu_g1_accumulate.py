@@ -1,5 +1,5 @@
-"""-m gpu: the accumulation kernel (k_g1_accumulate over the S29 field form, g1_kernels.hip; the field and point
-arithmetic itself is held against Python integers and oracle/g1.py on the CPU by tests/test_host_fp29.py) through the C
+"""-m gpu: the accumulation kernel (k_g1_accumulate over the S30 field form, g1_kernels.hip; the field and point
+arithmetic itself is held against Python integers and oracle/g1.py on the CPU by tests/test_host_fp30.py) through the C
 ABI: aggregate pubkeys against the closed form of the synthetic registry and against oracle/g1.py -- random keys, the
 structured keys (i + 1) G that hit the doubling branch, P / -P pairs, rows that hold no point (every one of them leaves
 the loop's general body and takes the kernel's redo path), caller-supplied points (pe_g1_sum: the table of the form is
