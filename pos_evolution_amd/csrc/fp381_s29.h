@@ -15,8 +15,8 @@
 // points -- a mixed add of 3 738 multiply-adds runs at the multiplier's issue rate, the simple instructions around them are
 // free and carries are not.  It was the accumulation's form in rounds 4-6 and the tree's in round 6; since round 7 both compute in
 // S30 (fp381_s30.h: 13 balanced limbs of 30 bits, 338 multiply-adds per product).  What remains on S29: the square roots of
-// the decompression kernels (fp_sqrt.h, fq_pow_pm3d4 below) and the tools that measure this form; finish and the wire formats
-// stay in fp381.h.
+// the decompression kernels (fp_sqrt.h, fq_pow_pm3d4 below) and the tools that measure this form (over g1_s29.h, which runs
+// the point formulas the kernels run over S30: g1_lazy.inc); finish and the wire formats stay in fp381.h.
 //
 // Lazy, signed values.  R' / p > 2^25, so a product of operands of magnitude < 2^386 (32 p) comes out in (-eps, p + eps)
 // with no final subtraction; a - b is a plain limb-wise subtraction (limbs of both signs are fine in the next product as
@@ -30,15 +30,7 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define PE_HD __host__ __device__ __forceinline__
-#define PE_HD_MEMBER static __host__ __device__ __forceinline__
-#else
-#define PE_HD static inline
-#define PE_HD_MEMBER static inline
-#endif
-#define PE_HD_CONST static constexpr  // constant-initialised: hipcc emits them for the device where device code reads them
+#include "pe_hd.h"
 
 namespace posevo {
 

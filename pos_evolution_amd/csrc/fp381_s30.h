@@ -21,24 +21,13 @@
 // on the low 30 bits against the multiples of p a value can be (FQ_KP_LO .. FQ_KP_LO + FQ_KP_N - 1: -8 .. 8), and an
 // exact comparison behind it (fq_is_zero_modp).
 //
-// Names live in posevo::s30 so that this form and S29 (which the G2 sums and the square roots keep) can share a translation
-// unit.  Host + device, plain C++, like fp381_s29.h.
+// Names live in posevo::s30 so that this form and S29 (which sits in posevo itself, and which the square roots keep) can
+// share a translation unit.  Host + device, plain C++, like fp381_s29.h; the point formulas over it: g1_s30.h (g1_lazy.inc).
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#endif
-#ifndef PE_HD
-#if defined(__HIPCC__)
-#define PE_HD __host__ __device__ __forceinline__
-#define PE_HD_MEMBER static __host__ __device__ __forceinline__
-#else
-#define PE_HD static inline
-#define PE_HD_MEMBER static inline
-#endif
-#define PE_HD_CONST static constexpr
-#endif
+#include "pe_hd.h"
+
 // The column accumulator of the products.  A host test build may define it as a checked 128-bit type (tests/native/fp30_host.cpp);
 // the code below uses only  T acc = 0;  acc += int64;  acc >>= n;  (int64_t)acc.
 #ifndef PE_FQ30_ACC

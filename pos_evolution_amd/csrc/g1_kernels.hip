@@ -18,7 +18,7 @@
 // Bound: integer VALU (a mixed add = 8 products + 2 squarings = 3 224 v_mad_i64_i32 per 100 bytes gathered), not HBM and
 // not MFMA -- see DESIGN.md "G1 roofline".  Three field forms live here: accumulation and tree compute in S30 (fp381_s30.h,
 // 13 balanced limbs of 30 bits: one multiply-add per limb product, no carry instructions; round 7, 3 224 multiply-adds per
-// mixed add where S29 took 3 738); the square roots of the decompression compute in S29 (fp_sqrt.h, fp381_s29.h); finish,
+// mixed add where S29 took 3 738; the point formulas are g1_lazy.inc, included by g1_s30.h); the square roots of the decompression compute in S29 (fp_sqrt.h, fp381_s29.h); finish,
 // wire formats and key validation in 12 x 32-bit limbs (fp381.h) -- latency-bound guests whose products are CALLS to one copy
 // of the code, so that what they cost the accumulation is not a 64 KB instruction cache full of their unrolled products.
 #define POSEVO_FP_MUL_CALLED 1  // every 12 x 32-bit product of this file's kernels is a call (see fp381.h)

@@ -1,7 +1,8 @@
 """CPU: the S29 field form (pos_evolution_amd/csrc/fp381_s29.h: 14 signed limbs of 29 bits, lazy Montgomery with
 R' = 2^406) and the XYZZ accumulation over it (g1_s29.h), compiled for the HOST from the very source the gfx950 kernels
-use (tests/native/fp29_host.cpp) and held against Python integers and oracle/g1.py.  No GPU; the kernels that use the
-form are checked by the -m gpu tests through the C ABI like every other path."""
+use (tests/native/fp29_host.cpp) and held against Python integers and oracle/g1.py: the kernels run the field form under
+their square roots, and the point formulas (g1_lazy.inc, one text for both lazy forms) over S30.  No GPU; the kernels are
+checked by the -m gpu tests through the C ABI like every other path."""
 import ctypes as C
 import os
 import random
