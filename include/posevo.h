@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define PE_ABI_VERSION 6
+#define PE_ABI_VERSION 7
 
 typedef struct pe_engine pe_engine;
 
@@ -82,7 +82,11 @@ typedef enum pe_att_status {
     PE_ATT_EMPTY_OR_INVALID_INDICES = 11,            /* is_valid_indexed_attestation structural part, pe:736/976 */
     PE_ATT_BAD_SIGNATURE = 12,                       /* injected pairing result false, pe:736/976 */
     PE_ATT_INCLUSION_WINDOW = 13,                    /* pe:726 */
-    PE_ATT_SOURCE_MISMATCH = 14                      /* assert is_matching_source (Appendix A.9) */
+    PE_ATT_SOURCE_MISMATCH = 14,                     /* assert is_matching_source (Appendix A.9) */
+    /* pe_slasher_ingest only (values >= 32): the row takes no part in the detection */
+    PE_SLASH_FUTURE_TARGET = 32,                     /* target.epoch > current_epoch */
+    PE_SLASH_TOO_OLD = 33,                           /* target.epoch + history_epochs <= current_epoch */
+    PE_SLASH_TABLE_FULL = 34                         /* new AttestationData for an epoch that already holds max_data_per_epoch */
 } pe_att_status;
 
 /* Constants the reference cites by name only (pe:467, 1021-1022, 1054, ...);
@@ -645,6 +649,57 @@ int pe_aggregate_sharded(pe_engine* h, const pe_attestation* atts, uint32_t n,
  * at most max_validators_per_committee bits (pe_config). */
 int pe_aggregate_exchange(pe_engine* h, pe_attestation* out_atts, uint32_t* out_n_groups, uint8_t* out_bits_arena,
                           uint64_t out_arena_cap, uint32_t* out_count, uint32_t cap_groups);
+
+/* ---- slashing detection: double and surround votes (pe:1128, pe:1134-1143, pe:1411-1415) -------------------------- */
+/* The engine consumes slashings (pe_on_attester_slashing, pe_mark_equivocating); the slasher FINDS them in the
+ * attestations the node already hands over.  Per validator and per target epoch of a window of history_epochs epochs
+ * (W - H, W] it keeps the FIRST AttestationData the validator attested (in hand-over order), and per epoch the table of the
+ * distinct AttestationData recorded for it (128 bytes each, compared exactly; at most max_data_per_epoch).  A record names
+ * its data as (target_epoch, id).  Device memory: 12 * history_epochs bytes per validator.
+ *
+ * pe_slasher_enable   (pe:1411-1415: every validator "eventually recognises equivocations" in its own view) allocates the
+ *                     history for the registry as loaded (pe_set_validators first; a registry of another size afterwards:
+ *                     enable again).  Enabling again, pe_slasher_disable and pe_store_init drop every record and table.
+ * pe_slasher_ingest   (pe:1128 the two Casper conditions, pe:1134-1143 is_slashable_attestation_data, pe:1447-1461
+ *                     on_attester_slashing).  current_epoch may not decrease (PE_ERR_INVALID_ARG, nothing changes); it
+ *                     becomes W, and epochs that left the window are cleared.  status[i], first match wins:
+ *                       PE_SLASH_FUTURE_TARGET, PE_SLASH_TOO_OLD                     the window;
+ *                       PE_ATT_NO_COMMITTEE_TABLE, _COMMITTEE_INDEX_OUT_OF_RANGE, _BITS_LENGTH_MISMATCH
+ *                                                     the committee, resolved against the table of the row's target epoch as
+ *                                                     pe_on_attestation_batch resolves it; the table must partition the registry;
+ *                       PE_SLASH_TABLE_FULL           new data for an epoch whose table is full.
+ *                     Then, for every validator v and every accepted row a with v's bit set, in array order: if v's record
+ *                     for a's target epoch holds a's data nothing happens; otherwise a is compared with every record b of v
+ *                     in the window and every slashable pair is one pe_slash_evidence:
+ *                       PE_SLASH_DOUBLE    same target epoch, different data: (d1, d2) = (the recorded one, a);
+ *                       PE_SLASH_SURROUND  d1.source < d2.source and d2.target < d1.target: d1 is the surrounding vote --
+ *                                          the argument order on_attester_slashing (pe:1454) accepts;
+ *                     and a is recorded if v's slot for its target epoch is empty (a rejected double vote is not recorded).
+ *                     *out_n_found = pieces of evidence found; the first `cap` that arrive are written to out_evidence in no
+ *                     particular order, THE REST IS DROPPED -- the history is updated all the same, so a caller that
+ *                     wants every pair sizes cap generously (out_n_found tells when it did not).
+ *                     flags & PE_SLASH_APPLY: every validator with evidence joins store.equivocating_indices on the device =
+ *                     on_attester_slashing with attesting_indices = [v] on both sides (pe:1459-1461), exact whatever cap is.
+ *                     Rows are host memory; bits host, pinned or device memory, or PE_BITS_RESIDENT with rows of the last
+ *                     pe_aggregate's out_atts.  Synchronous; inside a pipeline it first completes the outstanding work.
+ * pe_slasher_get_data     the AttestationData behind (target_epoch, id): the leading 128 bytes of *out, the rest zero.
+ * pe_slasher_get_records  the records of one target epoch: source epoch and data id per validator, 0xFFFFFFFF = none
+ *                         (parity tests, checkpoint).  An epoch outside the window reads as empty. */
+#define PE_SLASH_APPLY    0x1u
+#define PE_SLASH_DOUBLE   1u
+#define PE_SLASH_SURROUND 2u
+typedef struct pe_slash_evidence {
+    uint32_t validator, kind;           /* PE_SLASH_DOUBLE / PE_SLASH_SURROUND */
+    uint32_t target_epoch_1, id_1;      /* d1 */
+    uint32_t target_epoch_2, id_2;      /* d2 */
+} pe_slash_evidence;
+int pe_slasher_enable(pe_engine* h, uint32_t history_epochs, uint32_t max_data_per_epoch);
+int pe_slasher_disable(pe_engine* h);
+int pe_slasher_ingest(pe_engine* h, const pe_attestation* atts, uint32_t n, const uint8_t* bits_arena, uint64_t arena_len,
+                      uint64_t current_epoch, uint32_t flags, int32_t* status, pe_slash_evidence* out_evidence, uint32_t cap,
+                      uint32_t* out_n_found);
+int pe_slasher_get_data(pe_engine* h, uint64_t target_epoch, uint32_t id, pe_attestation* out);
+int pe_slasher_get_records(pe_engine* h, uint64_t target_epoch, uint32_t* out_source_epoch, uint32_t* out_id, uint64_t n);
 
 /* Measurement hooks (per-kernel event brackets, the in-situ timeline) are not part of the boundary: include/posevo_profile.h. */
 

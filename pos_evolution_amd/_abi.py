@@ -41,7 +41,12 @@ ATT_STATUS_NAMES = {
     6: "target not ancestor of beacon block", 7: "attestation slot not in the past", 8: "no committee table",
     9: "committee index out of range", 10: "bits length mismatch", 11: "empty or invalid indices",
     12: "bad signature", 13: "outside inclusion window", 14: "source mismatch",
+    32: "slasher: target epoch in the future", 33: "slasher: target epoch left the window",
+    34: "slasher: data table of the epoch is full",
 }
+PE_SLASH_FUTURE_TARGET, PE_SLASH_TOO_OLD, PE_SLASH_TABLE_FULL = 32, 33, 34
+PE_SLASH_APPLY = 1
+PE_SLASH_DOUBLE, PE_SLASH_SURROUND = 1, 2
 
 
 class pe_config(C.Structure):
@@ -179,6 +184,12 @@ SIGNATURES = {
     "pe_get_head_sharded_async": (C.c_int, [_H, _u8p]),
     "pe_aggregate_sharded": (C.c_int, [_H, _attp, C.c_uint32, _u8p, C.c_uint64, _attp, _u32p, _u32p, _u8p,
                                        C.c_uint64, _u8p, _u32p]),
+    "pe_slasher_enable": (C.c_int, [_H, C.c_uint32, C.c_uint32]),
+    "pe_slasher_disable": (C.c_int, [_H]),
+    "pe_slasher_ingest": (C.c_int, [_H, _attp, C.c_uint32, _u8p, C.c_uint64, C.c_uint64, C.c_uint32, _i32p, C.c_void_p,
+                                    C.c_uint32, _u32p]),
+    "pe_slasher_get_data": (C.c_int, [_H, C.c_uint64, C.c_uint32, _attp]),
+    "pe_slasher_get_records": (C.c_int, [_H, C.c_uint64, _u32p, _u32p, C.c_uint64]),
     "pe_pipeline_begin": (C.c_int, [_H]),
     "pe_pipeline_end": (C.c_int, [_H]),
     "pe_pipeline_end_lagged": (C.c_int, [_H]),

@@ -41,16 +41,16 @@ int32_t validate_for_fork_choice(pe_engine* h, const pe_attestation& a, Resolved
     return PE_ATT_OK;
 }
 
-}  // namespace posevo
-
 // The handlers and pe_get_indexed_attestations re-pack the caller's bits on the host: device memory would fault there.
-static bool bits_on_device(const uint8_t* bits_arena)
+bool bits_on_device(const uint8_t* bits_arena)
 {
     hipPointerAttribute_t pa;
     if (hipPointerGetAttributes(&pa, bits_arena) == hipSuccess) return pa.type == hipMemoryTypeDevice;
     (void)hipGetLastError();
     return false;
 }
+
+}  // namespace posevo
 
 // ---------------------------------------------------------------- on_attestation
 // Rows handed over resident (bits_arena == PE_BITS_RESIDENT): which group of the last pe_aggregate is this row?
@@ -62,7 +62,8 @@ static inline uint32_t att_data_tag(const pe_attestation& a)
     return (uint32_t)a.slot * 0x9E3779B1u ^ (uint32_t)a.index * 0x85EBCA6Bu ^ (uint32_t)a.target_epoch * 0xC2B2AE35u ^ r0 ^
            (r1 << 1);
 }
-static bool find_resident(const pe_engine* h, const pe_attestation& a, uint32_t* g_out, uint32_t guess)
+namespace posevo {
+bool find_resident(const pe_engine* h, const pe_attestation& a, uint32_t* g_out, uint32_t guess)
 {
     if (!h->res_valid) return false;
     const auto& rg = h->res_groups;
@@ -80,6 +81,7 @@ static bool find_resident(const pe_engine* h, const pe_attestation& a, uint32_t*
         if (rg[lo].n_bits == a.n_bits && rg[lo].tag == tag) { *g_out = (uint32_t)lo; return true; }
     return false;
 }
+}  // namespace posevo
 
 
 extern "C" {

@@ -513,6 +513,7 @@ void pe_engine_destroy(pe_engine* h)
     if (h->prof_base) (void)hipEventDestroy(h->prof_base);
     h->d_shuffle_scratch.release();
     h->d_points30.release();
+    slasher_release(h);
     if (h->comm && rccl().ok) (void)rccl().CommDestroy(h->comm);
     if (h->comm_g1 && rccl().ok) (void)rccl().CommDestroy(h->comm_g1);
     h->d_xchg.release();

@@ -8,6 +8,7 @@
 //   engine_resident.cpp the same path over rows resident in device memory (grouping + validation on the device)
 //   engine_g1.cpp      G1 / G2 sums over caller-chosen groups, BLSPubkey / BLSSignature wire formats
 //   engine_dist.cpp    multi-GPU exchange: RCCL owned by the engine, function-table collectives
+//   engine_slash.cpp   slashing detection: the per-validator vote history and its scan (double and surround votes)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -412,6 +413,21 @@ struct pe_engine {
     hipEvent_t ev_xchg = nullptr;       // single-communicator mode: G1 chain <-> engine stream hand-over
     bool dist_ready() const { return comm != nullptr || coll_custom; }
 
+    // ---- slashing detection (engine_slash.cpp) ----
+    struct Slasher {
+        bool enabled = false;
+        uint32_t history = 0, max_data = 0;  // H epochs | D distinct AttestationData per epoch
+        uint64_t n_val = 0;                  // registry size the history was allocated for
+        bool have_window = false;
+        uint64_t window = 0;                 // W: the history spans the target epochs (W - H, W]
+        DevBuf d_rec, d_ids, d_counter, d_evidence;  // u64[H][n_val] | u32[H][n_val] | u32 | the call's evidence
+        struct EpochData {                   // slot e mod H: the distinct AttestationData recorded for epoch e
+            std::vector<std::array<uint8_t, 128>> data;
+            std::unordered_map<std::string, uint32_t> id_of;
+        };
+        std::vector<EpochData> epochs;
+    } slasher;
+
     // ---- profiling ----
     bool profiling = false;
     uint64_t acc_launches = 0;  // k_g1_accumulate launches: totals mode brackets every 4th one (launch_g1_planned)
@@ -773,6 +789,12 @@ struct BatchMemo {
 };
 
 int32_t validate_for_fork_choice(pe_engine* h, const pe_attestation& a, Resolved* out, BatchMemo* memo);
+// rows handed over with PE_BITS_RESIDENT: which group of the last pe_aggregate is this row (engine_attest.cpp)
+bool find_resident(const pe_engine* h, const pe_attestation& a, uint32_t* g_out, uint32_t guess);
+bool bits_on_device(const uint8_t* bits_arena);
+// slashing detection (engine_slash.cpp): drop every record and table, keep the allocation | free it
+int slasher_reset(pe_engine* h);
+void slasher_release(pe_engine* h);
 // AttestationData (pe:689-697) is the first 128 bytes of the row, without padding
 static_assert(offsetof(pe_attestation, bits_offset) == 128, "pe_attestation: AttestationData must be the leading 128 bytes");
 inline bool att_data_equal(const pe_attestation& a, const pe_attestation& b) { return memcmp(&a, &b, 128) == 0; }

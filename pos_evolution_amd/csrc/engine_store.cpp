@@ -319,6 +319,7 @@ int pe_store_init(pe_engine* h, uint64_t genesis_time, uint64_t anchor_slot, con
     h->state_view_set = false;
     h->res_valid = false;
     h->rr.valid = false;
+    PE_TRY(slasher_reset(h));  // what the validators of the previous store attested says nothing about this one
     if (h->n_val) {
         const size_t n4 = (h->n_val + 3) & ~size_t(3);
         HIP_TRY(h, hipMemsetAsync(h->d_part_cur.p, 0, n4, h->stream));

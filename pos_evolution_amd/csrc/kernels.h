@@ -332,6 +332,36 @@ bool launch_pair_members_votes(hipStream_t s, const MembersArgs& rows_next, cons
 bool launch_pair_union_tree(hipStream_t s, const UnionArgs& rows_next, const TreeArgs& fc_prev);
 void pair_kernels_preload();  // resolve the pair kernels' code object now rather than inside the first streaming step
 
+// ---- slashing detection (slash_kernels.hip; host side: engine_slash.cpp) -----------------------------------------
+// is_slashable_attestation_data (pe:1134-1143) of every new vote of a validator against its history of H target epochs.
+// History, epoch-major: rec[(e mod H) * n_val + v] = (target_epoch + 1) << 32 | source_epoch, 0 = empty; ids[...] the data id
+// of the record, read only on a hit.  Epoch-major: the lanes of a wave (consecutive validators) read consecutive words of
+// every slot whatever their committees, and an epoch that leaves the window is one contiguous memset.
+struct SlashRow {                 // one accepted row of the batch; the array is in batch order
+    uint32_t bits_byte;           // byte offset of its bits (LSB-first) in the bit arena
+    uint32_t n_bits;              // committee length: bit i belongs to the validator at position i
+    uint32_t source, target;      // source.epoch, target.epoch
+    uint32_t id;                  // id of its AttestationData in the table of its target epoch
+    uint32_t pad[3];
+};
+struct SlashTable {               // one committee table the batch's rows resolve against (a partition of the registry)
+    const uint32_t* inv_comm;     // validator -> committee id (NONE32: in none)
+    const uint32_t* inv_pos;      // validator -> position in that committee
+    const uint32_t* crow_start;   // n_committees + 1: the committee's rows are crow_list[crow_start[c] .. crow_start[c + 1])
+};
+struct SlashArgs {
+    const SlashRow* rows;
+    const SlashTable* tables; uint32_t n_tables;
+    const uint32_t* crow_list;    // indices into rows[], ascending inside a committee (= batch order)
+    const uint8_t* bits;
+    unsigned long long* rec; uint32_t* ids; uint32_t history; uint64_t n_val;
+    uint32_t* counter;            // evidence found (device-scope counter, zeroed by the launcher's caller)
+    uint32_t* evidence; uint32_t cap;  // cap x 6 words {validator, kind, target_1, id_1, target_2, id_2}
+    uint8_t* flags;               // nullable: validators with evidence get VAL_EQUIVOCATING (PE_SLASH_APPLY)
+};
+constexpr int SLASH_NV = 4;       // new votes of one validator held in registers per pass over its history
+void launch_slash_scan(hipStream_t s, const SlashArgs& a);
+
 // The working-state view mirrors the registry (pe_store_init): sflags = active/slashed (+ active-in-previous-epoch),
 // increments = balance / effective_balance_increment.
 void launch_state_view_from_registry(hipStream_t s, const uint8_t* flags, const uint64_t* balance, uint64_t increment,

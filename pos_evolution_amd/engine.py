@@ -128,6 +128,9 @@ _ATT_DTYPE = np.dtype([
 ])  # == synth.ATT_DTYPE == struct pe_attestation (144 bytes)
 
 
+SLASH_EVIDENCE_DTYPE = np.dtype([("validator", "<u4"), ("kind", "<u4"), ("target_epoch_1", "<u4"), ("id_1", "<u4"),
+                                 ("target_epoch_2", "<u4"), ("id_2", "<u4")])  # == struct pe_slash_evidence
+
 _I32, _U32, _U64, _U8 = np.dtype(np.int32), np.dtype(np.uint32), np.dtype(np.uint64), np.dtype(np.uint8)
 
 
@@ -499,6 +502,55 @@ class Engine:
         if rc:
             self._check(rc)
         return status[:n], (agg[:n] if agg is not None else None), count[:n]
+
+    # -- slashing detection (pe:1128, pe:1134-1143) -------------------------
+    def validator_flags(self) -> np.ndarray:
+        """pe_get_validator_flags: the flag byte of every validator, PE_VAL_EQUIVOCATING included."""
+        n = self.num_validators
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        self._check(self._lib.pe_get_validator_flags(self._h, _ptr(out), n))
+        return out[:n]
+
+    def slasher_enable(self, history_epochs: int, max_data_per_epoch: int = 4096):
+        """pe_slasher_enable: a history of the first vote per validator and target epoch over ``history_epochs`` epochs
+        (12 bytes per validator and epoch in device memory), at most ``max_data_per_epoch`` distinct AttestationData per
+        epoch.  After set_validators; drops an earlier history."""
+        self._check(self._lib.pe_slasher_enable(self._h, int(history_epochs), int(max_data_per_epoch)))
+
+    def slasher_disable(self):
+        self._check(self._lib.pe_slasher_disable(self._h))
+
+    def slasher_ingest(self, rows=None, packed=None, current_epoch: int = 0, apply: bool = False, cap: int = 4096):
+        """pe_slasher_ingest -> (status int32[n], evidence): ``evidence`` = the first min(cap, found) pieces as a structured
+        array (SLASH_EVIDENCE_DTYPE: validator, kind, target_epoch_1, id_1, target_epoch_2, id_2; ids resolve through
+        slasher_data); ``self.slasher_found`` = the number found, which may exceed cap.  ``apply``: every validator with
+        evidence joins store.equivocating_indices on the device (PE_SLASH_APPLY).  ``packed=(rows, RESIDENT)``: rows of
+        the last aggregate's result, their OR-ed bits used where they lie."""
+        arr, arena = packed if packed is not None else pack_attestations(rows)
+        n = len(rows) if rows is not None else len(arr)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        evidence = np.zeros(max(int(cap), 1), dtype=SLASH_EVIDENCE_DTYPE)
+        found = C.c_uint32(0)
+        arena_p = _abi.PE_BITS_RESIDENT if arena is RESIDENT else _ptr(arena, C.c_uint8)
+        self._check(self._lib.pe_slasher_ingest(self._h, _att_ptr(arr), n, arena_p, arena.size, int(current_epoch),
+                                                _abi.PE_SLASH_APPLY if apply else 0, _ptr(status), _ptr(evidence), int(cap),
+                                                C.addressof(found)))
+        self.slasher_found = int(found.value)
+        return status[:n], evidence[:min(int(cap), self.slasher_found)]
+
+    def slasher_data(self, target_epoch: int, data_id: int) -> np.ndarray:
+        """pe_slasher_get_data -> one ATT_DTYPE row whose leading 128 bytes are the AttestationData behind the id."""
+        out = np.zeros(1, dtype=_ATT_DTYPE)
+        self._check(self._lib.pe_slasher_get_data(self._h, int(target_epoch), int(data_id), _ptr(out)))
+        return out[0]
+
+    def slasher_records(self, target_epoch: int):
+        """pe_slasher_get_records -> (source_epoch uint32[n_val], data id uint32[n_val]); 0xFFFFFFFF = no record."""
+        n = self.num_validators
+        src = np.empty(max(n, 1), dtype=np.uint32)
+        ids = np.empty(max(n, 1), dtype=np.uint32)
+        self._check(self._lib.pe_slasher_get_records(self._h, int(target_epoch), _ptr(src), _ptr(ids), n))
+        return src[:n], ids[:n]
 
     def get_indexed_attestations(self, rows=None, packed=None):
         """get_indexed_attestation x n (A.6): -> (status int32[n], offsets uint32[n+1], sorted attesting indices)."""

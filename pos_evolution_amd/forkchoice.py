@@ -9,6 +9,7 @@ pos-evolution.md (``pe:N``):
     on_block(store, signed_block, post_state)               pe:986-1036   (state_transition is the caller's)
     on_attestation(store, attestation, is_from_block=False) pe:963-979, pe:1423-1428
     on_attester_slashing(store, attester_slashing)          pe:1447-1461
+    find_attester_slashings(store, attestations)            pe:1128, pe:1134-1143 (the detection the handlers presume)
     get_head(store) -> Root                                 pe:1102-1116
     process_attestation(state, attestation)                 pe:722-754    (state bound with bind_state)
 
@@ -248,6 +249,70 @@ def on_attester_slashing(store: Store, attester_slashing) -> None:
 
     store.engine.on_attester_slashing(row(a1), list(a1.attesting_indices), row(a2), list(a2.attesting_indices))
     store.equivocating_indices |= set(a1.attesting_indices).intersection(a2.attesting_indices)
+
+
+@dataclass(eq=True, frozen=True)
+class AttestationData:
+    """pe:689-697"""
+    slot: int
+    index: int
+    beacon_block_root: bytes
+    source: Checkpoint
+    target: Checkpoint
+
+
+@dataclass
+class IndexedAttestation:
+    """Appendix A.6; ``signature_valid`` is the injected verdict of the pairing check, as on every attestation here."""
+    attesting_indices: List[int]
+    data: AttestationData
+    signature: object = None
+    signature_valid: bool = True
+
+
+@dataclass
+class AttesterSlashing:
+    """pe:1159-1162"""
+    attestation_1: IndexedAttestation
+    attestation_2: IndexedAttestation
+
+
+def find_attester_slashings(store: Store, attestations: Iterable, *, apply: bool = False,
+                            cap: Optional[int] = None) -> List[AttesterSlashing]:
+    """The double and surround votes (pe:1128) that ``attestations`` hold against what their validators attested before,
+    found on the GPU (Engine.slasher_enable first): one AttesterSlashing per slashable pair of AttestationData
+    (is_slashable_attestation_data(d1, d2), pe:1134-1143, in the argument order on_attester_slashing accepts), the sorted
+    validators that signed both as ``attesting_indices`` of both sides.  The history is that of the engine's window as of
+    get_current_slot(store); the attestations join it.  ``cap`` bounds the pieces of evidence read back (default: four
+    per set bit); more than that raises -- the history has moved on by then, so size it generously."""
+    eng = store.engine
+    rows = [_att_row(a) for a in attestations]
+    sc = eng.store_scalars()
+    spe, sps = int(eng.cfg.slots_per_epoch), int(eng.cfg.seconds_per_slot)
+    current_epoch = (sc["time"] - sc["genesis_time"]) // sps // spe
+    if cap is None:
+        cap = 4 * sum(int(np.count_nonzero(r.bits)) for r in rows) + 1024
+    _, evidence = eng.slasher_ingest(rows, current_epoch=current_epoch, apply=apply, cap=cap)
+    if eng.slasher_found > len(evidence):
+        raise EngineError(_abi.PE_ERR_CAPACITY, f"find_attester_slashings: {eng.slasher_found} pieces of evidence, cap {cap}")
+    pairs: Dict[tuple, List[int]] = {}
+    for ev in evidence:
+        key = (int(ev["target_epoch_1"]), int(ev["id_1"]), int(ev["target_epoch_2"]), int(ev["id_2"]))
+        pairs.setdefault(key, []).append(int(ev["validator"]))
+
+    def data(epoch, data_id):
+        r = eng.slasher_data(epoch, data_id)
+        return AttestationData(int(r["slot"]), int(r["index"]), r["beacon_block_root"].tobytes(),
+                               Checkpoint(int(r["source_epoch"]), r["source_root"].tobytes()),
+                               Checkpoint(int(r["target_epoch"]), r["target_root"].tobytes()))
+
+    out = []
+    for (e1, i1, e2, i2), validators in sorted(pairs.items()):
+        idx = sorted(set(validators))
+        out.append(AttesterSlashing(IndexedAttestation(list(idx), data(e1, i1)), IndexedAttestation(list(idx), data(e2, i2))))
+    if apply:
+        store.equivocating_indices |= {v for s_ in out for v in s_.attestation_1.attesting_indices}
+    return out
 
 
 def get_indexed_attestation(store: Store, attestation):
