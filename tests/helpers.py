@@ -37,3 +37,43 @@ def att_device_rows(atts, comm, slots_per_epoch):
     pos = (atts["slot"] % slots_per_epoch) * cps + atts["index"]
     member_off = comm.offsets[pos.astype(np.int64)]
     return member_off.astype(np.uint32), atts["n_bits"].astype(np.uint32), atts["bits_offset"].astype(np.uint32)
+
+
+def install_votes(e, tree, comm, vote, now_slot=None):
+    """Drive `vote` into the engine through on_attestation batches; returns the vote table actually installed
+    (validators whose Zipf block fails validate_on_attestation keep no message).  Committee c attests in slot
+    E * 32 + c // (committees per slot) of the epoch E behind the tree's last slot; the clock is set to now_slot
+    (default: the first slot of epoch E + 2)."""
+    n_comm = comm.offsets.size - 1
+    spe = 32
+    cps = n_comm // spe
+    # every attestation: slot = 31 of the block's epoch or later so block.slot <= slot; use a single far epoch
+    E = int(tree.slot.max()) // spe + 1
+    e.set_committees(E, comm.offsets, comm.members)
+    e.on_tick(((E + 2) * spe if now_slot is None else now_slot) * 12)
+    # equivocators' votes are dropped by update_latest_messages (pe:1438): the caller accounts for that
+    atts_list, bits_list = [], []
+    installed = np.full(vote.shape[0], NONE32, dtype=np.uint32)
+    for c in range(n_comm):
+        mem = comm.members[comm.offsets[c]:comm.offsets[c + 1]]
+        v = vote[mem]
+        for blk in np.unique(v[v != NONE32]):
+            blk = int(blk)
+            a = np.zeros(1, dtype=synth.ATT_DTYPE)[0]
+            a["slot"], a["index"] = E * spe + c // cps, c % cps
+            a["beacon_block_root"] = tree.roots[blk]
+            a["target_epoch"] = E
+            a["target_root"] = tree.roots[synth.ancestor_at(tree, blk, E * spe)]
+            a["source_root"] = tree.roots[0]
+            a["flags"] = 3   # signature valid | is_from_block (no wall-clock epoch check, pe:1423)
+            atts_list.append(a)
+            bits_list.append(v == blk)
+            installed[mem[v == blk]] = blk
+    if not atts_list:   # nobody votes: nothing to hand in
+        return installed
+    atts = np.array(atts_list, dtype=synth.ATT_DTYPE)
+    arena, offs, nb = synth.pack_bit_rows(bits_list)
+    atts["bits_offset"], atts["n_bits"] = offs, nb
+    status, _, _ = e.on_attestation_batch(packed=(atts, arena))
+    assert (status == 0).all(), np.unique(status)
+    return installed

@@ -5,6 +5,7 @@ import pytest
 import pos_evolution_amd.synth as synth
 from oracle import cport, g1
 from tests import helpers as H
+from tests.helpers import install_votes as _install_votes
 
 pytestmark = pytest.mark.gpu
 NONE32 = 0xFFFFFFFF
@@ -105,43 +106,6 @@ def test_get_head_vs_oracle(engine_factory, n_val, n_blocks, kind, boost, mixed)
             assert e.get_head() == tree.roots[head_o].tobytes()
         e.drain()
         assert np.array_equal(e.last_weights(), w_o)
-
-
-def _install_votes(e, tree, comm, vote):
-    """Drive `vote` into the engine through on_attestation batches; returns the vote table actually installed
-    (validators whose Zipf block fails validate_on_attestation keep no message)."""
-    n_comm = comm.offsets.size - 1
-    spe = 32
-    cps = n_comm // spe
-    n_blocks = tree.roots.shape[0]
-    # every attestation: slot = 31 of the block's epoch or later so block.slot <= slot; use a single far epoch
-    E = int(tree.slot.max()) // spe + 1
-    e.set_committees(E, comm.offsets, comm.members)
-    e.on_tick((E + 2) * spe * 12)
-    # equivocators' votes are dropped by update_latest_messages (pe:1438): the caller accounts for that
-    atts_list, bits_list = [], []
-    installed = np.full(vote.shape[0], NONE32, dtype=np.uint32)
-    for c in range(n_comm):
-        mem = comm.members[comm.offsets[c]:comm.offsets[c + 1]]
-        v = vote[mem]
-        for blk in np.unique(v[v != NONE32]):
-            blk = int(blk)
-            a = np.zeros(1, dtype=synth.ATT_DTYPE)[0]
-            a["slot"], a["index"] = E * spe + c // cps, c % cps
-            a["beacon_block_root"] = tree.roots[blk]
-            a["target_epoch"] = E
-            a["target_root"] = tree.roots[synth.ancestor_at(tree, blk, E * spe)]
-            a["source_root"] = tree.roots[0]
-            a["flags"] = 3   # signature valid | is_from_block (no wall-clock epoch check, pe:1423)
-            atts_list.append(a)
-            bits_list.append(v == blk)
-            installed[mem[v == blk]] = blk
-    atts = np.array(atts_list, dtype=synth.ATT_DTYPE)
-    arena, offs, nb = synth.pack_bit_rows(bits_list)
-    atts["bits_offset"], atts["n_bits"] = offs, nb
-    status, _, _ = e.on_attestation_batch(packed=(atts, arena))
-    assert (status == 0).all(), np.unique(status)
-    return installed
 
 
 @pytest.mark.parametrize("eta", [1, 20, 48, 10**6])
