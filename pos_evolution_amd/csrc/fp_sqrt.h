@@ -49,8 +49,8 @@ __device__ __forceinline__ void fp_half(fp& r, const fp& a)
 // w = a^((p-3)/4).  With it: a * w = a^((p+1)/4) is the square root of a when a is a quadratic residue (the caller checks
 // its square), and then w = 1 / sqrt(a) as well ((a w) w = a^((p-1)/2) = 1) -- the G2 decompression needs both.  When a is NOT a
 // residue, (a w)^2 = -a and (a w) w = -1.
-// The chain itself runs in the 29-bit form (fp381_s29.h, fq_pow_pm3d4: why, and the windows); Montgomery words in, canonical
-// Montgomery words out, one product each way.
+// The chain itself runs in the 29-bit form (fp381_s29.h, fq_pow_pm3d4: why, and the windows; the products are
+// fp381_lazy.inc's); Montgomery words in, canonical Montgomery words out, one product each way.
 __device__ POSEVO_POW_INLINE void fp_pow_pm3d4(fp& w, const fp& a)
 {
     fq x, r;

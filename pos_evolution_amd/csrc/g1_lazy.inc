@@ -1,8 +1,9 @@
 // g1_lazy.inc -- the XYZZ point formulas over a lazy signed-limb field form, written once: accumulator += affine point, the
 // complete add of two XYZZ points, and the hand-over of a finished point to the 12 x 32-bit XYZZ words k_g1_finish reads.
 // Included inside the form's namespace by g1_s29.h (over fp381_s29.h) and g1_s30.h (over fp381_s30.h): no include guard, no
-// namespace of its own.  Host + device: tests/test_host_fp29.py and tests/test_host_fp30.py run this text on the CPU
-// against oracle/g1.py, the gfx950 kernels compile it over S30.
+// namespace of its own -- like fp381_lazy.inc, the field arithmetic beneath it, which those two field headers share.
+// Host + device: tests/test_host_fp29.py and tests/test_host_fp30.py run this text on the CPU against oracle/g1.py, the
+// gfx950 kernels compile it over S30.
 //
 // Same formulas as g1.h (madd-2008-s / mmadd-2008-s / dbl-2008-s-1 / add-2008-s), same exact edge cases; what differs from
 // g1.h is the bookkeeping of a lazy form: products come out balanced, X3 (three terms) and Y3 (stored, subtracted from a
@@ -11,7 +12,7 @@
 //   fq_sub_operand(r, a, b)  r = a - b where the difference feeds a product (P = U2 - X1, R = S2 - Y1, Q - X3): limb-wise as
 //                            it is where the products accept it (S29), through a carry pass where they do not (S30);
 //   fq_first_operand(r, a)   a table row's coordinate as the accumulator's in g1q_set_first.
-// Everything else of the field form is used under the names both field headers share (fq, FQ_N, fq_mul, fq_sqr, fq_norm ...).
+// Everything else of the field form is used under the names of fp381_lazy.inc (fq, FQ_N, fq_mul, fq_sqr, fq_norm ...).
 
 // Where a function's products come from.  FqInline: fq_mul / fq_sqr expanded in place (straight-line, ~3 KB of code per
 // product): for the one hot loop body.  A kernel may pass a policy whose mul / sqr CALL a single non-inlined copy instead:

@@ -6,7 +6,7 @@
 // passes, S29: two) around eight products and two squarings -- 3 224 multiply-adds instead of 3 738.  Registry rows are
 // stored as balanced digits and are product operands as they are.
 #pragma once
-#include "fp381_s30.h"
+#include "fp381_s30.h"  // the form's own part; the field text both forms share is fp381_lazy.inc
 
 namespace posevo {
 namespace s30 {

@@ -1,5 +1,6 @@
-// pe_hd.h -- how the host + device headers (fp381_s29.h, fp381_s30.h and the point layers over them) declare a function,
-// a static member and a constant table, so that the same text compiles under hipcc and under a plain host compiler.
+// pe_hd.h -- how the host + device headers (fp381_s29.h, fp381_s30.h, the text they share and the point layers over them)
+// declare a function, a static member and a constant table, so that the same text compiles under hipcc and under a plain
+// host compiler.
 #pragma once
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>

@@ -356,9 +356,9 @@ def test_the_trees_complete_adds_over_the_lanes_accumulators(lib, checked, which
 
 
 def test_generated_constants_are_current():
-    """fp381_s30_consts.inc is what tools/gen_fp30_consts.py prints (everything in it follows from the prime)."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_fp30_consts.py")], capture_output=True, text=True,
-                         check=True).stdout
+    """fp381_s30_consts.inc is what tools/gen_fq_consts.py 30 prints (everything in it follows from the prime)."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_fq_consts.py"), "30"], capture_output=True,
+                         text=True, check=True).stdout
     assert out == open(os.path.join(ROOT, "pos_evolution_amd", "csrc", "fp381_s30_consts.inc")).read()
     n0 = int(out.split("FQ_N0INV = ")[1].split("u;")[0])
     assert (n0 * P + 1) % (1 << B) == 0

@@ -1,16 +1,28 @@
-// fpbench29.hip -- the S29 field form (pos_evolution_amd/csrc/fp381_s29.h, g1_s29.h) on the device: results against
-// the SAME source run on the host (which tests/test_host_fp29.py holds against Python integers), and throughput of the
-// product and of the mixed add beside the 12 x 32 form's (tools/fpbench.hip prints those).
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../pos_evolution_amd/csrc -o fpbench29 fpbench29.hip
+// fpbench_lazy.hip -- a lazy field form (pos_evolution_amd/csrc/fp381_lazy.inc under fp381_s29.h / fp381_s30.h, and the
+// point formulas g1_lazy.inc over it) on the device: results against the SAME source run on the host (which
+// tests/test_host_fp29.py / tests/test_host_fp30.py hold against Python integers), and throughput of the product and of the
+// mixed add.  One source, same kernels, same shapes for both forms, so their lines compare; beside the 12 x 32 form's
+// (tools/fpbench.hip prints those).
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -DFQ_FORM=29 -I../pos_evolution_amd/csrc -o fpbench29 fpbench_lazy.hip
+//        hipcc --offload-arch=gfx950 -O3 -std=c++17 -DFQ_FORM=30 -I../pos_evolution_amd/csrc -o fpbench30 fpbench_lazy.hip
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <random>
 #include <vector>
+#if FQ_FORM == 29
 #include "g1_s29.h"
-
 using namespace posevo;
+#define FORM "29"
+#elif FQ_FORM == 30
+#include "g1_s30.h"
+using namespace posevo::s30;
+#define FORM "30"
+#else
+#error "build with -DFQ_FORM=29 or -DFQ_FORM=30"
+#endif
+
 #define CHECK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); return 1; } } while (0)
 
 __global__ void k_mul_check(const fq* a, const fq* b, fq* out, int n)
@@ -20,8 +32,8 @@ __global__ void k_mul_check(const fq* a, const fq* b, fq* out, int n)
     fq r, s, d, t;
     fq_mul(r, a[i], b[i]);
     fq_sqr(s, a[i]);
-    fq_sub(d, r, s);       // a b - a^2, unreduced difference of two products
-    fq_mul(t, d, b[i]);    // ... straight into the next product
+    fq_sub_operand(d, r, s);  // a b - a^2, a difference of two products the way the form feeds it ...
+    fq_mul(t, d, b[i]);       // ... into the next product (S29: as it is, S30: through one carry pass)
     fq_canonical(out[i], t);
 }
 __global__ void k_run_check(const uint32_t* rows24, int run, uint32_t* out48, int n)
@@ -64,10 +76,17 @@ __global__ void __launch_bounds__(256) k_madd_chain(const fq* pts, fq* out, int 
 int main()
 {
     const int N = 1 << 15;
-    std::mt19937_64 rng(29);
-    auto rnd = [&](fq& o) {  // canonical limbs of a value below 2^380
-        for (int k = 0; k < FQ_N - 1; ++k) o.l[k] = (int32_t)(rng() & FQ_MASK);
+    std::mt19937_64 rng(FQ_FORM);
+    auto rnd = [&](fq& o) {  // a value below 2^380 the way the form's table stores one
+#if FQ_FORM == 29
+        for (int k = 0; k < FQ_N - 1; ++k) o.l[k] = (int32_t)(rng() & FQ_MASK);  // canonical limbs
         o.l[FQ_N - 1] = (int32_t)(rng() & 7);
+#else
+        fq c;
+        for (int k = 0; k < FQ_N - 1; ++k) c.l[k] = (int32_t)(rng() & FQ_MASK);
+        c.l[FQ_N - 1] = (int32_t)(rng() & 0xfffff);
+        fq_balance(o, c);  // balanced digits
+#endif
     };
     std::vector<fq> ha(N), hb(N), hr(N), he(N);
     for (int i = 0; i < N; ++i) { rnd(ha[i]); rnd(hb[i]); }
@@ -80,10 +99,10 @@ int main()
     int bad = 0;
     for (int i = 0; i < N; ++i) {
         fq r, s, d, t;
-        fq_mul(r, ha[i], hb[i]); fq_sqr(s, ha[i]); fq_sub(d, r, s); fq_mul(t, d, hb[i]); fq_canonical(he[i], t);
+        fq_mul(r, ha[i], hb[i]); fq_sqr(s, ha[i]); fq_sub_operand(d, r, s); fq_mul(t, d, hb[i]); fq_canonical(he[i], t);
         if (memcmp(&he[i], &hr[i], sizeof(fq))) ++bad;
     }
-    printf("S29 mul / sqr / sub / canonical, device vs host: %d / %d mismatches\n", bad, N);
+    printf("S" FORM " mul / sqr / sub / canonical, device vs host: %d / %d mismatches\n", bad, N);
 
     // accumulation runs: rows = Montgomery (R = 2^384) words of arbitrary field elements are NOT curve points; the group
     // law's formulas do not care, and host and device must agree word for word (the CPU test uses real points)
@@ -113,7 +132,7 @@ int main()
     }
     bad = 0;
     for (int i = 0; i < RUNS; ++i) if (memcmp(&o_host[48 * (size_t)i], &o_dev[48 * (size_t)i], 192)) ++bad;
-    printf("S29 accumulation runs of %d, device vs host: %d / %d mismatches\n", RUN, bad, RUNS);
+    printf("S" FORM " accumulation runs of %d, device vs host: %d / %d mismatches\n", RUN, bad, RUNS);
 
     fq* dx; CHECK(hipMalloc(&dx, ((size_t)256 * 4 * 256 * 2 + 8) * sizeof(fq)));
     for (size_t off = 0; off < (size_t)256 * 4 * 256 * 2; off += N) CHECK(hipMemcpy(dx + off, da, (size_t)N * sizeof(fq), hipMemcpyDeviceToDevice));
@@ -131,7 +150,7 @@ int main()
             }
             float ms; CHECK(hipEventElapsedTime(&ms, e0, e1));
             const double ops = (double)blocks * 256 * iters;
-            printf("%-10s waves/SIMD=%d: %.3f ms, %.2f G %s/s on the chip\n", which ? "s29 madd" : "s29 mul", wps, ms,
+            printf("%-10s waves/SIMD=%d: %.3f ms, %.2f G %s/s on the chip\n", which ? "s" FORM " madd" : "s" FORM " mul", wps, ms,
                    ops / ms / 1e6, which ? "mixed adds" : "products");
         }
     printf("compare: tools/fpbench (12 x 32 form) -- 57 G products/s, 4.6 G mixed adds/s at two waves per SIMD\n");
