@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define PE_ABI_VERSION 7
+#define PE_ABI_VERSION 8
 
 typedef struct pe_engine pe_engine;
 
@@ -400,6 +400,39 @@ int pe_get_committees(pe_engine* h, uint64_t epoch, uint32_t* out_n_committees, 
  * out[2] = current_target_balance (each max(EFFECTIVE_BALANCE_INCREMENT, sum), Appendix A.1).  The caller feeds
  * them to weigh_justification_and_finalization (pe:815-853), which is scalar logic on the state. */
 int pe_ffg_balances(pe_engine* h, uint64_t out[3]);
+
+/* ---- the epoch boundary over the resident registry ----------------------- */
+/* compute_proposer_index (pe:604-618), once per seed: for i = 0, 1, ... the candidate
+ * indices[compute_shuffled_index(i % total, total, seed)] is accepted iff
+ * effective_balance * 255 >= max_effective_balance * hash(seed + uint64_le(i / 32))[i % 32].
+ * effective balances = the working-state view (pe_state_set_validators; the pe_set_validators data until then).
+ * seeds: n_seeds x 32 bytes (the caller's state accessor, e.g. one per slot of an epoch).
+ * active_indices / n_active / shuffle_round_count: exactly as pe_compute_committees (NULL = validators 0..n_active-1;
+ * same validation, same bound on the round count); an empty active set is PE_ERR_INVALID_ARG (pe:608).
+ * max_tries: candidates examined per seed before giving up (0 = 4096).
+ * out_proposers u32[n_seeds]: the validator index, or 0xFFFFFFFF where no candidate within max_tries was accepted
+ *   (the reference loops forever there).
+ * out_tries u32[n_seeds] (may be NULL): the i at which the candidate was accepted; max_tries when none was.
+ * Synchronous; one GPU: PE_ERR_STATE on a handle with pe_dist_init* active. */
+int pe_compute_proposers(pe_engine* h, const uint8_t* seeds32, uint32_t n_seeds,
+                         const uint32_t* active_indices, uint32_t n_active, uint32_t shuffle_round_count,
+                         uint64_t max_effective_balance, uint32_t max_tries,
+                         uint32_t* out_proposers, uint32_t* out_tries);
+
+/* process_effective_balance_updates (pe:122-133) on the working-state view, in place:
+ * balances u64[n] = state.balances (host memory); increment = cfg.effective_balance_increment;
+ * thresholds = increment / hysteresis_quotient * {downward, upward}_multiplier.
+ * If the view still mirrors pe_set_validators, it is first materialised from it, flags included.
+ * The justified-checkpoint data that get_head weighs is NOT changed.
+ * Updates d_sbalance and the u16 increments the flag passes read.
+ * *out_n_changed = validators whose effective balance changed.
+ * out_effective_balance (may be NULL): the new values.
+ * n != registry size, or max_effective_balance / increment > 65535: PE_ERR_INVALID_ARG, nothing changed.
+ * Synchronous; one GPU: PE_ERR_STATE on a handle with pe_dist_init* active. */
+int pe_effective_balance_updates(pe_engine* h, uint64_t n, const uint64_t* balances,
+                                 uint64_t max_effective_balance, uint64_t hysteresis_quotient,
+                                 uint64_t downward_multiplier, uint64_t upward_multiplier,
+                                 uint64_t* out_n_changed, uint64_t* out_effective_balance);
 
 /* Plain G1 sum over caller-chosen groups: out[g] = sum_{j in [offsets[g], offsets[g+1])}
  * points[index[j]] (index NULL = identity).  points96 NULL = the validators' pubkeys. */

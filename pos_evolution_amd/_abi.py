@@ -144,6 +144,10 @@ SIGNATURES = {
     "pe_get_committee_epochs": (C.c_int, [_H, _u64p, C.c_uint32, _u32p]),
     "pe_get_committees": (C.c_int, [_H, C.c_uint64, _u32p, _u32p, C.c_uint32, _u32p, C.c_uint64]),
     "pe_ffg_balances": (C.c_int, [_H, _u64p]),
+    "pe_compute_proposers": (C.c_int, [_H, _u8p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _u32p,
+                                       _u32p]),
+    "pe_effective_balance_updates": (C.c_int, [_H, C.c_uint64, _u64p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _u64p,
+                                               _u64p]),
     "pe_g1_sum": (C.c_int, [_H, _u8p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u8p]),
     "pe_get_block": (C.c_int, [_H, C.c_uint32, _u8p, _u32p, _u64p, _u64p, _u8p, _u64p, _u8p]),
     "pe_get_validator_flags": (C.c_int, [_H, _u8p, C.c_uint64]),

@@ -9,6 +9,7 @@
 //   engine_g1.cpp      G1 / G2 sums over caller-chosen groups, BLSPubkey / BLSSignature wire formats
 //   engine_dist.cpp    multi-GPU exchange: RCCL owned by the engine, function-table collectives
 //   engine_slash.cpp   slashing detection: the per-validator vote history and its scan (double and surround votes)
+//   engine_epoch.cpp   the epoch boundary: proposer sampling and the effective-balance hysteresis over the resident registry
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -566,6 +567,8 @@ int run_tree(pe_engine* h, uint64_t* d_direct, const VoteTotals* d_totals, int c
              uint32_t* async_word = nullptr);
 int ensure_validator_arrays(pe_engine* h, uint64_t n);
 int upload_balances(pe_engine* h, uint64_t n, const uint64_t* bal, const uint8_t* flags);
+// the active set of a shuffle: NULL = validators 0 .. n_active - 1, else distinct indices into the registry
+int validate_active_set(pe_engine* h, const uint32_t* active_indices, uint32_t n_active);
 
 // Re-pack one attestation's bits into 32-bit words (zero padded, masked to n_use bits); returns popcount.
 uint32_t pack_bits(const uint8_t* src, uint32_t n_use, uint32_t* dst_words);

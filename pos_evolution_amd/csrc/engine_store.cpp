@@ -170,6 +170,31 @@ CommitteeTable* find_table(pe_engine* h, uint64_t epoch)
     return hit;
 }
 
+// The active set of a shuffle (pe_compute_committees, pe_compute_proposers).  active_indices NULL = every validator
+// 0 .. n_active - 1 is active (get_active_validator_indices of a registry without pending or exited validators): nothing
+// to validate beyond the count; otherwise distinct validator indices (get_active_validator_indices is increasing).
+int validate_active_set(pe_engine* h, const uint32_t* active_indices, uint32_t n_active)
+{
+    if (active_indices == nullptr) {
+        if (n_active > h->n_val) return fail(h, PE_ERR_INVALID_ARG, "n_active exceeds the registry");
+        return PE_OK;
+    }
+    bool increasing = true;
+    for (uint32_t i = 0; i < n_active && increasing; ++i) {
+        if (active_indices[i] >= h->n_val) return fail(h, PE_ERR_INVALID_ARG, "active index out of range");
+        if (i && active_indices[i] <= active_indices[i - 1]) increasing = false;
+    }
+    if (!increasing) {  // not sorted: the general distinctness check
+        std::vector<uint8_t> seen(h->n_val, 0);
+        for (uint32_t i = 0; i < n_active; ++i) {
+            if (active_indices[i] >= h->n_val) return fail(h, PE_ERR_INVALID_ARG, "active index out of range");
+            if (seen[active_indices[i]]) return fail(h, PE_ERR_INVALID_ARG, "duplicate active index");
+            seen[active_indices[i]] = 1;
+        }
+    }
+    return PE_OK;
+}
+
 // Re-pack one attestation's bits into 32-bit words (zero padded, masked to n_use bits); returns popcount.
 uint32_t pack_bits(const uint8_t* src, uint32_t n_use, uint32_t* dst_words)
 {
@@ -641,26 +666,8 @@ static int compute_committees_impl(pe_engine* h, uint64_t epoch, const uint8_t s
     if (n_committees == 0 || n_committees % h->cfg.slots_per_epoch != 0)
         return fail(h, PE_ERR_INVALID_ARG, "n_committees must be a positive multiple of SLOTS_PER_EPOCH");
     if (shuffle_round_count > 255) return fail(h, PE_ERR_INVALID_ARG, "shuffle_round_count is a uint8 in the spec");
-    // active_indices NULL = every validator 0 .. n_active - 1 is active (get_active_validator_indices of a registry
-    // without pending or exited validators): nothing to validate, nothing to upload
+    PE_TRY(validate_active_set(h, active_indices, n_active));
     const bool identity = active_indices == nullptr;
-    if (identity) {
-        if (n_active > h->n_val) return fail(h, PE_ERR_INVALID_ARG, "n_active exceeds the registry");
-    } else {   // the active set: distinct validator indices (get_active_validator_indices is increasing)
-        bool increasing = true;
-        for (uint32_t i = 0; i < n_active && increasing; ++i) {
-            if (active_indices[i] >= h->n_val) return fail(h, PE_ERR_INVALID_ARG, "active index out of range");
-            if (i && active_indices[i] <= active_indices[i - 1]) increasing = false;
-        }
-        if (!increasing) {  // not sorted: the general distinctness check
-            std::vector<uint8_t> seen(h->n_val, 0);
-            for (uint32_t i = 0; i < n_active; ++i) {
-                if (active_indices[i] >= h->n_val) return fail(h, PE_ERR_INVALID_ARG, "active index out of range");
-                if (seen[active_indices[i]]) return fail(h, PE_ERR_INVALID_ARG, "duplicate active index");
-                seen[active_indices[i]] = 1;
-            }
-        }
-    }
     lap.mark("comm.1_validate");
     std::vector<uint32_t> offsets(n_committees + 1);
     for (uint32_t c = 0; c <= n_committees; ++c)

@@ -826,6 +826,49 @@ uint32_t launch_ffg_balances(hipStream_t s, const uint64_t* balance, const uint8
     return (uint32_t)blocks;
 }
 
+// ------------------------------------------------------------------ effective-balance hysteresis
+// process_effective_balance_updates (pe:122-133), one lane per validator over the working-state view:
+//   if balance + DOWNWARD_THRESHOLD < effective_balance or effective_balance + UPWARD_THRESHOLD < balance:
+//       effective_balance = min(balance - balance % EFFECTIVE_BALANCE_INCREMENT, MAX_EFFECTIVE_BALANCE)
+// The two comparisons are written as differences, which say the same over the reference's unbounded integers and cannot
+// wrap in 64 bits.  Writes the balance and its u16 increment count where the value changed; *n_changed counts those
+// (a ballot per wave, one atomic per wave).
+__global__ void __launch_bounds__(256)
+k_effective_balance_update(const unsigned long long* __restrict__ balances, unsigned long long* __restrict__ eff_balance,
+                           uint16_t* __restrict__ increments, uint64_t n_val, unsigned long long increment,
+                           unsigned long long downward_threshold, unsigned long long upward_threshold,
+                           unsigned long long max_eff, unsigned long long* __restrict__ n_changed)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool changed = false;
+    if (i < n_val) {
+        const unsigned long long balance = balances[i], eff = eff_balance[i];
+        if ((eff > balance && eff - balance > downward_threshold) || (balance > eff && balance - eff > upward_threshold)) {
+            const unsigned long long next = min(balance - balance % increment, max_eff);
+            if (next != eff) {
+                eff_balance[i] = next;
+                increments[i] = (uint16_t)(next / increment);  // <= max_eff / increment <= 65535 (checked by the host)
+                changed = true;
+            }
+        }
+    }
+    const unsigned long long ballot = __ballot(changed);
+    if ((threadIdx.x & 63) == 0 && ballot) atomicAdd(n_changed, (unsigned long long)__builtin_popcountll(ballot));
+}
+
+void launch_effective_balance_update(hipStream_t s, const uint64_t* balances, uint64_t* eff_balance, uint16_t* increments,
+                                     uint64_t n_val, uint64_t increment, uint64_t downward_threshold,
+                                     uint64_t upward_threshold, uint64_t max_eff, uint64_t* n_changed)
+{
+    if (n_val == 0) return;
+    hipLaunchKernelGGL(k_effective_balance_update, dim3((unsigned)((n_val + 255) / 256)), dim3(256), 0, s,
+                       reinterpret_cast<const unsigned long long*>(balances),
+                       reinterpret_cast<unsigned long long*>(eff_balance), increments, n_val,
+                       (unsigned long long)increment, (unsigned long long)downward_threshold,
+                       (unsigned long long)upward_threshold, (unsigned long long)max_eff,
+                       reinterpret_cast<unsigned long long*>(n_changed));
+}
+
 // ------------------------------------------------------------------ working-state view = registry
 __global__ void __launch_bounds__(256)
 k_state_view_from_registry(const uint8_t* __restrict__ flags, const unsigned long long* __restrict__ balance,

@@ -423,6 +423,21 @@ void launch_indexed_attestations(hipStream_t s, const AttRow* rows, uint32_t n_r
 uint32_t launch_ffg_balances(hipStream_t s, const uint64_t* balance, const uint8_t* sflags, const uint8_t* part_cur,
                              const uint8_t* part_prev, uint64_t n_val, uint64_t* partials);
 
+// process_effective_balance_updates (pe:122-133) over the working-state view, in place: eff_balance / increments are
+// rewritten where the hysteresis rule moves a validator; *n_changed (device, zeroed by the caller) counts those.
+// thresholds = increment / HYSTERESIS_QUOTIENT * {downward, upward} multiplier; max_eff / increment <= 65535.
+void launch_effective_balance_update(hipStream_t s, const uint64_t* balances, uint64_t* eff_balance, uint16_t* increments,
+                                     uint64_t n_val, uint64_t increment, uint64_t downward_threshold,
+                                     uint64_t upward_threshold, uint64_t max_eff, uint64_t* n_changed);
+
+// compute_proposer_index (pe:604-618), one wave per seed (d_seeds_be: 8 big-endian words each): d_out_proposer[s] = the
+// first accepted candidate of seed s, d_out_tries[s] = the i it was accepted at; NONE32 / max_tries when none of the first
+// max_tries candidates was.  total >= 1 entries of d_indices (null = identity), every one an index into d_eff_balance;
+// rounds <= 255.
+void launch_proposer_sample(hipStream_t s, const uint32_t* d_seeds_be, uint32_t n_seeds, uint32_t total, uint32_t rounds,
+                            const uint32_t* d_indices, const uint64_t* d_eff_balance, uint64_t max_eff, uint32_t max_tries,
+                            uint32_t* d_out_proposer, uint32_t* d_out_tries);
+
 // compute_committee / compute_shuffled_index (pe:495-534) for a whole list: members[i] = indices[shuffled(i)].
 // d_source: rounds * ceil(n/256) * 8 words scratch; d_pivots: rounds words; d_indices null = identity.
 int launch_shuffle(hipStream_t s, const uint32_t* d_seed_be, uint32_t n, uint32_t rounds, uint32_t* d_source,

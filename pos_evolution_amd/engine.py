@@ -705,6 +705,45 @@ class Engine:
         self._check(self._lib.pe_ffg_balances(self._h, _ptr(out, C.c_uint64)))
         return int(out[0]), int(out[1]), int(out[2])
 
+    # -- epoch boundary ----------------------------------------------------
+    def compute_proposers(self, seeds, active_indices, rounds: int = 90,
+                          max_effective_balance: int = 32 * 10**9, max_tries: int = 0):
+        """compute_proposer_index (pe:604-618) on the GPU, once per seed, over the working-state view's effective
+        balances.  seeds: a sequence of 32-byte seeds (or a uint8 array of n x 32); active_indices: the index array, or an
+        int n meaning validators 0 .. n - 1.  -> (proposers uint32[n_seeds], tries uint32[n_seeds]); a proposer of
+        0xFFFFFFFF (tries == max_tries) means none of the first max_tries candidates (0 = 4096) was accepted."""
+        if isinstance(seeds, np.ndarray):
+            sd = np.ascontiguousarray(seeds, dtype=np.uint8).reshape(-1)
+        else:
+            sd = np.frombuffer(b"".join(bytes(s) for s in seeds), dtype=np.uint8)
+        assert sd.size % 32 == 0, "seeds are 32 bytes each"
+        n_seeds = sd.size // 32
+        if isinstance(active_indices, (int, np.integer)):
+            act, n_act = None, int(active_indices)
+        else:
+            act = np.ascontiguousarray(active_indices, dtype=np.uint32)
+            n_act = act.size
+        prop = np.empty(max(n_seeds, 1), dtype=np.uint32)
+        tries = np.empty(max(n_seeds, 1), dtype=np.uint32)
+        self._check(self._lib.pe_compute_proposers(self._h, _ptr(sd if n_seeds else None, C.c_uint8), n_seeds,
+                                                   _ptr(act, C.c_uint32), n_act, int(rounds),
+                                                   int(max_effective_balance), int(max_tries), _ptr(prop, C.c_uint32),
+                                                   _ptr(tries, C.c_uint32)))
+        return prop[:n_seeds], tries[:n_seeds]
+
+    def effective_balance_updates(self, balances, max_effective_balance: int = 32 * 10**9, hysteresis_quotient: int = 4,
+                                  downward_multiplier: int = 1, upward_multiplier: int = 5, want_result: bool = True):
+        """process_effective_balance_updates (pe:122-133) on the working-state view, in place.  balances: state.balances
+        (one per validator).  -> (n_changed, new effective balances uint64[n] | None when not want_result)."""
+        bal = np.ascontiguousarray(balances, dtype=np.uint64)
+        out = np.empty(max(bal.size, 1), dtype=np.uint64) if want_result else None
+        n_changed = C.c_uint64(0)
+        self._check(self._lib.pe_effective_balance_updates(self._h, bal.size, _ptr(bal if bal.size else None, C.c_uint64),
+                                                           int(max_effective_balance), int(hysteresis_quotient),
+                                                           int(downward_multiplier), int(upward_multiplier),
+                                                           C.addressof(n_changed), _ptr(out, C.c_uint64)))
+        return int(n_changed.value), (out[:bal.size] if want_result else None)
+
     def g1_sum(self, offsets, index=None, points96=None) -> np.ndarray:
         off = np.ascontiguousarray(offsets, dtype=np.uint32)
         idx = None if index is None else np.ascontiguousarray(index, dtype=np.uint32)

@@ -12,6 +12,8 @@ pos-evolution.md (``pe:N``):
     find_attester_slashings(store, attestations)            pe:1128, pe:1134-1143 (the detection the handlers presume)
     get_head(store) -> Root                                 pe:1102-1116
     process_attestation(state, attestation)                 pe:722-754    (state bound with bind_state)
+    compute_proposer_index(state, indices, seed)            pe:604-618    (state bound with bind_state)
+    process_effective_balance_updates(state)                pe:122-133    (state bound with bind_state)
 
 Objects are duck-typed: anything exposing the pyspec's field names works
 (``attestation.data.beacon_block_root``, ``attestation.aggregation_bits``,
@@ -470,3 +472,43 @@ def process_justification_and_finalization(state, *, get_block_root: Callable) -
     state._last_ffg_balances = (total_active_balance, previous_target_balance, current_target_balance)
     weigh_justification_and_finalization(state, total_active_balance, previous_target_balance,
                                          current_target_balance, get_block_root=get_block_root, slots_per_epoch=spe)
+
+
+# ----------------------------------------------------------------------------- epoch boundary
+SHUFFLE_ROUND_COUNT = 90
+MAX_EFFECTIVE_BALANCE = 32 * 10**9
+HYSTERESIS_QUOTIENT = 4
+HYSTERESIS_DOWNWARD_MULTIPLIER = 1
+HYSTERESIS_UPWARD_MULTIPLIER = 5
+
+
+def compute_proposer_index(state, indices: Sequence[int], seed: bytes, *, shuffle_round_count: int = SHUFFLE_ROUND_COUNT,
+                           max_effective_balance: int = MAX_EFFECTIVE_BALANCE, max_tries: int = 0) -> int:
+    """pe:604-618.  ``state`` must have been bound with ``bind_state``: the effective balances sampled are the
+    working-state view the binding uploaded.  Where the reference would loop forever (no candidate among the first
+    ``max_tries``, 0 = 4096, is accepted) this raises."""
+    b = _binding(state)
+    assert b is not None, "compute_proposer_index: bind_state(engine, state, ...) first"
+    assert len(indices) > 0
+    proposers, _ = b.engine.compute_proposers([bytes(seed)], np.asarray(indices, dtype=np.uint32), shuffle_round_count,
+                                              max_effective_balance, max_tries)
+    assert int(proposers[0]) != _abi.NONE32, "compute_proposer_index: no candidate was accepted within max_tries"
+    return int(proposers[0])
+
+
+def process_effective_balance_updates(state, *, max_effective_balance: int = MAX_EFFECTIVE_BALANCE,
+                                      hysteresis_quotient: int = HYSTERESIS_QUOTIENT,
+                                      downward_multiplier: int = HYSTERESIS_DOWNWARD_MULTIPLIER,
+                                      upward_multiplier: int = HYSTERESIS_UPWARD_MULTIPLIER) -> None:
+    """pe:122-133.  ``state`` must have been bound with ``bind_state``; the hysteresis rule runs over the engine's
+    working-state view against ``state.balances`` and the new effective balances are written back to
+    ``state.validators``."""
+    b = _binding(state)
+    assert b is not None, "process_effective_balance_updates: bind_state(engine, state, ...) first"
+    n = len(state.validators)
+    balances = np.fromiter((int(x) for x in state.balances), dtype=np.uint64, count=n)
+    n_changed, new = b.engine.effective_balance_updates(balances, max_effective_balance, hysteresis_quotient,
+                                                        downward_multiplier, upward_multiplier)
+    if n_changed:
+        for validator, value in zip(state.validators, new):
+            validator.effective_balance = int(value)
