@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define PE_ABI_VERSION 8
+#define PE_ABI_VERSION 9
 
 typedef struct pe_engine pe_engine;
 
@@ -215,8 +215,9 @@ int pe_set_committees(pe_engine* h, uint64_t epoch, uint32_t n_committees,
 /* The same table computed ON THE GPU from the epoch's seed: compute_committee (pe:495-504) over
  * compute_shuffled_index (pe:513-534, swap-or-not, shuffle_round_count rounds of SHA-256) for every committee
  * of the epoch: committee c = [active_indices[shuffled(i)] for i in [n*c/count, n*(c+1)/count)], count =
- * n_committees.  seed = get_seed(state, epoch, DOMAIN_BEACON_ATTESTER) (pe:481-486) and the active set are the
- * caller's (state accessors); active_indices NULL = validators 0 .. n_active - 1 (every validator active).  Registers
+ * n_committees.  seed = get_seed(state, epoch, DOMAIN_BEACON_ATTESTER) (pe:481-486) is the caller's (a state
+ * accessor); the active set is the caller's list, or PE_ACTIVE_RESIDENT = the list pe_active_set left on the device
+ * (below); active_indices NULL = validators 0 .. n_active - 1 (every validator active).  Registers
  * the table for `epoch` like pe_set_committees and KEEPS IT ON THE DEVICE; out_offsets (n_committees + 1) and
  * out_members (n_active) are optional copies of the result (NULL: nothing is read back). */
 int pe_compute_committees(pe_engine* h, uint64_t epoch, const uint8_t seed[32], const uint32_t* active_indices,
@@ -408,7 +409,8 @@ int pe_ffg_balances(pe_engine* h, uint64_t out[3]);
  * effective balances = the working-state view (pe_state_set_validators; the pe_set_validators data until then).
  * seeds: n_seeds x 32 bytes (the caller's state accessor, e.g. one per slot of an epoch).
  * active_indices / n_active / shuffle_round_count: exactly as pe_compute_committees (NULL = validators 0..n_active-1;
- * same validation, same bound on the round count); an empty active set is PE_ERR_INVALID_ARG (pe:608).
+ * same validation, same bound on the round count, PE_ACTIVE_RESIDENT accepted); an empty active set is
+ * PE_ERR_INVALID_ARG (pe:608).
  * max_tries: candidates examined per seed before giving up (0 = 4096).
  * out_proposers u32[n_seeds]: the validator index, or 0xFFFFFFFF where no candidate within max_tries was accepted
  *   (the reference loops forever there).
@@ -433,6 +435,47 @@ int pe_effective_balance_updates(pe_engine* h, uint64_t n, const uint64_t* balan
                                  uint64_t max_effective_balance, uint64_t hysteresis_quotient,
                                  uint64_t downward_multiplier, uint64_t upward_multiplier,
                                  uint64_t* out_n_changed, uint64_t* out_effective_balance);
+
+/* ---- the active validator set over the resident registry ------------------ */
+/* Validator.activation_epoch / exit_epoch (pe:43-44) of the whole registry, copied into device memory (16 B per
+ * validator).  n must equal pe_num_validators(h): else PE_ERR_INVALID_ARG and nothing changes.  FAR_FUTURE_EPOCH is
+ * 2^64 - 1; every comparison the engine makes on these values is unsigned 64-bit.  The arrays are dropped where the
+ * working-state view is: pe_store_init, and a pe_set_validators that changes n.  Setting them drops the resident
+ * active list (it was compacted from the previous values).  *out_is_set = 0: none held, the outputs are not written.
+ * Checkpoint / resume: read them with _get, hand them back with _set. */
+int pe_registry_set_epochs(pe_engine* h, uint64_t n, const uint64_t* activation_epoch, const uint64_t* exit_epoch);
+int pe_registry_get_epochs(pe_engine* h, uint64_t n, uint64_t* out_activation_epoch, uint64_t* out_exit_epoch,
+                           int* out_is_set);
+
+/* get_active_validator_indices(state, epoch): every v with activation_epoch[v] <= epoch < exit_epoch[v]
+ * (is_active_validator), in increasing order of v -- the order the shuffle reads (pe:495-504).  One ordered compaction
+ * over the resident epochs; the list STAYS ON THE DEVICE as the handle's resident active list, with its epoch and length.
+ * *out_n_active = len(list): what get_committee_count_per_slot (pe:461-468), compute_weak_subjectivity_period
+ *   (pe:1267) and get_latest_weak_subjectivity_checkpoint_epoch (pe:1234) ask for.
+ * *out_total_balance = max(EFFECTIVE_BALANCE_INCREMENT, sum of effective_balance over the list): get_total_active_balance
+ *   (pe:1268) for `epoch`; effective balances = the working-state view (pe_state_set_validators; the pe_set_validators
+ *   data until then).  The same quantity and rule as pe_ffg_balances out[0]; slashed validators count, as there.
+ * out_indices (may be NULL; capacity pe_num_validators(h)): a copy of the list, *out_n_active entries.
+ * Without epochs (pe_registry_set_epochs): PE_ERR_STATE.  One resident list per handle: the next call replaces it.
+ * Synchronous (completes open pipelines first); one GPU: PE_ERR_STATE on a handle with pe_dist_init* active. */
+int pe_active_set(pe_engine* h, uint64_t epoch, uint32_t* out_n_active, uint64_t* out_total_balance,
+                  uint32_t* out_indices);
+
+/* As `active_indices` of pe_compute_committees, pe_compute_committees_async and pe_compute_proposers: the resident
+ * list, read by the kernels where pe_active_set left it -- no host validation (increasing and in range by
+ * construction), no copy, no upload.  n_active must equal the resident length (else PE_ERR_INVALID_ARG); without a
+ * resident list the calls return PE_ERR_STATE.  The list is dropped with the epochs, and by pe_registry_set_epochs.
+ * pe_compute_committees_async reads the list on the shuffle's own stream, behind the call's return: it records an
+ * event there, and the next pe_active_set makes the engine's stream wait for that event before its kernels rewrite
+ * the list (ordered on the device, no host wait; one buffer, not two). */
+#define PE_ACTIVE_RESIDENT ((const uint32_t*)(uintptr_t)1)
+
+/* PE_VAL_ACTIVE / PE_VAL_ACTIVE_PREV of the working-state view from the resident epochs: PE_VAL_ACTIVE = activity at
+ * current_epoch, PE_VAL_ACTIVE_PREV = activity at max(current_epoch, 1) - 1 (get_previous_epoch's clamp at
+ * GENESIS_EPOCH).  PE_VAL_SLASHED and every other bit are kept.  If the view still mirrors pe_set_validators, it is
+ * first materialised from it exactly as pe_effective_balance_updates does.  The justified-checkpoint flags get_head
+ * weighs (pe_get_validator_flags) are NOT changed.  Without epochs: PE_ERR_STATE.  Synchronous; one GPU. */
+int pe_state_refresh_activity(pe_engine* h, uint64_t current_epoch);
 
 /* Plain G1 sum over caller-chosen groups: out[g] = sum_{j in [offsets[g], offsets[g+1])}
  * points[index[j]] (index NULL = identity).  points96 NULL = the validators' pubkeys. */

@@ -148,6 +148,10 @@ SIGNATURES = {
                                        _u32p]),
     "pe_effective_balance_updates": (C.c_int, [_H, C.c_uint64, _u64p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _u64p,
                                                _u64p]),
+    "pe_registry_set_epochs": (C.c_int, [_H, C.c_uint64, _u64p, _u64p]),
+    "pe_registry_get_epochs": (C.c_int, [_H, C.c_uint64, _u64p, _u64p, C.c_void_p]),
+    "pe_active_set": (C.c_int, [_H, C.c_uint64, C.c_void_p, C.c_void_p, _u32p]),
+    "pe_state_refresh_activity": (C.c_int, [_H, C.c_uint64]),
     "pe_g1_sum": (C.c_int, [_H, _u8p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u8p]),
     "pe_get_block": (C.c_int, [_H, C.c_uint32, _u8p, _u32p, _u64p, _u64p, _u8p, _u64p, _u8p]),
     "pe_get_validator_flags": (C.c_int, [_H, _u8p, C.c_uint64]),
@@ -209,6 +213,7 @@ SIGNATURES = {
 
 PE_ROWS_RESIDENT = 1  # include/posevo.h: "every group of the last pe_aggregate over rows in device memory"
 PE_BITS_RESIDENT = 1  # the address include/posevo.h defines as "bits are where the last pe_aggregate left them"
+PE_ACTIVE_RESIDENT = 1  # ... and as "the active list is where the last pe_active_set left it"
 PE_ATT_FLAG_OVERLAPPING_BITS = 0x4
 
 _lib = None

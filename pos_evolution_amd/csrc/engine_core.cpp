@@ -544,8 +544,10 @@ void pe_engine_destroy(pe_engine* h)
                       &h->d_part_cur, &h->d_part_prev, &h->d_tsize, &h->d_tparent, &h->d_trank, &h->d_tleaf,
                       &h->d_tpos, &h->d_tidx, &h->d_direct, &h->d_weights, &h->d_totals, &h->d_head,
                       &h->d_broot_tab, &h->d_broots, &h->d_bslot_pos,
-                      &h->d_partials, &h->d_lane_partials, &h->d_out96, &h->d_tmp_points, &h->d_tmp_be, &h->d_tmp_points30})
+                      &h->d_partials, &h->d_lane_partials, &h->d_out96, &h->d_tmp_points, &h->d_tmp_be, &h->d_tmp_points30,
+                      &h->d_activation_epoch, &h->d_exit_epoch, &h->d_active, &h->d_active_wg})
         b->release();
+    if (h->ev_active_read) (void)hipEventDestroy(h->ev_active_read);
     for (auto& t : h->tables) {
         t.d_members.release(); t.d_offsets.release(); t.d_inv_comm.release(); t.d_inv_pos.release();
         t.d_stage.release(); t.h_stage.release();

@@ -9,7 +9,8 @@
 //   engine_g1.cpp      G1 / G2 sums over caller-chosen groups, BLSPubkey / BLSSignature wire formats
 //   engine_dist.cpp    multi-GPU exchange: RCCL owned by the engine, function-table collectives
 //   engine_slash.cpp   slashing detection: the per-validator vote history and its scan (double and surround votes)
-//   engine_epoch.cpp   the epoch boundary: proposer sampling and the effective-balance hysteresis over the resident registry
+//   engine_epoch.cpp   the epoch boundary: the active set, proposer sampling and the effective-balance hysteresis over the
+//                      resident registry
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -221,6 +222,15 @@ struct pe_engine {
     DevBuf d_sbalance, d_sflags;  // working-state view (process_attestation rewards, FFG sums)
     bool state_view_set = false;  // false: the working state mirrors the pe_set_validators data
     std::vector<uint8_t> h_flags;  // host mirror (equivocating bit is OR-ed in here)
+    // ---- registry epochs and the resident active list (engine_epoch.cpp) ----
+    DevBuf d_activation_epoch, d_exit_epoch;  // u64[n_val] each (pe:43-44); dropped where the working-state view is
+    bool epochs_set = false;
+    DevBuf d_active, d_active_wg;    // get_active_validator_indices of active_epoch, u32[active_n] | the compaction's scratch
+    bool active_valid = false;
+    uint64_t active_epoch = 0;
+    uint32_t active_n = 0;
+    hipEvent_t ev_active_read = nullptr;  // behind the last pe_compute_committees_async that reads d_active, on its stream
+    bool active_read_pending = false;     // ... and the engine's stream has not waited for it yet
 
     // ---- tree snapshot (pre-order) ----
     bool tree_dirty = true;
@@ -568,7 +578,18 @@ int run_tree(pe_engine* h, uint64_t* d_direct, const VoteTotals* d_totals, int c
 int ensure_validator_arrays(pe_engine* h, uint64_t n);
 int upload_balances(pe_engine* h, uint64_t n, const uint64_t* bal, const uint8_t* flags);
 // the active set of a shuffle: NULL = validators 0 .. n_active - 1, else distinct indices into the registry
+// ... or PE_ACTIVE_RESIDENT = the list pe_active_set left on the device (n_active must be its length)
 int validate_active_set(pe_engine* h, const uint32_t* active_indices, uint32_t n_active);
+// the device list a shuffle gathers through: null = identity, the resident list, or `staged` (the caller's, uploaded)
+inline const uint32_t* active_list_dev(const pe_engine* h, const uint32_t* active_indices, const uint32_t* staged)
+{
+    if (active_indices == nullptr) return nullptr;
+    return active_indices == PE_ACTIVE_RESIDENT ? h->d_active.as<uint32_t>() : staged;
+}
+// registry epochs and the resident list say nothing about a new store or a registry of another size (engine_epoch.cpp)
+void registry_epochs_drop(pe_engine* h);
+// a working-state view that still mirrors the registry becomes a view of its own, flags included (engine_epoch.cpp)
+int materialise_state_view(pe_engine* h);
 
 // Re-pack one attestation's bits into 32-bit words (zero padded, masked to n_use bits); returns popcount.
 uint32_t pack_bits(const uint8_t* src, uint32_t n_use, uint32_t* dst_words);

@@ -173,8 +173,16 @@ CommitteeTable* find_table(pe_engine* h, uint64_t epoch)
 // The active set of a shuffle (pe_compute_committees, pe_compute_proposers).  active_indices NULL = every validator
 // 0 .. n_active - 1 is active (get_active_validator_indices of a registry without pending or exited validators): nothing
 // to validate beyond the count; otherwise distinct validator indices (get_active_validator_indices is increasing).
+// PE_ACTIVE_RESIDENT = the list pe_active_set compacted on the device: increasing and in range by construction, so only its
+// presence and its length are checked and the host reads none of it.
 int validate_active_set(pe_engine* h, const uint32_t* active_indices, uint32_t n_active)
 {
+    if (active_indices == PE_ACTIVE_RESIDENT) {
+        if (!h->active_valid)
+            return fail(h, PE_ERR_STATE, "PE_ACTIVE_RESIDENT: the handle holds no resident active list (pe_active_set first)");
+        if (n_active != h->active_n) return fail(h, PE_ERR_INVALID_ARG, "PE_ACTIVE_RESIDENT: n_active differs from the resident list's length");
+        return PE_OK;
+    }
     if (active_indices == nullptr) {
         if (n_active > h->n_val) return fail(h, PE_ERR_INVALID_ARG, "n_active exceeds the registry");
         return PE_OK;
@@ -342,6 +350,7 @@ int pe_store_init(pe_engine* h, uint64_t genesis_time, uint64_t anchor_slot, con
     // chain's states), the working-state view and its participation arrays, the resident aggregate
     for (auto& t : h->tables) { t.n_committees = 0; t.offsets.clear(); t.is_partition = false; t.stamp = 0; }
     h->state_view_set = false;
+    registry_epochs_drop(h);
     h->res_valid = false;
     h->rr.valid = false;
     PE_TRY(slasher_reset(h));  // what the validators of the previous store attested says nothing about this one
@@ -422,6 +431,7 @@ int pe_set_validators(pe_engine* h, uint64_t n, const uint8_t* pubkeys96, const 
     }
     if (h->d_totals.p) HIP_TRY(h, hipMemsetAsync(h->d_totals.p, 0, h->d_totals.cap, h->stream));  // grid may shrink
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (n != old_n) registry_epochs_drop(h);  // u64[old_n] arrays and a list of the old registry
     h->n_val = n;
     return PE_OK;
 }
@@ -668,6 +678,7 @@ static int compute_committees_impl(pe_engine* h, uint64_t epoch, const uint8_t s
     if (shuffle_round_count > 255) return fail(h, PE_ERR_INVALID_ARG, "shuffle_round_count is a uint8 in the spec");
     PE_TRY(validate_active_set(h, active_indices, n_active));
     const bool identity = active_indices == nullptr;
+    const bool staged = !identity && active_indices != PE_ACTIVE_RESIDENT;  // a host list: copied and uploaded
     lap.mark("comm.1_validate");
     std::vector<uint32_t> offsets(n_committees + 1);
     for (uint32_t c = 0; c <= n_committees; ++c)
@@ -710,7 +721,7 @@ static int compute_committees_impl(pe_engine* h, uint64_t epoch, const uint8_t s
             HIP_TRY(h, hipStreamCreateWithFlags(&h->prep_stream, hipStreamNonBlocking));
         }
         const size_t o_seed = 0, o_offs = 64, o_idx = (64 + 4ull * (n_committees + 1) + 63) & ~size_t(63);
-        const size_t bytes = o_idx + (identity ? 0 : 4ull * n_active) + 64;
+        const size_t bytes = o_idx + (staged ? 4ull * n_active : 0) + 64;
         HIP_TRY(h, t->h_stage.ensure(bytes));
         HIP_TRY(h, t->d_stage.ensure(bytes));
         uint8_t* hs = t->h_stage.as<uint8_t>();
@@ -718,7 +729,7 @@ static int compute_committees_impl(pe_engine* h, uint64_t epoch, const uint8_t s
         for (int i = 0; i < 8; ++i)
             sw[i] = ((uint32_t)seed[4 * i] << 24) | ((uint32_t)seed[4 * i + 1] << 16) | ((uint32_t)seed[4 * i + 2] << 8) | seed[4 * i + 3];
         memcpy(hs + o_offs, offsets.data(), 4ull * (n_committees + 1));
-        if (!identity && n_active) memcpy(hs + o_idx, active_indices, 4ull * n_active);
+        if (staged && n_active) memcpy(hs + o_idx, active_indices, 4ull * n_active);
         HIP_TRY(h, t->d_members.ensure(std::max<size_t>(64, 4ull * n_active)));
         HIP_TRY(h, t->d_offsets.ensure(4ull * (n_committees + 1)));
         HIP_TRY(h, h->d_shuffle_scratch.ensure(std::max<size_t>(64, 32ull * nb * shuffle_round_count + 4ull * shuffle_round_count + 64)));
@@ -732,7 +743,13 @@ static int compute_committees_impl(pe_engine* h, uint64_t epoch, const uint8_t s
         uint32_t* d_source = h->d_shuffle_scratch.as<uint32_t>();
         uint32_t* d_pivots = d_source + 8ull * nb * shuffle_round_count;
         launch_shuffle(ps, reinterpret_cast<uint32_t*>(ds + o_seed), n_active, shuffle_round_count, d_source, d_pivots,
-                       identity ? nullptr : reinterpret_cast<uint32_t*>(ds + o_idx), t->d_members.as<uint32_t>());
+                       active_list_dev(h, active_indices, reinterpret_cast<uint32_t*>(ds + o_idx)), t->d_members.as<uint32_t>());
+        if (!identity && !staged) {
+            // the shuffle reads the resident list where it lies: a later pe_active_set orders its rewrite behind this event
+            if (!h->ev_active_read) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_active_read, hipEventDisableTiming));
+            HIP_TRY(h, hipEventRecord(h->ev_active_read, ps));
+            h->active_read_pending = true;
+        }
         HIP_TRY(h, hipMemcpyAsync(t->d_offsets.p, ds + o_offs, 4ull * (n_committees + 1), hipMemcpyDeviceToDevice, ps));
         if (h->n_val)
             launch_invert_committees(ps, t->d_members.as<uint32_t>(), t->d_offsets.as<uint32_t>(), n_committees,
@@ -751,14 +768,14 @@ static int compute_committees_impl(pe_engine* h, uint64_t epoch, const uint8_t s
         return PE_OK;
     }
     Stage st(h);
-    PE_TRY(st.reserve(64 + (identity ? 0 : 4ull * n_active) + 4ull * (n_committees + 1) + 1024));
+    PE_TRY(st.reserve(64 + (staged ? 4ull * n_active : 0) + 4ull * (n_committees + 1) + 1024));
     const size_t off_seed = st.alloc(32);
-    const size_t off_idx = st.alloc(identity ? 4 : 4ull * n_active + 4);
+    const size_t off_idx = st.alloc(staged ? 4ull * n_active + 4 : 4);
     const size_t off_offs = st.alloc(4ull * (n_committees + 1));
     uint32_t* sw = st.host<uint32_t>(off_seed);
     for (int i = 0; i < 8; ++i)
         sw[i] = ((uint32_t)seed[4 * i] << 24) | ((uint32_t)seed[4 * i + 1] << 16) | ((uint32_t)seed[4 * i + 2] << 8) | seed[4 * i + 3];
-    if (!identity && n_active) memcpy(st.host<uint32_t>(off_idx), active_indices, 4ull * n_active);
+    if (staged && n_active) memcpy(st.host<uint32_t>(off_idx), active_indices, 4ull * n_active);
     memcpy(st.host<uint32_t>(off_offs), offsets.data(), 4ull * (n_committees + 1));
     HIP_TRY(h, t->d_members.ensure(std::max<size_t>(64, 4ull * n_active)));
     HIP_TRY(h, t->d_offsets.ensure(4ull * (n_committees + 1)));
@@ -768,7 +785,7 @@ static int compute_committees_impl(pe_engine* h, uint64_t epoch, const uint8_t s
     uint32_t* d_source = h->d_tmp_be.as<uint32_t>();
     uint32_t* d_pivots = d_source + 8ull * nb * shuffle_round_count;
     launch_shuffle(cs, st.dev<uint32_t>(off_seed), n_active, shuffle_round_count, d_source, d_pivots,
-                   identity ? nullptr : st.dev<uint32_t>(off_idx), t->d_members.as<uint32_t>());
+                   active_list_dev(h, active_indices, st.dev<uint32_t>(off_idx)), t->d_members.as<uint32_t>());
     HIP_TRY(h, hipMemcpyAsync(t->d_offsets.p, st.dev<uint32_t>(off_offs), 4ull * (n_committees + 1),
                               hipMemcpyDeviceToDevice, cs));
     if (h->n_val) {

@@ -438,6 +438,25 @@ void launch_proposer_sample(hipStream_t s, const uint32_t* d_seeds_be, uint32_t 
                             const uint32_t* d_indices, const uint64_t* d_eff_balance, uint64_t max_eff, uint32_t max_tries,
                             uint32_t* d_out_proposer, uint32_t* d_out_tries);
 
+// get_active_validator_indices(state, epoch): the ordered compaction of the registry's active validators
+// (activation_epoch[v] <= epoch < exit_epoch[v], unsigned 64-bit), its length and its effective-balance sum in three
+// launches on one stream: k_active_compact<false> (per-workgroup counts and balance partials), k_active_scan (one workgroup:
+// exclusive offsets, the count, the sum), k_active_compact<true> (the indices, in increasing order, no atomics).
+constexpr int ACTIVE_WG = 256;          // T: validators per workgroup of k_active_compact, one lane each
+constexpr int ACTIVE_SCAN_TILE = 1024;  // S: workgroup counts one pass of k_active_scan's loop takes, one lane each
+struct ActiveTotals { unsigned long long balance; uint32_t n_active; uint32_t pad; };
+// d_wg: scratch of active_scratch_bytes(n_val) bytes; d_out_indices: capacity n_val; *d_totals: written by the scan
+// (balance = the plain 64-bit sum, the caller applies get_total_balance's floor).  n_val >= 1.
+size_t active_scratch_bytes(uint64_t n_val);
+void launch_active_compact(hipStream_t s, const uint64_t* d_activation_epoch, const uint64_t* d_exit_epoch, uint64_t epoch,
+                           const uint64_t* d_eff_balance, uint64_t n_val, void* d_wg, uint32_t* d_out_indices,
+                           ActiveTotals* d_totals);
+
+// PE_VAL_ACTIVE / PE_VAL_ACTIVE_PREV of the working-state view from the registry epochs: activity at current_epoch and at
+// previous_epoch; every other bit of sflags[v] is kept.
+void launch_activity_flags(hipStream_t s, const uint64_t* d_activation_epoch, const uint64_t* d_exit_epoch,
+                           uint64_t current_epoch, uint64_t previous_epoch, uint64_t n_val, uint8_t* sflags);
+
 // compute_committee / compute_shuffled_index (pe:495-534) for a whole list: members[i] = indices[shuffled(i)].
 // d_source: rounds * ceil(n/256) * 8 words scratch; d_pivots: rounds words; d_indices null = identity.
 int launch_shuffle(hipStream_t s, const uint32_t* d_seed_be, uint32_t n, uint32_t rounds, uint32_t* d_source,

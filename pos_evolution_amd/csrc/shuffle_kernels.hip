@@ -12,6 +12,7 @@
 //   source = hash(seed + uint_to_bytes(uint8(round)) + uint_to_bytes(uint32(position // 256)))   (pe:525-529)
 //   byte   = source[(position % 256) // 8] ; bit = (byte >> (position % 8)) % 2        (pe:530-531)
 // Integer/hash work, no MFMA.  SURVEY.md 8(f) rank 1.
+// Further down: proposer sampling (k_proposer_sample) and the active set the shuffles start from (k_active_compact).
 #include "kernels.h"
 
 namespace posevo {
@@ -370,6 +371,167 @@ void launch_proposer_sample(hipStream_t s, const uint32_t* d_seeds_be, uint32_t 
     hipLaunchKernelGGL(k_proposer_sample, dim3(n_seeds), dim3(PROP_WAVE), 0, s, d_seeds_be, total, rounds, d_indices,
                        reinterpret_cast<const unsigned long long*>(d_eff_balance), (unsigned long long)max_eff, max_tries,
                        d_out_proposer, d_out_tries);
+}
+
+// ------------------------------------------------------------------ active set
+// get_active_validator_indices(state, epoch): every v with activation_epoch[v] <= epoch < exit_epoch[v] (is_active_validator;
+// both comparisons unsigned 64-bit, FAR_FUTURE_EPOCH = 2^64 - 1 is an ordinary value), in increasing order of v, with
+// len(...) and the effective-balance sum get_total_balance needs.  Three launches on one stream:
+//   k_active_compact<false>  one lane per validator, ACTIVE_WG of them per workgroup: the two epochs (coalesced 8-byte loads),
+//                            a wave64 ballot, its popcount and the wave's balance sum; the four waves meet in LDS ->
+//                            wg_count[b], wg_balance[b]
+//   k_active_scan            one workgroup walks the counts ACTIVE_SCAN_TILE at a time: exclusive offsets, the total count
+//                            and the total balance
+//   k_active_compact<true>   the same ballot again; rank in the wave = mbcnt(ballot), the wave's base = the offset of the
+//                            workgroup + the counts of the waves before it -> out_indices[base + rank] = v
+// No atomics and no waiting of one workgroup for another: the order of the output is fixed by construction, and the
+// integer sums are exact in any order.  The second pass re-reads the epochs (16 B per validator).
+constexpr int ACTIVE_WAVES = ACTIVE_WG / 64;
+static_assert(ACTIVE_WG % 64 == 0 && ACTIVE_SCAN_TILE % 64 == 0, "whole waves");
+
+__device__ __forceinline__ bool is_active_validator(unsigned long long activation_epoch, unsigned long long exit_epoch,
+                                                    unsigned long long epoch)
+{
+    return activation_epoch <= epoch && epoch < exit_epoch;
+}
+__device__ __forceinline__ unsigned long long active_wave_sum_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+template <bool SCATTER>
+__global__ void __launch_bounds__(ACTIVE_WG)
+k_active_compact(const unsigned long long* __restrict__ activation_epoch, const unsigned long long* __restrict__ exit_epoch,
+                 unsigned long long epoch, const unsigned long long* __restrict__ eff_balance, uint64_t n_val,
+                 uint32_t* __restrict__ wg_count, unsigned long long* __restrict__ wg_balance,
+                 const uint32_t* __restrict__ wg_offset, uint32_t* __restrict__ out_indices)
+{
+    __shared__ uint32_t wave_count[ACTIVE_WAVES];
+    __shared__ unsigned long long wave_balance[ACTIVE_WAVES];
+    const uint64_t v = (uint64_t)blockIdx.x * ACTIVE_WG + threadIdx.x;
+    const uint32_t wave = threadIdx.x >> 6;
+    const bool active = v < n_val && is_active_validator(activation_epoch[v], exit_epoch[v], epoch);
+    const unsigned long long ballot = __ballot(active);
+    if constexpr (!SCATTER) {
+        const unsigned long long balance = active_wave_sum_u64(active ? eff_balance[v] : 0ull);
+        if ((threadIdx.x & 63) == 0) {
+            wave_count[wave] = (uint32_t)__builtin_popcountll(ballot);
+            wave_balance[wave] = balance;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t count = 0;
+            unsigned long long sum = 0;
+#pragma unroll
+            for (int w = 0; w < ACTIVE_WAVES; ++w) { count += wave_count[w]; sum += wave_balance[w]; }
+            wg_count[blockIdx.x] = count;
+            wg_balance[blockIdx.x] = sum;
+        }
+    } else {
+        if ((threadIdx.x & 63) == 0) wave_count[wave] = (uint32_t)__builtin_popcountll(ballot);
+        __syncthreads();
+        uint32_t base = wg_offset[blockIdx.x];
+#pragma unroll
+        for (int w = 0; w < ACTIVE_WAVES; ++w) base += (uint32_t)w < wave ? wave_count[w] : 0u;
+        // active lanes below this one in the wave
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+        if (active) out_indices[base + rank] = (uint32_t)v;  // base + rank < the total count <= n_val
+    }
+}
+
+// grid: ONE workgroup.  carry is uniform across it; the loop's trip count depends on n_wg alone.
+__global__ void __launch_bounds__(ACTIVE_SCAN_TILE)
+k_active_scan(const uint32_t* __restrict__ wg_count, const unsigned long long* __restrict__ wg_balance, uint32_t n_wg,
+              uint32_t* __restrict__ wg_offset, ActiveTotals* __restrict__ totals)
+{
+    constexpr int WAVES = ACTIVE_SCAN_TILE / 64;
+    __shared__ uint32_t wave_total[WAVES];
+    __shared__ unsigned long long wave_balance[WAVES];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t carry = 0;
+    unsigned long long balance = 0;
+    for (uint32_t tile = 0; tile < n_wg; tile += ACTIVE_SCAN_TILE) {
+        const uint32_t i = tile + threadIdx.x;
+        const uint32_t count = i < n_wg ? wg_count[i] : 0u;
+        if (i < n_wg) balance += wg_balance[i];
+        uint32_t inclusive = count;  // prefix sum over the wave
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t up = __shfl_up(inclusive, off, 64);
+            if (lane >= (uint32_t)off) inclusive += up;
+        }
+        if (lane == 63) wave_total[wave] = inclusive;
+        __syncthreads();
+        uint32_t before = carry, all = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+            const uint32_t t = wave_total[w];
+            before += (uint32_t)w < wave ? t : 0u;
+            all += t;
+        }
+        if (i < n_wg) wg_offset[i] = before + inclusive - count;
+        carry += all;
+        __syncthreads();  // wave_total is rewritten by the next tile
+    }
+    balance = active_wave_sum_u64(balance);
+    if (lane == 0) wave_balance[wave] = balance;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long sum = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) sum += wave_balance[w];
+        totals->balance = sum;
+        totals->n_active = carry;
+        totals->pad = 0;
+    }
+}
+
+// scratch: wg_balance u64[n_wg] | wg_count u32[n_wg] | wg_offset u32[n_wg]
+static uint32_t active_workgroups(uint64_t n_val) { return (uint32_t)((n_val + ACTIVE_WG - 1) / ACTIVE_WG); }
+size_t active_scratch_bytes(uint64_t n_val) { return 16ull * active_workgroups(n_val); }
+
+void launch_active_compact(hipStream_t s, const uint64_t* d_activation_epoch, const uint64_t* d_exit_epoch, uint64_t epoch,
+                           const uint64_t* d_eff_balance, uint64_t n_val, void* d_wg, uint32_t* d_out_indices,
+                           ActiveTotals* d_totals)
+{
+    if (n_val == 0) return;
+    const uint32_t n_wg = active_workgroups(n_val);
+    unsigned long long* wg_balance = static_cast<unsigned long long*>(d_wg);
+    uint32_t* wg_count = reinterpret_cast<uint32_t*>(wg_balance + n_wg);
+    uint32_t* wg_offset = wg_count + n_wg;
+    const unsigned long long* act = reinterpret_cast<const unsigned long long*>(d_activation_epoch);
+    const unsigned long long* ext = reinterpret_cast<const unsigned long long*>(d_exit_epoch);
+    const unsigned long long* bal = reinterpret_cast<const unsigned long long*>(d_eff_balance);
+    hipLaunchKernelGGL(k_active_compact<false>, dim3(n_wg), dim3(ACTIVE_WG), 0, s, act, ext, (unsigned long long)epoch, bal,
+                       n_val, wg_count, wg_balance, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(k_active_scan, dim3(1), dim3(ACTIVE_SCAN_TILE), 0, s, wg_count, wg_balance, n_wg, wg_offset, d_totals);
+    hipLaunchKernelGGL(k_active_compact<true>, dim3(n_wg), dim3(ACTIVE_WG), 0, s, act, ext, (unsigned long long)epoch, bal,
+                       n_val, (uint32_t*)nullptr, (unsigned long long*)nullptr, wg_offset, d_out_indices);
+}
+
+// PE_VAL_ACTIVE (0x01) = activity at current_epoch, PE_VAL_ACTIVE_PREV (0x08) = activity at previous_epoch; the other bits stay.
+__global__ void __launch_bounds__(256)
+k_activity_flags(const unsigned long long* __restrict__ activation_epoch, const unsigned long long* __restrict__ exit_epoch,
+                 unsigned long long current_epoch, unsigned long long previous_epoch, uint64_t n_val,
+                 uint8_t* __restrict__ sflags)
+{
+    const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_val) return;
+    const unsigned long long a = activation_epoch[v], x = exit_epoch[v];
+    const uint32_t f = sflags[v] & ~0x09u;
+    sflags[v] = (uint8_t)(f | (is_active_validator(a, x, current_epoch) ? 0x01u : 0u) |
+                          (is_active_validator(a, x, previous_epoch) ? 0x08u : 0u));
+}
+void launch_activity_flags(hipStream_t s, const uint64_t* d_activation_epoch, const uint64_t* d_exit_epoch,
+                           uint64_t current_epoch, uint64_t previous_epoch, uint64_t n_val, uint8_t* sflags)
+{
+    if (n_val == 0) return;
+    hipLaunchKernelGGL(k_activity_flags, dim3((unsigned)((n_val + 255) / 256)), dim3(256), 0, s,
+                       reinterpret_cast<const unsigned long long*>(d_activation_epoch),
+                       reinterpret_cast<const unsigned long long*>(d_exit_epoch), (unsigned long long)current_epoch,
+                       (unsigned long long)previous_epoch, n_val, sflags);
 }
 
 }  // namespace posevo

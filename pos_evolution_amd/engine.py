@@ -65,6 +65,9 @@ def _ptr(a, ctype=None):
         return a.ctypes.data
 
 
+_ACTIVE_RESIDENT_ARG = DeviceArena(_abi.PE_ACTIVE_RESIDENT, 0)   # the sentinel address, as _ptr passes it on
+
+
 def _att_ptr(arr):
     """ctypes array of pe_attestation or numpy structured array (synth.ATT_DTYPE) -> address."""
     if isinstance(arr, np.ndarray):
@@ -155,6 +158,17 @@ class _RowsResident:
 
 
 ROWS_RESIDENT = _RowsResident()
+
+
+class _ActiveResident:
+    """Sentinel for ``active_indices`` of ``compute_committees``, ``compute_committees_async`` and ``compute_proposers``:
+    the list the last ``active_set`` left on the device (PE_ACTIVE_RESIDENT, include/posevo.h)."""
+
+    def __repr__(self):
+        return "ACTIVE_RESIDENT"
+
+
+ACTIVE_RESIDENT = _ActiveResident()
 
 
 class AggregateResult(dict):
@@ -261,6 +275,7 @@ class Engine:
         self._ring_i = 0
         self._ring_ord = {}
         self._lag = int(self._lib.pe_pipeline_get_lag(self._h)) or 2
+        self._resident_active = 0   # length of the list the last active_set left on the device
 
     def set_pipeline_lag(self, depth: int):
         """Lag depth of ``pipeline(lagged=True)`` blocks (pe_pipeline_set_lag): a block's outputs are complete when the
@@ -424,12 +439,9 @@ class Engine:
                            shuffle_round_count: int = 90, want_result: bool = True):
         """compute_committee / compute_shuffled_index (pe:495-534) for the whole epoch on the GPU; registers the
         table for `epoch` (it stays on the device).  active_indices: the index array, or an int n meaning validators
-        0 .. n - 1.  -> (offsets uint32[C+1], members uint32[n_active]) when want_result, else nothing is read back."""
-        if isinstance(active_indices, (int, np.integer)):   # "every validator 0 .. n - 1 is active": nothing to upload
-            act, n_act = None, int(active_indices)
-        else:
-            act = np.ascontiguousarray(active_indices, dtype=np.uint32)
-            n_act = act.size
+        0 .. n - 1, or ACTIVE_RESIDENT (the list of the last ``active_set``).  -> (offsets uint32[C+1], members
+        uint32[n_active]) when want_result, else nothing is read back."""
+        act, n_act = self._active_arg(active_indices)
         off = np.empty(n_committees + 1, dtype=np.uint32) if want_result else None
         mem = np.empty(max(n_act, 1), dtype=np.uint32) if want_result else None
         self._check(self._lib.pe_compute_committees(self._h, epoch, _root(seed), _ptr(act, C.c_uint32), n_act,
@@ -439,9 +451,11 @@ class Engine:
 
     def compute_committees_async(self, epoch: int, seed: bytes, n_active: int, n_committees: int,
                                  shuffle_round_count: int = 90):
-        """pe_compute_committees_async over validators 0 .. n_active - 1: enqueued on the state-transition stream, nothing
-        waited for or read back; the table is usable by the calls that follow."""
-        rc = self._lib.pe_compute_committees_async(self._h, epoch, _root(seed), None, int(n_active), n_committees,
+        """pe_compute_committees_async over validators 0 .. n_active - 1, or over the list of the last ``active_set``
+        (n_active = ACTIVE_RESIDENT): enqueued on the state-transition stream, nothing waited for or read back; the table
+        is usable by the calls that follow."""
+        act, n_act = self._active_arg(n_active)
+        rc = self._lib.pe_compute_committees_async(self._h, epoch, _root(seed), _ptr(act, C.c_uint32), n_act, n_committees,
                                                    shuffle_round_count)
         if rc:
             self._check(rc)
@@ -706,11 +720,51 @@ class Engine:
         return int(out[0]), int(out[1]), int(out[2])
 
     # -- epoch boundary ----------------------------------------------------
+    def _active_arg(self, active_indices):
+        """-> (what ``_ptr`` turns into the C argument, n_active) of an ``active_indices`` argument: ACTIVE_RESIDENT (with
+        the length ``active_set`` reported), an int n (validators 0 .. n - 1: nothing to upload) or an index array."""
+        if active_indices is ACTIVE_RESIDENT:
+            return _ACTIVE_RESIDENT_ARG, self._resident_active
+        if isinstance(active_indices, (int, np.integer)):
+            return None, int(active_indices)
+        act = np.ascontiguousarray(active_indices, dtype=np.uint32)
+        return act, act.size
+
+    def registry_set_epochs(self, activation_epoch, exit_epoch):
+        """Validator.activation_epoch / exit_epoch (pe:43-44) of the whole registry -> device memory."""
+        act = np.ascontiguousarray(activation_epoch, dtype=np.uint64)
+        ext = np.ascontiguousarray(exit_epoch, dtype=np.uint64)
+        assert act.size == ext.size, "one activation and one exit epoch per validator"
+        self._check(self._lib.pe_registry_set_epochs(self._h, act.size, _ptr(act if act.size else None, C.c_uint64),
+                                                     _ptr(ext if ext.size else None, C.c_uint64)))
+
+    def registry_get_epochs(self):
+        """-> (activation_epoch u64[n], exit_epoch u64[n], is_set); is_set False: the handle holds none."""
+        n = self.num_validators
+        act, ext, is_set = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64), C.c_int(0)
+        self._check(self._lib.pe_registry_get_epochs(self._h, n, _ptr(act), _ptr(ext), C.addressof(is_set)))
+        return act[:n], ext[:n], bool(is_set.value)
+
+    def active_set(self, epoch: int, want_indices: bool = False):
+        """get_active_validator_indices(state, epoch) over the resident epochs -> (n_active, total_balance, indices
+        uint32[n_active] | None); the list stays on the device for ACTIVE_RESIDENT.  total_balance is
+        get_total_active_balance's value for `epoch` over the working-state view."""
+        idx = np.empty(max(self.num_validators, 1), dtype=np.uint32) if want_indices else None
+        n_active, total = C.c_uint32(0), C.c_uint64(0)
+        self._check(self._lib.pe_active_set(self._h, int(epoch), C.addressof(n_active), C.addressof(total),
+                                            _ptr(idx, C.c_uint32)))
+        self._resident_active = int(n_active.value)
+        return int(n_active.value), int(total.value), (idx[:n_active.value] if want_indices else None)
+
+    def state_refresh_activity(self, current_epoch: int):
+        """PE_VAL_ACTIVE / PE_VAL_ACTIVE_PREV of the working-state view from the resident epochs."""
+        self._check(self._lib.pe_state_refresh_activity(self._h, int(current_epoch)))
+
     def compute_proposers(self, seeds, active_indices, rounds: int = 90,
                           max_effective_balance: int = 32 * 10**9, max_tries: int = 0):
         """compute_proposer_index (pe:604-618) on the GPU, once per seed, over the working-state view's effective
-        balances.  seeds: a sequence of 32-byte seeds (or a uint8 array of n x 32); active_indices: the index array, or an
-        int n meaning validators 0 .. n - 1.  -> (proposers uint32[n_seeds], tries uint32[n_seeds]); a proposer of
+        balances.  seeds: a sequence of 32-byte seeds (or a uint8 array of n x 32); active_indices: the index array, an
+        int n meaning validators 0 .. n - 1, or ACTIVE_RESIDENT.  -> (proposers uint32[n_seeds], tries uint32[n_seeds]); a proposer of
         0xFFFFFFFF (tries == max_tries) means none of the first max_tries candidates (0 = 4096) was accepted."""
         if isinstance(seeds, np.ndarray):
             sd = np.ascontiguousarray(seeds, dtype=np.uint8).reshape(-1)
@@ -718,11 +772,7 @@ class Engine:
             sd = np.frombuffer(b"".join(bytes(s) for s in seeds), dtype=np.uint8)
         assert sd.size % 32 == 0, "seeds are 32 bytes each"
         n_seeds = sd.size // 32
-        if isinstance(active_indices, (int, np.integer)):
-            act, n_act = None, int(active_indices)
-        else:
-            act = np.ascontiguousarray(active_indices, dtype=np.uint32)
-            n_act = act.size
+        act, n_act = self._active_arg(active_indices)
         prop = np.empty(max(n_seeds, 1), dtype=np.uint32)
         tries = np.empty(max(n_seeds, 1), dtype=np.uint32)
         self._check(self._lib.pe_compute_proposers(self._h, _ptr(sd if n_seeds else None, C.c_uint8), n_seeds,

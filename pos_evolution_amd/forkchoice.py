@@ -14,6 +14,11 @@ pos-evolution.md (``pe:N``):
     process_attestation(state, attestation)                 pe:722-754    (state bound with bind_state)
     compute_proposer_index(state, indices, seed)            pe:604-618    (state bound with bind_state)
     process_effective_balance_updates(state)                pe:122-133    (state bound with bind_state)
+    get_active_validator_indices(state, epoch)              named at pe:467 (state bound with bind_state)
+    get_committee_count_per_slot(state, epoch)              pe:461-468
+    compute_weak_subjectivity_period(state)                 pe:1257-1287
+    get_latest_weak_subjectivity_checkpoint_epoch(state)    pe:1225-1241
+    is_within_weak_subjectivity_period(...)                 pe:1298-1301  (the final comparison)
 
 Objects are duck-typed: anything exposing the pyspec's field names works
 (``attestation.data.beacon_block_root``, ``attestation.aggregation_bits``,
@@ -512,3 +517,113 @@ def process_effective_balance_updates(state, *, max_effective_balance: int = MAX
     if n_changed:
         for validator, value in zip(state.validators, new):
             validator.effective_balance = int(value)
+
+
+# ----------------------------------------------------------------------------- the active set and what is counted from it
+FAR_FUTURE_EPOCH = 2**64 - 1
+# the constants pe:461-468 and pe:1225-1287 name, mainnet values; pass `preset=` to replace any of them
+MAINNET_PRESET = {
+    "SLOTS_PER_EPOCH": 32, "MAX_COMMITTEES_PER_SLOT": 64, "TARGET_COMMITTEE_SIZE": 128,
+    "MIN_VALIDATOR_WITHDRAWABILITY_DELAY": 256, "MIN_PER_EPOCH_CHURN_LIMIT": 4, "CHURN_LIMIT_QUOTIENT": 65536,
+    "MAX_DEPOSITS": 16, "SAFETY_DECAY": 10, "ETH_TO_GWEI": 10**9, "MAX_EFFECTIVE_BALANCE": MAX_EFFECTIVE_BALANCE,
+}
+
+
+def _preset(preset: Optional[dict]) -> dict:
+    return MAINNET_PRESET if preset is None else {**MAINNET_PRESET, **preset}
+
+
+def is_active_validator(validator, epoch: int) -> bool:
+    """Named by the reference, not given: the standard activation_epoch <= epoch < exit_epoch."""
+    return int(validator.activation_epoch) <= int(epoch) < int(validator.exit_epoch)
+
+
+def _active_set(state, epoch: int, want_indices: bool = False):
+    """(n_active, total_active_balance, indices | None) of a bound state from the engine; the registry's epochs are
+    handed to it once per binding."""
+    b = _binding(state)
+    assert b is not None, "the active set: bind_state(engine, state, ...) first"
+    if not getattr(b, "epochs_resident", False):
+        n = len(state.validators)
+        b.engine.registry_set_epochs(
+            np.fromiter((int(v.activation_epoch) for v in state.validators), dtype=np.uint64, count=n),
+            np.fromiter((int(v.exit_epoch) for v in state.validators), dtype=np.uint64, count=n))
+        b.epochs_resident = True
+    return b.engine.active_set(int(epoch), want_indices)
+
+
+def _current_epoch(state, p: dict) -> int:
+    return int(state.slot) // p["SLOTS_PER_EPOCH"]
+
+
+def get_active_validator_indices(state, epoch: int) -> List[int]:
+    """Named at pe:467 / pe:1234 / pe:1267.  ``state`` must have been bound with ``bind_state``; the list is compacted on
+    the GPU and stays there as the engine's resident active list (``ACTIVE_RESIDENT``)."""
+    return [int(i) for i in _active_set(state, epoch, True)[2]]
+
+
+def get_committee_count_per_slot(state, epoch: int, *, n_active: Optional[int] = None, preset: Optional[dict] = None) -> int:
+    """pe:461-468.  ``n_active`` = len(get_active_validator_indices(state, epoch)) where the caller already holds it
+    (``state`` is then not read); else it is counted on the GPU for the bound ``state``."""
+    p = _preset(preset)
+    if n_active is None:
+        n_active = _active_set(state, epoch)[0]
+    return max(1, min(p["MAX_COMMITTEES_PER_SLOT"], int(n_active) // p["SLOTS_PER_EPOCH"] // p["TARGET_COMMITTEE_SIZE"]))
+
+
+def get_validator_churn_limit(state, *, n_active: Optional[int] = None, preset: Optional[dict] = None) -> int:
+    """Named at pe:1270, not given: the standard max(MIN_PER_EPOCH_CHURN_LIMIT, active validators // CHURN_LIMIT_QUOTIENT)."""
+    p = _preset(preset)
+    if n_active is None:
+        n_active = _active_set(state, _current_epoch(state, p))[0]
+    return max(p["MIN_PER_EPOCH_CHURN_LIMIT"], int(n_active) // p["CHURN_LIMIT_QUOTIENT"])
+
+
+def compute_weak_subjectivity_period(state, *, n_active: Optional[int] = None, total_active_balance: Optional[int] = None,
+                                     preset: Optional[dict] = None) -> int:
+    """pe:1257-1287.  The two registry-wide quantities -- the active validators of the current epoch and their total
+    balance -- come from one ``Engine.active_set`` call for the bound ``state``, or from the caller (both together;
+    ``state`` is then not read)."""
+    p = _preset(preset)
+    if n_active is None or total_active_balance is None:
+        assert n_active is None and total_active_balance is None, "pass both n_active and total_active_balance, or neither"
+        n_active, total_active_balance, _ = _active_set(state, _current_epoch(state, p))
+    count = int(n_active)
+    mean = int(total_active_balance) // count // p["ETH_TO_GWEI"]           # t: average active balance, ETH
+    cap = p["MAX_EFFECTIVE_BALANCE"] // p["ETH_TO_GWEI"]                    # T
+    churn = get_validator_churn_limit(state, n_active=count, preset=p)      # delta
+    top_ups = p["MAX_DEPOSITS"] * p["SLOTS_PER_EPOCH"]                      # Delta
+    decay = p["SAFETY_DECAY"]                                               # D
+    light, heavy = 200 + 3 * decay, 200 + 12 * decay
+    if cap * light < mean * heavy:
+        by_churn = count * (mean * heavy - cap * light) // (600 * churn * (2 * mean + cap))
+        by_top_ups = count * light // (600 * top_ups)
+        return p["MIN_VALIDATOR_WITHDRAWABILITY_DELAY"] + max(by_churn, by_top_ups)
+    return p["MIN_VALIDATOR_WITHDRAWABILITY_DELAY"] + 3 * count * decay * mean // (200 * top_ups * (cap - mean))
+
+
+def get_latest_weak_subjectivity_checkpoint_epoch(state, safety_decay: float = 0.1, *, n_active: Optional[int] = None,
+                                                  finalized_epoch: Optional[int] = None, preset: Optional[dict] = None):
+    """pe:1225-1241, its float arithmetic as written (the result is a float whenever the modulus is).  ``n_active`` and
+    ``finalized_epoch`` from the caller, or from the bound ``state``."""
+    p = _preset(preset)
+    if n_active is None:
+        n_active = _active_set(state, _current_epoch(state, p))[0]
+    if finalized_epoch is None:
+        finalized_epoch = int(state.finalized_checkpoint.epoch)
+    count = int(n_active)
+    churn_floor, quotient = p["MIN_PER_EPOCH_CHURN_LIMIT"], p["CHURN_LIMIT_QUOTIENT"]
+    # whole multiples of 256 epochs; true division, then floor division of a float: a float modulus, as in the reference
+    if count >= churn_floor * quotient:
+        extra = 256 * ((safety_decay * quotient / 2) // 256)
+    else:
+        extra = 256 * ((safety_decay * count / (2 * churn_floor)) // 256)
+    modulus = p["MIN_VALIDATOR_WITHDRAWABILITY_DELAY"] + extra
+    return finalized_epoch - (finalized_epoch % modulus)
+
+
+def is_within_weak_subjectivity_period(current_epoch: int, ws_state_epoch: int, ws_period: int) -> bool:
+    """The comparison pe:1298-1301 ends in: ws_period = compute_weak_subjectivity_period(ws_state), ws_state_epoch and
+    current_epoch = the epochs of ws_state.slot and of the store's current slot.  The two asserts before it (pe:1295-1296)
+    compare roots and are the caller's."""
+    return int(current_epoch) <= int(ws_state_epoch) + int(ws_period)
