@@ -702,9 +702,9 @@ int aggregate_impl(pe_engine* h, const pe_attestation* atts, uint32_t n, const u
         ProfScope ps(h, PE_KERNEL_BITS_UNION);
         // the kernels write their host-bound outputs straight into the pinned block (host-coherent, like the head
         // word): no device-to-host copy commands in a step
-        launch_bits_union(ms, st.dev<UnionGroup>(off_ug), ng, st.dev<uint32_t>(off_ub), st.dev<uint8_t>(off_arena),
-                          h->A().d_res_bits.as<uint32_t>(), h->A().d_res_info.as<uint32_t>(), ob.host<uint32_t>(off_obits),
-                          ob.host<uint32_t>(off_oinfo));
+        launch_bits_union(ms, UnionArgs{st.dev<UnionGroup>(off_ug), ng, st.dev<uint32_t>(off_ub), st.dev<uint8_t>(off_arena),
+                                        h->A().d_res_bits.as<uint32_t>(), h->A().d_res_info.as<uint32_t>(),
+                                        ob.host<uint32_t>(off_obits), ob.host<uint32_t>(off_oinfo), /*plan_dev=*/nullptr});
     }
     lap.mark("agg.3b_union");
     if (want_pk) {

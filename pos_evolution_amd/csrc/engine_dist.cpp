@@ -283,14 +283,15 @@ static int get_head_sharded_impl(pe_engine* h, uint8_t out_root[32], bool async)
         PE_TRY(ob.ensure());
     }
     uint64_t* buf = h->d_xchg.as<uint64_t>();
+    VotesArgs va = votes_args(h);  // ... into the exchange buffer: weights, then the totals
+    va.direct = buf;
+    va.totals = reinterpret_cast<VoteTotals*>(buf + nb);
     if (async && hold_eligible(h) && h->n_val) {
         // a streaming step: votes -> all-reduce -> tree go out with the NEXT aggregate's row kernels (engine_pair.cpp); every
         // rank holds and issues alike, so the all-reduce keeps its place in the order of this communicator's collectives
         PE_TRY(tree_args(h, buf, reinterpret_cast<const VoteTotals*>(buf + nb), /*clear_direct=*/1, ob.host<uint32_t>(off),
                          &h->held.tree));
-        h->held.votes = VotesArgs{h->d_vote_block.as<uint32_t>(), h->d_balance.as<uint64_t>(), h->d_flags.as<uint8_t>(),
-                                  h->n_val, h->cfg.filter_slashed, h->d_tpos.as<uint32_t>(), nb, buf,
-                                  reinterpret_cast<VoteTotals*>(buf + nb), expiry_slots_ptr(h), min_vote_slot(h)};
+        h->held.votes = va;
         h->held.between = [h, words]() -> int { return dist_all_reduce_u64(h, h->d_xchg.p, words, h->stream); };
         h->held.have_head = true;
         h->held.active = true;
@@ -310,10 +311,7 @@ static int get_head_sharded_impl(pe_engine* h, uint8_t out_root[32], bool async)
         ProfScope ps(h, PE_KERNEL_VOTES);
         // no memsets (k_tree zeroes the weights it read; the totals are plain per-workgroup stores), and inside a
         // pipeline the lean form that fits beside a running k_g1_accumulate
-        launch_votes(h->stream, h->d_vote_block.as<uint32_t>(), h->d_balance.as<uint64_t>(), h->d_flags.as<uint8_t>(),
-                     h->n_val, h->cfg.filter_slashed, h->d_tpos.as<uint32_t>(), nb, buf,
-                     reinterpret_cast<VoteTotals*>(buf + nb), 0, expiry_slots_ptr(h), min_vote_slot(h),
-                     /*lean=*/h->pipelining ? 1 : 0);
+        launch_votes(h->stream, va, /*lean=*/h->pipelining ? 1 : 0);
     }
     HIP_TRY(h, hipGetLastError());
     lap.mark("dist.votes_launch");

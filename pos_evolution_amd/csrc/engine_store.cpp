@@ -849,10 +849,7 @@ int pe_get_head(pe_engine* h, uint8_t out_root[32])
     }
     {
         ProfScope ps(h, PE_KERNEL_VOTES);
-        launch_votes(h->stream, h->d_vote_block.as<uint32_t>(), h->d_balance.as<uint64_t>(), h->d_flags.as<uint8_t>(),
-                     h->n_val, h->cfg.filter_slashed, h->d_tpos.as<uint32_t>(), (uint32_t)h->blocks.size(),
-                     h->d_direct.as<uint64_t>(), h->d_totals.as<VoteTotals>(), 0, expiry_slots_ptr(h),
-                     min_vote_slot(h), /*lean=*/h->pipelining ? 1 : 0);
+        launch_votes(h->stream, votes_args(h), /*lean=*/h->pipelining ? 1 : 0);
     }
     lap.mark("head.1_launch_votes");
     uint32_t head;
@@ -944,11 +941,13 @@ static int votes_partial_impl(pe_engine* h, void* dev_buf_u64, uint32_t n_blocks
     int rc = refresh_tree(h);
     if (rc) return rc;
     uint64_t* buf = static_cast<uint64_t*>(dev_buf_u64);
+    VotesArgs va = votes_args(h);  // n_blocks == the store's block count (checked above)
+    va.direct = buf;
+    va.totals = reinterpret_cast<VoteTotals*>(buf + n_blocks);
     {
         ProfScope ps(h, PE_KERNEL_VOTES);
-        launch_votes(h->stream, h->d_vote_block.as<uint32_t>(), h->d_balance.as<uint64_t>(), h->d_flags.as<uint8_t>(),
-                     h->n_val, h->cfg.filter_slashed, h->d_tpos.as<uint32_t>(), n_blocks, buf,
-                     reinterpret_cast<VoteTotals*>(buf + n_blocks), 1, expiry_slots_ptr(h), min_vote_slot(h));
+        votes_clear_exchange(h->stream, va.direct, n_blocks, va.totals);  // the caller's buffer: nothing keeps it zeroed
+        launch_votes(h->stream, va, /*lean=*/0);
     }
     HIP_TRY(h, hipGetLastError());
     return PE_OK;

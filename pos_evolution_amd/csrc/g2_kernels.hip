@@ -648,7 +648,7 @@ k_g2_count_bad(const int32_t* __restrict__ status, const uint32_t* __restrict__ 
     uint32_t bad = 0;
     for (uint32_t j = lane; j < cnt; j += 64) bad += status[index ? index[first + j] : first + j] != 0;
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) bad += __shfl_xor(bad, off, 64);
+    for (int off = 32; off >= 1; off >>= 1) bad += __shfl_xor(bad, off, 64);  // (not wave_sum: the kernel's code differs)
     if (lane == 0) out_bad[g] = bad;
 }
 __global__ void __launch_bounds__(256)

@@ -88,17 +88,7 @@ struct VoteTotals {            // one per K_votes workgroup (VOTES_MAX_WG slots)
     unsigned long long total_active_balance;
     unsigned long long num_active;
 };
-// direct[pos] += effective_balance of every counted validator voting for the block at pos.
-void launch_votes(hipStream_t s, const uint32_t* vote_block, const uint64_t* eff_balance, const uint8_t* flags,
-                  uint64_t n_val, uint32_t filter_slashed, const uint32_t* pos_of_idx,
-                  uint32_t n_blocks, uint64_t* direct, VoteTotals* totals, int zero_first,
-                  const uint32_t* vote_slot = nullptr, uint32_t min_vote_slot = 0, int lean = 0);
-// Subtree sums (prefix scan over pre-order), viability, best child, pointer-jumping descent.
-void launch_tree(hipStream_t s, const TreeDev& tree, uint64_t* direct, const VoteTotals* totals,
-                 uint64_t totals_override_balance, uint64_t totals_override_num, int use_override,
-                 uint32_t justified_pos, uint32_t boost_pos, uint64_t slots_per_epoch, uint64_t boost_percent,
-                 uint64_t balance_increment, uint64_t* weights_by_idx, uint32_t* head_idx, int clear_direct,
-                 int lean = 0);
+// (k_votes and k_tree are launched over VotesArgs / TreeArgs: see "argument blocks" below)
 
 // One resolved attestation (device row).
 struct AttRow {
@@ -131,21 +121,14 @@ void launch_participation(hipStream_t s, const AttRow* rows, uint32_t n_rows, co
                           uint64_t base_reward_per_increment, uint32_t* part_cur_words,
                           uint32_t* part_prev_words, uint64_t* numerators, const uint32_t* numerator_slot,
                           const uint32_t* gates = nullptr);
-// aggregation_bits = OR over the group's member attestations; count = popcount (wave reduce).
+// aggregation_bits = OR over the group's member attestations; count = popcount (wave reduce): k_bits_union, launched
+// over UnionArgs (see "argument blocks" below).
 struct UnionGroup {
     uint32_t list_start;   // into att_bytes[]: BYTE offsets of the member attestations' bits in the raw arena
     uint32_t n_atts;
     uint32_t n_bits;       // len(aggregation_bits): bits past it in the last word are masked off
     uint32_t out_word;     // word offset of the output bitfield
 };
-// bit_arena: the caller's packed bit arena as uploaded (any byte alignment per member; readable 8 bytes past the last
-// member).  out_info[2g] = popcount of the union, out_info[2g + 1] = sum of the members' popcounts minus that: non-zero
-// <=> members of the group overlap (their signatures would be counted twice, validator guide A.8).
-// host_arena / host_info (nullable): the same two outputs written a second time straight into host-coherent pinned
-// memory, so that no device-to-host copy command has to follow the kernel.
-void launch_bits_union(hipStream_t s, const UnionGroup* groups, uint32_t n_groups, const uint32_t* att_bytes,
-                       const uint8_t* bit_arena, uint32_t* out_arena, uint32_t* out_info,
-                       uint32_t* host_arena = nullptr, uint32_t* host_info = nullptr, const AttPlan* plan_dev = nullptr);
 
 // ---- attestation rows resident in device memory (att_kernels.hip; host side: engine_resident.cpp) ----------------
 // pe_aggregate / pe_on_attestation_batch / pe_process_attestation_batch with the rows handed over in device (or
@@ -211,13 +194,6 @@ struct StateCtxDev {              // the slice of BeaconState process_attestatio
     uint32_t head_blk[64];        // get_block_root_at_slot(state, slot - spe + j)
     unsigned long long base_reward_per_increment;
 };
-// tab / cnt_tab: the grouping table (slot -> first row of the class, ATT_EMPTY when free) and the class sizes; both are
-// left clean by k_att_members.  arena_pad32: 32 bytes behind the copied bit arena, zeroed here.
-void launch_att_ingest(hipStream_t s, const void* rows, uint32_t n, uint32_t* tab, uint32_t* cnt_tab, uint32_t tab_mask,
-                       uint32_t* slot_of, uint64_t arena_len, AttPlan* plan, void* arena_pad32,
-                       const uint32_t* n_dev = nullptr,  // n_dev: the row count lives on the device, n bounds it
-                       const void* arena_src = nullptr, void* arena_dst = nullptr);  // arena_src (device memory, 16-byte
-                                                          // aligned): the launch copies arena_len bytes to arena_dst itself
 // k_att_plan runs one lane per input row over as many 256-lane workgroups as the batch needs.  What its workgroups tell each
 // other travels through two small records in device memory, both all-zero between launches (the last workgroup to finish
 // clears them):
@@ -255,19 +231,9 @@ void launch_att_pack(hipStream_t s, const void* rows, const AttGroup* grp, const
 void launch_att_unpack(hipStream_t s, const uint32_t* recv, uint32_t world, uint32_t slots, uint32_t wps, void* out_rows,
                        uint32_t* out_bits, uint32_t* n_dev, uint32_t* err_host);
 // n_bound: upper bound of the groups (sizes the grid); cap: entries of the caller's status / count arrays
-void launch_att_validate_fc(hipStream_t s, const void* rows, const AttGroup* grp, const AttPlan* plan, uint32_t n_bound,
-                            uint32_t cap, BlockTableDev bt, FcCtx fc, const uint32_t* union_info, AttRow* out_rows,
-                            int32_t* status_dev, int32_t* status_host, uint32_t* count_host, uint32_t* err_host);
 void launch_att_validate_state(hipStream_t s, const void* rows, const AttGroup* grp, const AttPlan* plan, uint32_t n_bound,
                                uint32_t cap, BlockTableDev bt, const StateCtxDev& st, const uint32_t* union_info,
                                AttRow* out_rows, int32_t* status_dev, int32_t* status_host, uint32_t* err_host);
-// validator-major LMD update over both candidate tables in one launch (each lane walks its validator's committee of
-// the current-epoch table, then of the previous-epoch one); the per-committee row
-// lists are unordered (built with atomics), the batch-order rule is applied by comparing AttRow::order.
-void launch_lmd_vm_tables(hipStream_t s, const AttRow* rows, TablesDev tables, uint32_t* const crow_start[2],
-                          uint32_t* const crow_list[2], const AttPlan* plan, const uint32_t* bit_arena,
-                          const uint8_t* flags, uint64_t n_val, uint64_t* vote_key, uint32_t* vote_block,
-                          uint32_t* vote_slot, const uint32_t* gates);
 // process_attestation's flag loop, one wave per committee: the committee's rows run in batch order inside the wave
 // (committees of a partition table touch disjoint validators, so waves are independent).
 void launch_participation_tables(hipStream_t s, const AttRow* rows, TablesDev tables, uint32_t* const crow_start[2],
@@ -276,22 +242,35 @@ void launch_participation_tables(hipStream_t s, const AttRow* rows, TablesDev ta
                                  uint32_t* part_cur_words, uint32_t* part_prev_words, uint64_t* numerators,
                                  const uint32_t* gates, uint32_t cap);  // cap: slots of numerators[]; more groups = no-op
 
-// ---- paired launches (pair_kernels.hip) --------------------------------------------------------------------------
+// ---- argument blocks: the launch interface of the row and fork-choice kernels ------------------------------------------
+// Each of these kernels takes ONE struct by value, and the struct is what its launcher takes: the engine fills a block
+// (votes_args, tree_args, engine_resident.cpp) and either launches it now or holds it back (engine_pair.cpp).
 // A streaming caller's engine stream carries two independent chains: the fork-choice chain of step N (validate ->
 // LMD -> votes -> tree) and the row chain of step N + 1 (ingest -> plan -> members -> union).  Side by side on two
 // streams the command processor's queue interleaving costs more than the overlap gives; launched as ONE
-// kernel per pair -- block ranges of one grid, each range running the body of its own kernel -- they overlap without a
-// second queue.  The argument blocks below are the stand-alone kernels' parameters, so that a held-back launch can be
-// issued either way (engine_pair.cpp).
+// kernel per pair (pair_kernels.hip) -- block ranges of one grid, each range running the body of its own kernel over its
+// own block -- they overlap without a second queue.
 struct IngestArgs {
-    const void* rows; uint32_t n; uint32_t* tab; uint32_t* cnt_tab; uint32_t tab_mask; uint32_t* slot_of;
-    uint64_t arena_len; AttPlan* plan; void* arena_pad32; const uint32_t* n_dev; const void* arena_src; void* arena_dst;
+    const void* rows; uint32_t n;
+    uint32_t* tab; uint32_t* cnt_tab;  // the grouping table (slot -> first row of the class, ATT_EMPTY when free) and the
+    uint32_t tab_mask;                 // class sizes; both are left clean by k_att_members
+    uint32_t* slot_of;
+    uint64_t arena_len; AttPlan* plan;
+    void* arena_pad32;                 // 32 bytes behind the copied bit arena, zeroed here
+    const uint32_t* n_dev;             // nullable: the row count lives on the device, n bounds it
+    const void* arena_src; void* arena_dst;  // arena_src (nullable; device memory, 16-byte aligned): the launch copies
+                                             // arena_len bytes to arena_dst itself
 };
 struct ValidateFcArgs {
-    const void* rows; const AttGroup* grp; const AttPlan* plan; uint32_t n_bound, cap; BlockTableDev bt; FcCtx fc;
+    const void* rows; const AttGroup* grp; const AttPlan* plan;
+    uint32_t n_bound, cap;  // upper bound of the groups (sizes the grid); entries of the caller's status / count arrays
+    BlockTableDev bt; FcCtx fc;
     const uint32_t* union_info; AttRow* out_rows; int32_t* status_dev; int32_t* status_host; uint32_t* count_host;
     uint32_t* err_host;
 };
+// validator-major LMD update over both candidate tables in one launch (each lane walks its validator's committee of the
+// current-epoch table, then of the previous-epoch one); the per-committee row lists are unordered (built with atomics),
+// the batch-order rule is applied by comparing AttRow::order.
 struct LmdVmArgs {
     const AttRow* rows; TablesDev tables; const uint32_t* crow_start[2]; const uint32_t* crow_list[2];
     const AttPlan* plan; const uint32_t* bit_arena; const uint8_t* flags; uint64_t n_val; uint64_t* vote_key;
@@ -303,26 +282,37 @@ struct MembersArgs {
     uint32_t* host_group_of; void* host_out_rows; const uint32_t* n_dev;
     G1Group* g1; uint32_t* crow_cursor[2]; uint32_t* crow_list[2];  // written per group by the lane of its first row
 };
+// direct[pos] += effective_balance of every counted validator voting for the block at pos.
 struct VotesArgs {
     const uint32_t* vote_block; const uint64_t* eff_balance; const uint8_t* flags; uint64_t n_val;
     uint32_t filter_slashed; const uint32_t* pos_of_idx; uint32_t n_blocks; uint64_t* direct; VoteTotals* totals;
-    const uint32_t* vote_slot; uint32_t min_vote_slot;
+    const uint32_t* vote_slot; uint32_t min_vote_slot;  // vote-expiry variant: nullptr / 0 without it
 };
 struct UnionArgs {
-    const UnionGroup* groups; uint32_t n_groups; const uint32_t* att_bytes; const uint8_t* bit_arena;
-    uint32_t* out_arena; uint32_t* out_info; uint32_t* host_arena; uint32_t* host_info; const AttPlan* plan_dev;
+    const UnionGroup* groups; uint32_t n_groups; const uint32_t* att_bytes;
+    const uint8_t* bit_arena;  // the caller's packed bit arena as uploaded (any byte alignment per member; readable 8 bytes
+                               // past the last member)
+    uint32_t* out_arena;
+    uint32_t* out_info;        // [2g] = popcount of the union, [2g + 1] = sum of the members' popcounts minus that: non-zero
+                               // <=> members of the group overlap (their signatures would be counted twice, A.8)
+    uint32_t* host_arena; uint32_t* host_info;  // nullable: the same two outputs written a second time straight into
+                               // host-coherent pinned memory, so that no device-to-host copy command has to follow the kernel
+    const AttPlan* plan_dev;   // nullable: the group count lives on the device, n_groups bounds it
 };
+// Subtree sums (prefix scan over pre-order), viability, best child, the descent to the head.
 struct TreeArgs {
     TreeDev tree; uint64_t* direct; const VoteTotals* totals; uint64_t ov_balance, ov_num; int use_override;
     uint32_t justified_pos, boost_pos; uint64_t slots_per_epoch, boost_percent, balance_increment;
     uint64_t* weights_by_idx; uint32_t* head_idx; int clear_direct;
 };
-// the stand-alone launches over the same argument blocks (lean: the shapes that fit beside a running accumulation)
+// the stand-alone launches (lean: the shapes that fit beside a running accumulation)
 void launch_att_ingest(hipStream_t s, const IngestArgs& a);
 void launch_att_validate_fc(hipStream_t s, const ValidateFcArgs& a);
 void launch_lmd_vm_tables(hipStream_t s, const LmdVmArgs& a);
 void launch_att_members(hipStream_t s, const MembersArgs& a);
 void launch_votes(hipStream_t s, const VotesArgs& a, int lean);
+// zeroes a caller-owned exchange buffer in front of launch_votes (the engine's own buffers are left zeroed by k_tree)
+void votes_clear_exchange(hipStream_t s, uint64_t* direct, uint32_t n_blocks, VoteTotals* totals);
 void launch_bits_union(hipStream_t s, const UnionArgs& a);
 void launch_tree(hipStream_t s, const TreeArgs& a, int lean);
 // ... and pairwise.  Each returns false when the pair has no common shape (the caller then launches the two alone).

@@ -14,13 +14,11 @@
 //   k_pair_members_votes     k_att_members(N+1)  |  k_votes<lean>(N)          the votes' fat workgroups first, 512 lanes
 //   k_pair_union_tree        k_bits_union(N+1)   |  k_tree<lean>(N)           block 0 = the tree's one workgroup
 //
-// The bodies are the stand-alone kernels' own code (att_kernels.hip / fc_kernels.hip compiled here with
-// POSEVO_BODIES_ONLY: device functions that take their block index as an argument), so results cannot differ; which form
-// runs is the engine's choice per step (engine_pair.cpp).  Integer / byte work, latency-bound: no MFMA.
-#define POSEVO_BODIES_ONLY 1
-#include "att_kernels.hip"
-#include "fc_kernels.hip"
-#undef POSEVO_BODIES_ONLY
+// The bodies are the stand-alone kernels' own code (att_bodies.inc / fc_bodies.inc: device functions that take their block
+// index as an argument, included here and by att_kernels.hip / fc_kernels.hip), so results cannot differ; which form runs is
+// the engine's choice per step (engine_pair.cpp).  Integer / byte work, latency-bound: no MFMA.
+#include "att_bodies.inc"
+#include "fc_bodies.inc"
 
 namespace posevo {
 
@@ -43,7 +41,7 @@ bool launch_pair_ingest_validate(hipStream_t s, const IngestArgs& ia, const Vali
 
 // ------------------------------------------------------------------ plan(N+1) | LMD(N)
 // 256-lane blocks both: the plan's workgroups first (a workgroup of the plan waits for the records of LOWER block indices
-// only, att_kernels.hip), then one lane per validator.  No LDS to speak of: the LMD blocks queue for nothing (round 5's
+// only, att_bodies.inc), then one lane per validator.  No LDS to speak of: the LMD blocks queue for nothing (round 5's
 // one-workgroup plan made each of them reserve its 70 KB).
 __global__ void __launch_bounds__(PLAN_WG) __attribute__((amdgpu_waves_per_eu(8, 8)))
 k_pair_plan_lmd(const AttPlanArgs pa, const LmdVmArgs la, const uint32_t nb_plan)

@@ -14,6 +14,7 @@
 // Integer/hash work, no MFMA.  SURVEY.md 8(f) rank 1.
 // Further down: proposer sampling (k_proposer_sample) and the active set the shuffles start from (k_active_compact).
 #include "kernels.h"
+#include "wave64.h"
 
 namespace posevo {
 
@@ -394,12 +395,6 @@ __device__ __forceinline__ bool is_active_validator(unsigned long long activatio
 {
     return activation_epoch <= epoch && epoch < exit_epoch;
 }
-__device__ __forceinline__ unsigned long long active_wave_sum_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 template <bool SCATTER>
 __global__ void __launch_bounds__(ACTIVE_WG)
@@ -415,7 +410,7 @@ k_active_compact(const unsigned long long* __restrict__ activation_epoch, const 
     const bool active = v < n_val && is_active_validator(activation_epoch[v], exit_epoch[v], epoch);
     const unsigned long long ballot = __ballot(active);
     if constexpr (!SCATTER) {
-        const unsigned long long balance = active_wave_sum_u64(active ? eff_balance[v] : 0ull);
+        const unsigned long long balance = wave_sum(active ? eff_balance[v] : 0ull);
         if ((threadIdx.x & 63) == 0) {
             wave_count[wave] = (uint32_t)__builtin_popcountll(ballot);
             wave_balance[wave] = balance;
@@ -456,7 +451,7 @@ k_active_scan(const uint32_t* __restrict__ wg_count, const unsigned long long* _
         const uint32_t i = tile + threadIdx.x;
         const uint32_t count = i < n_wg ? wg_count[i] : 0u;
         if (i < n_wg) balance += wg_balance[i];
-        uint32_t inclusive = count;  // prefix sum over the wave
+        uint32_t inclusive = count;  // prefix sum over the wave (not wave_incl_scan: the kernel's code differs)
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
             const uint32_t up = __shfl_up(inclusive, off, 64);
@@ -475,7 +470,7 @@ k_active_scan(const uint32_t* __restrict__ wg_count, const unsigned long long* _
         carry += all;
         __syncthreads();  // wave_total is rewritten by the next tile
     }
-    balance = active_wave_sum_u64(balance);
+    balance = wave_sum(balance);
     if (lane == 0) wave_balance[wave] = balance;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -126,7 +126,7 @@ def test_rows_in_shuffled_order_keep_first_appearance_order(engine_factory):
                                                          (9000, 64, 37, True)])        # 2368 rows: a ragged last workgroup
 def test_the_plan_over_many_workgroups_equals_the_host_grouping(engine_factory, n_val, n_comm, parts, shuffle):
     """k_att_plan runs one lane per row over ceil(n / 256) workgroups that hand their running sums to each other through
-    look-back records (att_kernels.hip): group ids, union offsets, member lists, committee row lists and the G1 plan of a
+    look-back records (att_bodies.inc): group ids, union offsets, member lists, committee row lists and the G1 plan of a
     batch that spans many workgroups -- rows of a group far apart -- must be what the host path derives; twice on the same
     engine (the records have to come back clean)."""
     wa = _world(engine_factory, n_val, n_comm, seed=21, density=0.7, parts=parts)

@@ -116,6 +116,62 @@ def test_two_shards_on_one_gpu(engine_factory):
     assert (local[0] <= ref_w).all() and (local[1] <= ref_w).all()
 
 
+def test_votes_partial_into_a_dirty_exchange_buffer(engine_factory):
+    """pe_votes_partial adds into a buffer the CALLER owns and nobody keeps zeroed: the call itself has to clear the weights
+    and the per-workgroup totals before k_votes runs.  The buffer starts as 0xFF bytes and is dirty again for the second
+    call (head_from_weights leaves the summed weights in it).
+        0 - 1 - 2          heavy: validators 0..38, 1989 ETH
+            1 - 3 - 4      light: validators 39..62, 1980 ETH, + the proposer boost (40 % of 2 x 63.5 ETH) = the head
+    so the head hangs on the totals as much as on the weights."""
+    import torch
+    V, ETH = 64, 10**9
+    tree = synth.Tree(synth.make_roots(5, b"dirty"), np.array([H.NONE32, 0, 1, 1, 3], dtype=np.uint32),
+                      np.array([0, 1, 2, 3, 4], dtype=np.uint64))
+    bal = ((32 + np.arange(V)) * ETH).astype(np.uint64)
+    flags = np.full(V, 0x01, dtype=np.uint8)
+    comm = synth.random_committees(V, 32, 31)
+    vote = np.full(V, H.NONE32, dtype=np.uint32)
+    vote[:39], vote[39:63] = 2, 4
+    e = engine_factory()
+    H.load_tree(e, tree)
+    e.set_validators(bal, flags)
+    assert np.array_equal(H.install_votes(e, tree, comm, vote), vote)
+    e.set_proposer_boost(tree.roots[4].tobytes())
+
+    buf = torch.full((5 + _abi.PE_EXCHANGE_EXTRA,), -1, dtype=torch.int64, device=torch.device("cuda", 0))  # 0xFF bytes
+
+    def check(want_head):
+        ref_head, ref_w = e.get_head(), e.get_weights()
+        assert ref_head == tree.roots[want_head].tobytes()
+        e.votes_partial(buf.data_ptr())
+        assert e.head_from_weights(buf.data_ptr()) == ref_head
+        assert np.array_equal(e.last_weights(), ref_w)
+        return ref_w
+
+    w = check(4)
+    assert w[2] == 1989 * ETH and 1980 * ETH < w[4] < w[2] + 50 * ETH   # the boost decides
+    torch.cuda.synchronize()
+    assert buf.cpu().numpy().any()   # dirty again
+    # validator 0 (32 ETH) moves from the heavy branch to the light one with a vote of the next epoch
+    E = int(tree.slot.max()) // 32 + 2
+    c = int(np.searchsorted(comm.offsets, int(np.where(comm.members == 0)[0][0]), side="right") - 1)
+    mem = comm.members[comm.offsets[c]:comm.offsets[c + 1]]
+    a = np.zeros(1, dtype=synth.ATT_DTYPE)
+    a["slot"], a["index"] = E * 32 + c, 0   # 32 committees: one per slot
+    a["beacon_block_root"] = a["target_root"] = tree.roots[4]
+    a["target_epoch"] = E
+    a["source_root"] = tree.roots[0]
+    a["flags"] = 3
+    arena, offs, nb = synth.pack_bit_rows([mem == 0])
+    a["bits_offset"], a["n_bits"] = offs, nb
+    e.set_committees(E, comm.offsets, comm.members)
+    e.on_tick((E + 1) * 32 * 12)
+    status, _, _ = e.on_attestation_batch(packed=(a, arena))
+    assert not status.any()
+    w2 = check(4)
+    assert w2[2] == w[2] - 32 * ETH and w2[4] == w[4] + 32 * ETH
+
+
 def test_sharded_forkchoice_world_size_one(engine_factory):
     import torch
     import torch.distributed as dist
