@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define PE_ABI_VERSION 9
+#define PE_ABI_VERSION 10
 
 typedef struct pe_engine pe_engine;
 
@@ -320,7 +320,7 @@ int pe_get_head_async(pe_engine* h, uint8_t out_root[32]);
  * (index 0 = anchor).  out must hold pe_num_blocks(h) entries. */
 int pe_get_weights(pe_engine* h, uint64_t* out_weights, uint32_t n);
 /* The per-block weights the LAST head computation left behind (pe_get_head, or pe_head_from_weights on a reduced
- * multi-GPU buffer), without recomputing them. */
+ * multi-GPU buffer), without recomputing them.  pe_prune drops them: PE_ERR_STATE until the next head computation. */
 int pe_get_last_weights(pe_engine* h, uint64_t* out_weights, uint32_t n);
 
 /* on_attestation (pe:963-979, pe:1423-1428) x n, applied AS IF sequentially in
@@ -531,12 +531,48 @@ uint64_t pe_num_validators(const pe_engine* h);
 int pe_block_root_at(const pe_engine* h, uint32_t block_index, uint8_t out_root[32]);
 int pe_block_index_of(const pe_engine* h, const uint8_t root[32], uint32_t* out_index);
 /* store.latest_messages: epoch and block index per validator; block index
- * 0xFFFFFFFF = no message. */
+ * 0xFFFFFFFF = no message (epoch 0), PE_VOTE_PRUNED = a message whose block pe_prune removed (its epoch is kept). */
 int pe_get_latest_messages(pe_engine* h, uint64_t* out_epoch, uint32_t* out_block_index, uint64_t n);
+
+/* ---- pruning at finalization ------------------------------------------------------------------------------------
+ * The block table holds at most 8192 LIVE blocks (the tree kernel keeps it in LDS); pe_prune re-roots it at
+ * store.finalized_checkpoint.root.  Kept: exactly the finalized root and its descendants, in their relative insertion
+ * order (still parent-first), so the root becomes block 0 with parent 0xFFFFFFFF; its proper ancestors and every side
+ * branch go.  on_block refuses a block that does not descend from the finalized root (pe:998-1005), get_head starts at
+ * the justified root (pe:1106), which descends from it, and a block's weight is the sum over its own subtree (pe:322):
+ * no removed block can be a head, a child in the descent or a parent of a new block, nor add to the weight of one that
+ * can, so the call is unobservable to pe_get_head.
+ *   Latest messages stay on the device and follow the re-indexing there (k_votes_remap).  A message on a removed block
+ * keeps its epoch -- update_latest_messages compares against it (pe:1440): a later vote of an equal or lower epoch is
+ * still refused -- and its block index becomes PE_VOTE_PRUNED: it weighs on nothing, which is what it weighs on among
+ * the kept blocks in the reference.  pe_get_latest_messages reports (epoch, PE_VOTE_PRUNED); pe_set_latest_messages
+ * accepts that pair, so export / import round-trip a pruned store.
+ *   Synchronous, like pe_active_set: it first issues held-back launches and completes every open pipeline.  Everything
+ * that can fail is checked before anything changes: store not initialised -> PE_ERR_STATE; finalized root not in the
+ * table -> PE_ERR_UNKNOWN_ROOT; justified root (or a non-zero best_justified root that is in the table) outside the kept
+ * subtree -> PE_ERR_STATE; a handle with pe_dist_init* active -> PE_ERR_STATE.  With the finalized root already at block 0
+ * the call changes nothing and launches nothing (blocks_before == blocks_after, zero vote counts).  proposer_boost_root
+ * stays as it is (a boost root that is not in the table boosts nothing); the weights of pe_get_last_weights are dropped;
+ * the slasher's history holds no block indices and is not touched.  The caller decides when: typically after a
+ * pe_on_block that raised finalized_checkpoint.
+ *   DEVIATION (the reference's Store never forgets a block): the pruned store equals the reference store with those
+ * blocks deleted from store.blocks, and equals the unpruned reference on every call sequence in which no later call names
+ * a deleted block.  An attestation that names one fails the reference's own assert "beacon_block_root / target.root in
+ * store.blocks" (A.4) with PE_ATT_UNKNOWN_BEACON_BLOCK_ROOT / PE_ATT_UNKNOWN_TARGET_ROOT; a block whose parent was
+ * removed fails pe:990 (PE_ERR_UNKNOWN_PARENT) where the unpruned reference would fail at pe:1000.  Both are rejections
+ * that leave the store untouched. */
+#define PE_VOTE_PRUNED 0xFFFFFFFEu   /* latest message whose block was pruned */
+typedef struct pe_prune_stats {
+    uint32_t blocks_before, blocks_after;
+    uint64_t votes_remapped;   /* latest messages whose block was kept under another index */
+    uint64_t votes_orphaned;   /* latest messages whose block was removed by this call */
+} pe_prune_stats;
+int pe_prune(pe_engine* h, pe_prune_stats* out /* may be NULL */);
 /* ---- checkpoint / resume: the store is a handful of flat arrays -------------------------------
  * Export: pe_get_store_scalars, pe_get_block x pe_num_blocks (insertion order: parents first), pe_get_validator_flags
  * (incl. PE_VAL_EQUIVOCATING), pe_get_latest_messages (+ _slots under the vote-expiry variant), pe_participation_get.
- * Import into a fresh handle: pe_store_init(genesis_time, block 0) -> pe_add_block in order -> pe_set_validators
+ * Import into a fresh handle: pe_store_init(genesis_time, block 0) -> pe_set_block_checkpoints(0, ...) (after a pe_prune
+ * block 0 is an ordinary block whose post-state checkpoints decide filter_block_tree's leaf test) -> pe_add_block in order -> pe_set_validators
  * (balances, flags without the equivocating bit, pubkeys) -> pe_mark_equivocating -> pe_set_latest_messages ->
  * pe_on_tick(time) -> pe_set_checkpoints / pe_set_best_justified / pe_set_proposer_boost -> pe_participation_set.
  * pos_evolution_amd.Engine.export_state / import_state do exactly this. */
@@ -545,7 +581,13 @@ int pe_get_block(const pe_engine* h, uint32_t block_index, uint8_t root[32], uin
                  uint64_t* post_finalized_epoch, uint8_t post_finalized_root[32]);
 int pe_get_validator_flags(const pe_engine* h, uint8_t* out_flags, uint64_t n);
 int pe_get_latest_message_slots(pe_engine* h, uint32_t* out_slot, uint64_t n);
-/* block_index 0xFFFFFFFF = no message; slot may be NULL (only read under the vote-expiry variant). */
+/* The post-state checkpoints of a block already in the table (block_states[root].current_justified_checkpoint /
+ * .finalized_checkpoint), as pe_get_block reports them: pe_store_init gives block 0 the anchor checkpoint for both. */
+int pe_set_block_checkpoints(pe_engine* h, uint32_t block_index, uint64_t post_justified_epoch,
+                             const uint8_t post_justified_root[32], uint64_t post_finalized_epoch,
+                             const uint8_t post_finalized_root[32]);
+/* block_index 0xFFFFFFFF = no message (the epoch is ignored); PE_VOTE_PRUNED = a message of that epoch on a pruned block;
+ * slot may be NULL (only read under the vote-expiry variant). */
 int pe_set_latest_messages(pe_engine* h, uint64_t n, const uint64_t* epoch, const uint32_t* block_index,
                            const uint32_t* slot);
 int pe_set_best_justified(pe_engine* h, uint64_t epoch, const uint8_t root[32]);

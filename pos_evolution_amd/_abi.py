@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("POSEVO_LIB_PATH") or os.path.join(_HERE, "libposevo.s
 
 PE_OK = 0
 PE_ERR_NO_DEVICE = -2
+PE_ERR_UNKNOWN_PARENT = -4
+PE_ERR_UNKNOWN_ROOT = -9
 PE_ERR_CAPACITY = -10
 PE_ERR_STATE = -14
 PE_ERR_TIMEOUT = -15
@@ -44,6 +46,7 @@ ATT_STATUS_NAMES = {
     32: "slasher: target epoch in the future", 33: "slasher: target epoch left the window",
     34: "slasher: data table of the epoch is full",
 }
+PE_ATT_UNKNOWN_TARGET_ROOT, PE_ATT_UNKNOWN_BEACON_BLOCK_ROOT = 3, 4
 PE_SLASH_FUTURE_TARGET, PE_SLASH_TOO_OLD, PE_SLASH_TABLE_FULL = 32, 33, 34
 PE_SLASH_APPLY = 1
 PE_SLASH_DOUBLE, PE_SLASH_SURROUND = 1, 2
@@ -79,6 +82,12 @@ class pe_state_ctx(C.Structure):
         ("previous_justified_epoch", C.c_uint64), ("previous_justified_root", C.c_uint8 * 32),
         ("base_reward_per_increment", C.c_uint64),
     ]
+
+
+class pe_prune_stats(C.Structure):
+    """struct pe_prune_stats (include/posevo.h): what one pe_prune did."""
+    _fields_ = [("blocks_before", C.c_uint32), ("blocks_after", C.c_uint32), ("votes_remapped", C.c_uint64),
+                ("votes_orphaned", C.c_uint64)]
 
 
 _P = C.POINTER
@@ -153,6 +162,8 @@ SIGNATURES = {
     "pe_active_set": (C.c_int, [_H, C.c_uint64, C.c_void_p, C.c_void_p, _u32p]),
     "pe_state_refresh_activity": (C.c_int, [_H, C.c_uint64]),
     "pe_g1_sum": (C.c_int, [_H, _u8p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u8p]),
+    "pe_prune": (C.c_int, [_H, C.c_void_p]),
+    "pe_set_block_checkpoints": (C.c_int, [_H, C.c_uint32, C.c_uint64, _u8p, C.c_uint64, _u8p]),
     "pe_get_block": (C.c_int, [_H, C.c_uint32, _u8p, _u32p, _u64p, _u64p, _u8p, _u64p, _u8p]),
     "pe_get_validator_flags": (C.c_int, [_H, _u8p, C.c_uint64]),
     "pe_get_latest_message_slots": (C.c_int, [_H, _u32p, C.c_uint64]),
@@ -215,6 +226,7 @@ PE_ROWS_RESIDENT = 1  # include/posevo.h: "every group of the last pe_aggregate 
 PE_BITS_RESIDENT = 1  # the address include/posevo.h defines as "bits are where the last pe_aggregate left them"
 PE_ACTIVE_RESIDENT = 1  # ... and as "the active list is where the last pe_active_set left it"
 PE_ATT_FLAG_OVERLAPPING_BITS = 0x4
+PE_VOTE_PRUNED = 0xFFFFFFFE  # block index of a latest message whose block pe_prune removed (its epoch is kept)
 
 _lib = None
 

@@ -240,6 +240,7 @@ struct pe_engine {
     std::vector<uint32_t> h_pos_of_idx;
     PinBuf h_head;  // 64 B of host-coherent pinned memory the tree kernel writes the head index into
     uint32_t votes_grid = 0;  // workgroups of the last k_votes launch on the engine's own buffers
+    bool weights_stale = false;  // pe_prune re-indexed the table: d_weights is by the old indices until the next k_tree
 
     // ---- committees ----
     std::vector<CommitteeTable> tables;

@@ -276,6 +276,7 @@ int tree_args(pe_engine* h, uint64_t* d_direct, const VoteTotals* d_totals, int 
         if (find_block(h, h->boost_root, &bi)) boost_pos = h->h_pos_of_idx[bi];
     }
     *const_cast<volatile uint32_t*>(head_word) = NONE32;
+    h->weights_stale = false;  // the launch this block is for writes the weights by the table's present indices
     *out = TreeArgs{tree_dev(h), d_direct, d_totals, 0, 0, 0, h->h_pos_of_idx[just_idx], boost_pos, h->cfg.slots_per_epoch,
                     h->cfg.proposer_score_boost, h->cfg.effective_balance_increment, h->d_weights.as<uint64_t>(), head_word,
                     clear_direct};
@@ -930,6 +931,8 @@ int pe_get_last_weights(pe_engine* h, uint64_t* out_weights, uint32_t n)
     int rc = need_init(h);
     if (rc) return rc;
     if (!out_weights || n != h->blocks.size() || !h->d_weights.p) return fail(h, PE_ERR_INVALID_ARG, "n must equal pe_num_blocks");
+    if (h->weights_stale)
+        return fail(h, PE_ERR_STATE, "pe_get_last_weights: pe_prune dropped the weights of the last head computation");
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     HIP_TRY(h, hipMemcpy(out_weights, h->d_weights.p, 8ull * n, hipMemcpyDeviceToHost));
     return PE_OK;
@@ -981,6 +984,73 @@ int pe_head_from_weights(pe_engine* h, const void* dev_buf_u64, uint32_t n_block
     return head_from_weights_impl(h, dev_buf_u64, n_blocks, out_root);
 }
 
+// ---------------------------------------------------------------- prune
+// Re-root the block table at the finalized root (include/posevo.h has the argument and the stated deviation).  The kept
+// blocks are the root and its descendants in their relative insertion order, so parents still precede children and the
+// relative lexicographic order of the roots -- the tie-break -- is the one they had.
+int pe_prune(pe_engine* h, pe_prune_stats* out)
+{
+    int rc = need_init(h);  // issues what is held and completes every open pipeline: rows in flight carry block indices, and a
+    if (rc) return rc;      // pending pe_get_head_async completion turns a head index into a root
+    if (h->dist_ready())
+        return fail(h, PE_ERR_STATE, "pe_prune: the handle exchanges with other ranks (pe_dist_init); "
+                                     "pruning under validator-range shards is not supported");
+    uint32_t fin;
+    if (!find_block(h, h->finalized.root, &fin))
+        return fail(h, PE_ERR_UNKNOWN_ROOT, "pe_prune: the finalized checkpoint's root is not in the store");
+    const uint32_t n_old = (uint32_t)h->blocks.size();
+    pe_prune_stats st{n_old, n_old, 0, 0};
+    if (fin == 0) {  // already rooted there: nothing changes, nothing is launched
+        if (out) *out = st;
+        return PE_OK;
+    }
+    std::vector<uint32_t> map(n_old, PE_VOTE_PRUNED);
+    uint32_t n_new = 0;
+    map[fin] = n_new++;
+    for (uint32_t i = fin + 1; i < n_old; ++i)  // parents first: a descendant's parent has been decided
+        if (map[h->blocks[i].parent] != PE_VOTE_PRUNED) map[i] = n_new++;
+    uint32_t idx;
+    if (!find_block(h, h->justified.root, &idx) || map[idx] == PE_VOTE_PRUNED)
+        return fail(h, PE_ERR_STATE, "pe_prune: the justified checkpoint's root does not descend from the finalized root");
+    if (!is_zero_root(h->best_justified.root) && find_block(h, h->best_justified.root, &idx) && map[idx] == PE_VOTE_PRUNED)
+        return fail(h, PE_ERR_STATE, "pe_prune: the best justified checkpoint's root does not descend from the finalized root");
+    // the latest messages follow on the device; the two counts come back through the arena's output block
+    if (h->n_val) {
+        Stage sg(h);
+        PE_TRY(sg.reserve(4ull * n_old));
+        const size_t off_map = sg.alloc(4ull * n_old);
+        OutBlock ob(h);
+        const size_t off_cnt = ob.alloc(16);
+        PE_TRY(ob.ensure());
+        memcpy(sg.host<uint32_t>(off_map), map.data(), 4ull * n_old);
+        HIP_TRY(h, sg.upload());
+        HIP_TRY(h, hipMemsetAsync(ob.dev<uint8_t>(off_cnt), 0, 16, h->stream));
+        launch_votes_remap(h->stream, RemapArgs{h->d_vote_block.as<uint32_t>(), h->n_val, sg.dev<uint32_t>(off_map), n_old,
+                                                ob.dev<unsigned long long>(off_cnt)});
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, ob.download(off_cnt, 16));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        st.votes_remapped = ob.host<unsigned long long>(off_cnt)[0];
+        st.votes_orphaned = ob.host<unsigned long long>(off_cnt)[1];
+    }
+    std::vector<Block> kept;
+    kept.reserve(n_new);
+    for (uint32_t i = fin; i < n_old; ++i) {
+        if (map[i] == PE_VOTE_PRUNED) continue;
+        Block b = h->blocks[i];
+        b.parent = i == fin ? NONE32 : map[b.parent];
+        kept.push_back(b);
+    }
+    h->blocks.swap(kept);
+    h->index_of.clear();
+    for (uint32_t i = 0; i < n_new; ++i) h->index_of.emplace(h->blocks[i].root, i);
+    h->weights_stale = true;
+    h->tree_dirty = true;
+    st.blocks_after = n_new;
+    if (out) *out = st;
+    return refresh_tree(h);  // pre-order positions, ranks over the kept roots, the device look-up tables
+}
+
 // ---------------------------------------------------------------- inspection
 uint32_t pe_num_blocks(const pe_engine* h) { return h ? (uint32_t)h->blocks.size() : 0; }
 uint64_t pe_num_validators(const pe_engine* h) { return h ? h->n_val : 0; }
@@ -1009,7 +1079,7 @@ int pe_get_latest_messages(pe_engine* h, uint64_t* out_epoch, uint32_t* out_bloc
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     for (uint64_t i = 0; i < n; ++i) {
         if (key[i] == 0) { out_epoch[i] = 0; out_block_index[i] = NONE32; }
-        else out_epoch[i] = (key[i] >> 32) - 1;
+        else out_epoch[i] = (key[i] >> 32) - 1;  // PE_VOTE_PRUNED: the message keeps its epoch and has lost its block
     }
     return PE_OK;
 }
@@ -1055,7 +1125,8 @@ int pe_set_latest_messages(pe_engine* h, uint64_t n, const uint64_t* epoch, cons
     std::vector<uint32_t> blk(n);
     for (uint64_t i = 0; i < n; ++i) {
         if (block_index[i] == NONE32) { key[i] = 0; blk[i] = NONE32; continue; }
-        if (block_index[i] >= h->blocks.size()) return fail(h, PE_ERR_INVALID_ARG, "latest message names an unknown block");
+        if (block_index[i] >= h->blocks.size() && block_index[i] != PE_VOTE_PRUNED)  // pruned: the epoch is kept
+            return fail(h, PE_ERR_INVALID_ARG, "latest message names an unknown block");
         if (epoch[i] >= 0xFFFFFFFEull) return fail(h, PE_ERR_CAPACITY, "target epoch does not fit 32 bits");
         key[i] = ((epoch[i] + 1) << 32) | 0xFFFFFFFFull;  // settled vote (see k_lmd)
         blk[i] = block_index[i];
@@ -1067,6 +1138,19 @@ int pe_set_latest_messages(pe_engine* h, uint64_t n, const uint64_t* epoch, cons
         else HIP_TRY(h, hipMemsetAsync(h->d_vote_slot.p, 0, 4 * n, h->stream));
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));  // the host vectors die at scope exit
+    return PE_OK;
+}
+int pe_set_block_checkpoints(pe_engine* h, uint32_t i, uint64_t pj_epoch, const uint8_t pj_root[32], uint64_t pf_epoch,
+                             const uint8_t pf_root[32])
+{
+    int rc = need_init(h);
+    if (rc) return rc;
+    if (!pj_root || !pf_root) return PE_ERR_INVALID_ARG;
+    if (i >= h->blocks.size()) return fail(h, PE_ERR_INVALID_ARG, "pe_set_block_checkpoints: no such block");
+    Block& b = h->blocks[i];
+    b.post_justified.epoch = pj_epoch; b.post_justified.root = to_root(pj_root);
+    b.post_finalized.epoch = pf_epoch; b.post_finalized.root = to_root(pf_root);
+    h->tree_dirty = true;  // filter_block_tree's leaf test reads them
     return PE_OK;
 }
 int pe_set_best_justified(pe_engine* h, uint64_t epoch, const uint8_t root[32])

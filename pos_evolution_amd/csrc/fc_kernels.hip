@@ -10,6 +10,8 @@
 //                    of B"), filter_block_tree viability (A.3) from a second scan,
 //                    best child by (weight, root) (pe:1114-1116), then pointer jumping
 //                    replaces the sequential descent of pe:1107-1116.
+//   k_votes_remap    pe_prune: the latest messages' block indices follow the re-rooted block table
+//                    (old index -> new index through a map staged in LDS).
 //   k_lmd_*          update_latest_messages (pe:1435-1441) for a whole batch with the
 //                    sequential semantics kept by a 64-bit atomicMax on (epoch+1, ~order).
 //   k_participation  the flag loop of process_attestation (pe:744-749).
@@ -62,6 +64,73 @@ void launch_votes(hipStream_t s, const VotesArgs& a, int lean)
         hipLaunchKernelGGL(k_votes<1>, dim3(blocks), dim3(VOTES_WG), sizeof(uint64_t) * a.n_blocks, s, a);
     else
         hipLaunchKernelGGL(k_votes<2>, dim3(blocks), dim3(VOTES_WG), sizeof(uint64_t) * a.n_blocks, s, a);
+}
+
+// ------------------------------------------------------------------ votes remap (pe_prune)
+// The block table has been re-rooted at the finalized root: a latest message's block index goes through the map old
+// insertion index -> new one.  NONE32 (no message), VOTE_PRUNED (orphaned by an earlier prune) and anything else
+// >= n_old stay as they are; vote_key and vote_slot are not touched (a message keeps its epoch and slot).
+__device__ __forceinline__ uint32_t remap_one(const uint32_t x, const uint32_t* __restrict__ lmap, const uint32_t n_old,
+                                              uint32_t& remapped, uint32_t& orphaned)
+{
+    if (x >= n_old) return x;
+    const uint32_t y = lmap[x];
+    orphaned += y == VOTE_PRUNED ? 1u : 0u;  // sums, not a branch between the two counters: they stay in registers
+    remapped += (y != VOTE_PRUNED && y != x) ? 1u : 0u;
+    return y;
+}
+
+__global__ void __launch_bounds__(REMAP_WG)
+k_votes_remap(const RemapArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lmap[];  // n_old entries (<= 32 KB)
+    uint32_t* __restrict__ vote_block = a.vote_block;
+    const uint64_t n_val = a.n_val;
+    const uint32_t n_old = a.n_old;
+    for (uint32_t b = threadIdx.x; b < n_old; b += REMAP_WG) lmap[b] = a.map[b];
+    __syncthreads();
+    uint32_t remapped = 0, orphaned = 0;
+    const uint64_t n_quads = (n_val + 3) / 4;
+    const uint64_t stride = (uint64_t)gridDim.x * REMAP_WG;
+    for (uint64_t q = (uint64_t)blockIdx.x * REMAP_WG + threadIdx.x; q < n_quads; q += stride) {
+        const uint64_t v0 = q * 4;
+        if (v0 + 4 <= n_val) {  // the array is 16-byte aligned and v0 % 4 == 0
+            const uint4 t = *reinterpret_cast<const uint4*>(vote_block + v0);
+            const uint32_t x = remap_one(t.x, lmap, n_old, remapped, orphaned);
+            const uint32_t y = remap_one(t.y, lmap, n_old, remapped, orphaned);
+            const uint32_t z = remap_one(t.z, lmap, n_old, remapped, orphaned);
+            const uint32_t w = remap_one(t.w, lmap, n_old, remapped, orphaned);
+            *reinterpret_cast<uint4*>(vote_block + v0) = make_uint4(x, y, z, w);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (v0 + k < n_val) vote_block[v0 + k] = remap_one(vote_block[v0 + k], lmap, n_old, remapped, orphaned);
+        }
+    }
+    // wave reduce -> LDS -> one device atomic per workgroup and count
+    __shared__ uint32_t wg_cnt[2];
+    if (threadIdx.x == 0) { wg_cnt[0] = 0; wg_cnt[1] = 0; }
+    remapped = wave_sum(remapped);
+    orphaned = wave_sum(orphaned);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        if (remapped) atomicAdd(&wg_cnt[0], remapped);
+        if (orphaned) atomicAdd(&wg_cnt[1], orphaned);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (wg_cnt[0]) atomicAdd(a.counts, (unsigned long long)wg_cnt[0]);
+        if (wg_cnt[1]) atomicAdd(a.counts + 1, (unsigned long long)wg_cnt[1]);
+    }
+}
+
+void launch_votes_remap(hipStream_t s, const RemapArgs& a)
+{
+    if (a.n_val == 0 || a.n_old == 0 || a.n_old > (uint32_t)TREE_MAX_BLOCKS) return;
+    const uint64_t n_quads = (a.n_val + 3) / 4;
+    uint64_t blocks = (n_quads + REMAP_WG - 1) / REMAP_WG;
+    if (blocks > REMAP_MAX_WG) blocks = REMAP_MAX_WG;
+    hipLaunchKernelGGL(k_votes_remap, dim3((unsigned)blocks), dim3(REMAP_WG), sizeof(uint32_t) * a.n_old, s, a);
 }
 
 // ------------------------------------------------------------------ tree

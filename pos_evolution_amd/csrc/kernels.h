@@ -305,7 +305,17 @@ struct TreeArgs {
     uint32_t justified_pos, boost_pos; uint64_t slots_per_epoch, boost_percent, balance_increment;
     uint64_t* weights_by_idx; uint32_t* head_idx; int clear_direct;
 };
+// pe_prune: vote_block[v] = map[vote_block[v]] for every latest message that names a block of the old table.
+struct RemapArgs {
+    uint32_t* vote_block; uint64_t n_val;  // padded to a multiple of four entries, 16-byte aligned
+    const uint32_t* map; uint32_t n_old;   // old insertion index -> new one, VOTE_PRUNED where the block goes; n_old <= TREE_MAX_BLOCKS
+    unsigned long long* counts;            // [0] += messages whose index changed (block kept), [1] += messages orphaned
+};
+constexpr uint32_t VOTE_PRUNED = 0xFFFFFFFEu;  // PE_VOTE_PRUNED (include/posevo.h)
+constexpr int REMAP_WG = 256;
+constexpr unsigned REMAP_MAX_WG = 256;  // grid cap: one pass covers REMAP_MAX_WG * REMAP_WG * 4 validators, then the grid strides
 // the stand-alone launches (lean: the shapes that fit beside a running accumulation)
+void launch_votes_remap(hipStream_t s, const RemapArgs& a);
 void launch_att_ingest(hipStream_t s, const IngestArgs& a);
 void launch_att_validate_fc(hipStream_t s, const ValidateFcArgs& a);
 void launch_lmd_vm_tables(hipStream_t s, const LmdVmArgs& a);

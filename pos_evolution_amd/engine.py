@@ -411,6 +411,17 @@ class Engine:
         self._check(self._lib.pe_set_checkpoints(self._h, justified[0], _root(justified[1]), finalized[0],
                                                  _root(finalized[1])))
 
+    def prune(self) -> dict:
+        """pe_prune: re-root the block table at store.finalized_checkpoint.root (the root and its descendants stay, in
+        their insertion order; the root becomes block 0) and remap the latest messages on the device.  The caller decides
+        when -- typically after an ``on_block`` that raised the finalized checkpoint.  -> dict(blocks_before, blocks_after,
+        votes_remapped, votes_orphaned); unobservable to ``get_head`` (include/posevo.h has the argument and the stated
+        deviation for later calls that name a removed block)."""
+        st = _abi.pe_prune_stats()
+        self._check(self._lib.pe_prune(self._h, C.addressof(st)))
+        return dict(blocks_before=int(st.blocks_before), blocks_after=int(st.blocks_after),
+                    votes_remapped=int(st.votes_remapped), votes_orphaned=int(st.votes_orphaned))
+
     def set_proposer_boost(self, root: bytes):
         self._check(self._lib.pe_set_proposer_boost(self._h, _root(root)))
 
@@ -1071,7 +1082,9 @@ class Engine:
         return out.value
 
     def latest_messages(self):
-        """-> (epoch uint64[V], block_index uint32[V]); block_index 0xFFFFFFFF = no message."""
+        """-> (epoch uint64[V], block_index uint32[V]); block_index 0xFFFFFFFF = no message (epoch 0), PE_VOTE_PRUNED
+        (0xFFFFFFFE) = a message whose block ``prune`` removed: it keeps its epoch, so a later vote of an equal or lower
+        epoch is still refused, and weighs on nothing."""
         n = self.num_validators
         ep = np.zeros(max(n, 1), dtype=np.uint64)
         bi = np.zeros(max(n, 1), dtype=np.uint32)
@@ -1141,6 +1154,10 @@ class Engine:
         sc = st["scalars"]
         roots = st["roots"]
         self.store_init(sc["genesis_time"], int(st["slot"][0]), roots[0].tobytes())
+        # block 0 of a pruned store is an ordinary block: its own post-state checkpoints, not the anchor's
+        self._check(self._lib.pe_set_block_checkpoints(
+            self._h, 0, int(st["post_justified_epoch"][0]), _root(st["post_justified_root"][0].tobytes()),
+            int(st["post_finalized_epoch"][0]), _root(st["post_finalized_root"][0].tobytes())))
         for i in range(1, roots.shape[0]):
             self.add_block(roots[i].tobytes(), roots[int(st["parent"][i])].tobytes(), int(st["slot"][i]),
                            (int(st["post_justified_epoch"][i]), st["post_justified_root"][i].tobytes()),

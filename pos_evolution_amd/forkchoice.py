@@ -11,6 +11,7 @@ pos-evolution.md (``pe:N``):
     on_attester_slashing(store, attester_slashing)          pe:1447-1461
     find_attester_slashings(store, attestations)            pe:1128, pe:1134-1143 (the detection the handlers presume)
     get_head(store) -> Root                                 pe:1102-1116
+    prune(store)                                            -- (not in the reference: its Store never forgets a block)
     process_attestation(state, attestation)                 pe:722-754    (state bound with bind_state)
     compute_proposer_index(state, indices, seed)            pe:604-618    (state bound with bind_state)
     process_effective_balance_updates(state)                pe:122-133    (state bound with bind_state)
@@ -126,7 +127,8 @@ class Store:
     def latest_messages(self) -> Dict[int, LatestMessage]:
         epoch, block = self.engine.latest_messages()
         roots = [self.engine.block_root_at(i) for i in range(self.engine.num_blocks)]
-        return {int(i): LatestMessage(int(epoch[i]), roots[int(block[i])])
+        # a message whose block ``prune`` removed keeps its epoch; its root is gone and reads as the unset root
+        return {int(i): LatestMessage(int(epoch[i]), roots[int(block[i])] if block[i] != _abi.PE_VOTE_PRUNED else ZERO_ROOT)
                 for i in np.nonzero(block != _abi.NONE32)[0]}
 
     # -- inputs the pyspec derives from states the engine does not hold -----------
@@ -336,6 +338,22 @@ def get_head(store: Store) -> bytes:
     have not been handed over (Store.ensure_justified_state)."""
     store.ensure_justified_state()
     return store.engine.get_head()
+
+
+def prune(store: Store) -> dict:
+    """Re-root the store at ``store.finalized_checkpoint.root`` (Engine.prune): the finalized root and its descendants
+    stay, every other block leaves the engine's table and ``store.blocks``.  Not a reference function -- its Store never
+    forgets a block -- but unobservable to ``get_head``: on_block refuses blocks outside that subtree (pe:998-1005),
+    get_head starts inside it (pe:1106) and a block's weight sums its own subtree (pe:322).  Call it after an ``on_block``
+    that raised the finalized checkpoint.  -> the engine's counts (blocks_before, blocks_after, votes_remapped,
+    votes_orphaned)."""
+    eng = store.engine
+    stats = eng.prune()
+    if stats["blocks_after"] != stats["blocks_before"]:
+        kept = {eng.block_root_at(i) for i in range(eng.num_blocks)}
+        for root in [r for r in store.blocks if r not in kept]:
+            del store.blocks[root]
+    return stats
 
 
 # ----------------------------------------------------------------------------- process_attestation
