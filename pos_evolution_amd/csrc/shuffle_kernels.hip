@@ -245,10 +245,9 @@ int launch_shuffle(hipStream_t s, const uint32_t* d_seed_be, uint32_t n, uint32_
                            rounds, d_source, d_pivots);
     // the LDS form needs n / 16 bytes (+ the ragged ends) of LDS: up to ~1.5 M indices inside 96 KB; larger (and tiny) lists
     // take the gather
-    constexpr bool lds_ok = true;
     const size_t lds_bytes = 32ull * ((size_t)nb / 2 + 4);
     constexpr size_t LDS_CAP = SHUF_LDS_CAP;
-    if (lds_ok && lds_bytes <= LDS_CAP && n >= 4096 && rounds > 0) {
+    if (lds_bytes <= LDS_CAP && n >= 4096 && rounds > 0) {
         constexpr int PER = 4;
         if (first_use_on_this_device<4242>())
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_shuffle_indices_lds<PER>),

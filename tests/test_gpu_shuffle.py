@@ -1,6 +1,16 @@
 """-m gpu: committee computation on the GPU (pe_compute_committees) against the reference's own functions
 compute_committee (pe:495-504) / compute_shuffled_index (pe:513-534) as transcribed in the L0 oracle -- this part
-of the path is defined verbatim by the reference, so parity here is pinned by the reference text."""
+of the path is defined verbatim by the reference, so parity here is pinned by the reference text.
+
+Which kernel of launch_shuffle (shuffle_kernels.hip) each case reaches -- k_shuffle_indices_lds<4> takes 4096 <= n <= 1 571 072
+with rounds > 0, k_shuffle_indices (the gather) everything else:
+  test_compute_committees_vs_reference_functions   minimal (10 rounds): n = 1, 2, 33, 257 the gather, n = 5000 the LDS form;
+                                                   mainnet (90 rounds): n = 100, 2500, both the gather.  Whole lists.
+  test_golden_shuffle_vectors                      n <= 333: the gather.  Whole lists.
+  test_million_validator_epoch_...                 n = 2^20, 90 rounds: the LDS form; a permutation and 64 positions.
+  test_compute_committees_identity_active_set_...  n = 30000, 90 rounds: the LDS form, against a second run of itself.
+The LDS form at 90 rounds on whole lists, and the sizes, round counts and pivots at which the two kernels' code paths change,
+are in tests/test_gpu_shuffle_edges.py, against the whole-list model of tests/shuffle_model.py."""
 import json
 import os
 
