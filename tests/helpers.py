@@ -77,3 +77,64 @@ def install_votes(e, tree, comm, vote, now_slot=None):
     status, _, _ = e.on_attestation_batch(packed=(atts, arena))
     assert (status == 0).all(), np.unique(status)
     return installed
+
+
+def closed_form_sums(index_sets, a, b):
+    """closed_form_sum for many sets at once: |S|*A + (sum i)*B, from the doublings of A and of B computed once (a few
+    additions per set where a double-and-add per set costs hundreds).  -> list of 96-byte encodings."""
+    sets = [np.asarray(s, dtype=np.int64).reshape(-1) for s in index_sets]
+    counts = [int(s.size) for s in sets]
+    sums = [int(s.sum()) for s in sets]
+    dbl_a, dbl_b = [g1.mul(a, g1.G)], [g1.mul(b, g1.G)]
+    for table, top in ((dbl_a, max(counts, default=0)), (dbl_b, max(sums, default=0))):
+        while (1 << len(table)) <= top:
+            table.append(g1.double(table[-1]))
+    memo = {}
+
+    def times(n, table):
+        acc, i = None, 0
+        while n:
+            if n & 1:
+                acc = g1.add(acc, table[i])
+            n >>= 1
+            i += 1
+        return acc
+
+    out = []
+    for c, s in zip(counts, sums):
+        if (c, s) not in memo:
+            memo[(c, s)] = g1.to_bytes96(g1.add(times(c, dbl_a), times(s, dbl_b)))
+        out.append(memo[(c, s)])
+    return out
+
+
+def ragged_committees(sizes, n_val, seed, slots_per_epoch=32):
+    """A committee table whose first len(sizes) committees have exactly the given sizes, in that order, padded with empty
+    committees to a multiple of slots_per_epoch.  Members: the head of a seeded permutation of the registry [0, n_val) --
+    nobody sits in two committees (a partition, as the resident-row path requires)."""
+    sizes = [int(s) for s in sizes]
+    total = sum(sizes)
+    assert total <= n_val
+    pad = -len(sizes) % slots_per_epoch
+    offsets = np.concatenate([[0], np.cumsum(sizes + [0] * pad)]).astype(np.uint32)
+    members = np.random.Generator(np.random.PCG64(seed)).permutation(n_val)[:total].astype(np.uint32)
+    return synth.Committees(offsets, members)
+
+
+def committee_attestations(comm, tree, epoch, committees, bit_rows, slots_per_epoch=32):
+    """One pe_attestation row per entry: row i attests for committee committees[i] of `epoch` with the bits bit_rows[i]
+    (n_bits = len(bit_rows[i]), whatever the committee's size), voting for the tree's last block with a consistent FFG
+    target.  -> (atts, arena)."""
+    cps = (comm.offsets.size - 1) // slots_per_epoch
+    blk = tree.roots.shape[0] - 1
+    assert int(tree.slot[blk]) <= epoch * slots_per_epoch
+    atts = np.zeros(len(committees), dtype=synth.ATT_DTYPE)
+    c = np.asarray(committees, dtype=np.uint64)
+    atts["slot"], atts["index"] = epoch * slots_per_epoch + c // cps, c % cps
+    atts["beacon_block_root"] = tree.roots[blk]
+    atts["source_epoch"], atts["source_root"] = 0, tree.roots[0]
+    atts["target_epoch"], atts["target_root"] = epoch, tree.roots[synth.ancestor_at(tree, blk, epoch * slots_per_epoch)]
+    atts["flags"] = 1
+    arena, offs, nb = synth.pack_bit_rows(bit_rows)
+    atts["bits_offset"], atts["n_bits"] = offs, nb
+    return atts, arena
