@@ -5,6 +5,7 @@
 // differ.  Like fp381_lazy.inc it has no include guard; unlike it, it opens namespace posevo itself.  No __global__
 // function, no launcher and no __device__ variable belongs here.
 #include <algorithm>
+#include "att_row.h"
 #include "kernels.h"
 #include "wave64.h"
 
@@ -101,7 +102,7 @@ __device__ __forceinline__ void att_ingest_body(const uint32_t bid, const uint32
     load_row(r, rows, i);
     const uint32_t b0 = r.q[8].x, nb = r.q[8].y;
     // "attestation bits exceed the arena" / "target epoch must fit 32 bits" of the host path: the whole call fails
-    if (nb > 0x7FFFFFFFu || (unsigned long long)b0 + ((unsigned long long)nb + 7) / 8 > arena_len || row_target_epoch(r) >= 0xFFFFFFFEull) atomicMax(&plan->error, ERR_INVALID_ARG);
+    if (!att_bits_in_arena(b0, nb, arena_len) || row_target_epoch(r) >= 0xFFFFFFFEull) atomicMax(&plan->error, ERR_INVALID_ARG);
     uint32_t h = att_hash(r) & mask;
     for (;;) {
         const uint32_t prev = atomicCAS(&tab[h], ATT_EMPTY, i);
@@ -204,15 +205,11 @@ __device__ __forceinline__ void att_plan_body(const uint32_t bid, const uint32_t
     if (table == NONE32) st = ST_NO_TABLE;
     else if (in) {
         const TableDev& t = a.tables.t[table];
-        const unsigned long long cps = t.n_committees / spe;
-        // compute_committee(index = (slot % SLOTS_PER_EPOCH) * cps + data.index, count = cps * SLOTS_PER_EPOCH):
-        // on_attestation's get_beacon_committee asserts nothing about data.index itself -- only the flat id has
-        // to exist; pe:727 (process_attestation) and pe_aggregate require data.index < cps
-        const unsigned long long flat = index < 0xFFFFFFFFull ? (slot_no % spe) * cps + index : ~0ull;
-        index_over = index >= cps ? 1u : 0u;
-        if (flat >= t.n_committees) st = ST_INDEX_RANGE;
+        const CommitteePos cp = att_committee_pos(t.n_committees, spe, slot_no, index);  // (att_row.h: who requires what)
+        index_over = cp.index_over ? 1u : 0u;
+        if (!cp.exists) st = ST_INDEX_RANGE;
         else {
-            pos = (uint32_t)flat;
+            pos = cp.pos;
             mbase = t.offsets[pos];
             size = t.offsets[pos + 1] - mbase;
             if (nbits != size) st = ST_BITS_LENGTH;  // len(aggregation_bits) == len(committee), pe:730

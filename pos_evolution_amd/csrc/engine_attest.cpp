@@ -1,7 +1,8 @@
 // engine_attest.cpp -- on_attestation (pe:963-979, 1423-1428), process_attestation (pe:722-754) and aggregation
 // (validator guide A.8; pe:474/659/715/1536) over attestation rows in HOST memory: validate_on_attestation (A.4) and
 // the grouping run here, the bit / point / table work on the device.  engine_resident.cpp is the same path with the
-// rows resident in device memory.
+// rows resident in device memory.  The two row rules both share with the device bodies (bits inside the arena, committee
+// position) are att_row.h; resolve_committee (engine_internal.h) applies the second to a loaded table.
 #include "engine_internal.h"
 
 using namespace posevo;
@@ -29,25 +30,10 @@ int32_t validate_for_fork_choice(pe_engine* h, const pe_attestation& a, Resolved
     // get_indexed_attestation -> get_beacon_committee(target_state, slot, index) (A.6)
     CommitteeTable* t = find_table(h, a.target_epoch);
     if (!t) return PE_ATT_NO_COMMITTEE_TABLE;
-    const uint64_t cps = t->n_committees / h->cfg.slots_per_epoch;
-    const uint64_t pos = (a.slot % h->cfg.slots_per_epoch) * cps + a.index;
-    if (pos >= t->n_committees) return PE_ATT_COMMITTEE_INDEX_OUT_OF_RANGE;
-    const uint32_t size = t->offsets[pos + 1] - t->offsets[pos];
-    if (a.n_bits < size) return PE_ATT_BITS_LENGTH_MISMATCH;  // bits[i] would raise for i >= len(bits)
-    out->table = t;
-    out->pos = (uint32_t)pos;
-    out->size = size;
+    if (!resolve_committee(h, t, a, out).exists) return PE_ATT_COMMITTEE_INDEX_OUT_OF_RANGE;
+    if (a.n_bits < out->size) return PE_ATT_BITS_LENGTH_MISMATCH;  // bits[i] would raise for i >= len(bits)
     out->block_idx = blk_idx;
     return PE_ATT_OK;
-}
-
-// The handlers and pe_get_indexed_attestations re-pack the caller's bits on the host: device memory would fault there.
-bool bits_on_device(const uint8_t* bits_arena)
-{
-    hipPointerAttribute_t pa;
-    if (hipPointerGetAttributes(&pa, bits_arena) == hipSuccess) return pa.type == hipMemoryTypeDevice;
-    (void)hipGetLastError();
-    return false;
 }
 
 }  // namespace posevo
@@ -61,6 +47,17 @@ static inline uint32_t att_data_tag(const pe_attestation& a)
     memcpy(&r1, a.target_root, 4);
     return (uint32_t)a.slot * 0x9E3779B1u ^ (uint32_t)a.index * 0x85EBCA6Bu ^ (uint32_t)a.target_epoch * 0xC2B2AE35u ^ r0 ^
            (r1 << 1);
+}
+// What a row over resident bits answers once the aggregate's {popcount, overlap} of its group g are on the host (`info`):
+// members that overlap never verify (A.8), no member is A.7's empty index list; *count (optional) = the popcount of an
+// accepted row.  Fails when the aggregate's completion never filled `info`.
+static int resident_verdict(pe_engine* h, const std::vector<uint32_t>& info, uint32_t g, int32_t* status, uint32_t* count = nullptr)
+{
+    if (2 * (size_t)g + 1 >= info.size()) return fail(h, PE_ERR_STATE, "resident aggregate did not complete");
+    if (info[2 * g + 1]) *status = PE_ATT_BAD_SIGNATURE;
+    else if (info[2 * g] == 0) *status = PE_ATT_EMPTY_OR_INVALID_INDICES;
+    if (count) *count = *status == PE_ATT_OK ? info[2 * g] : 0;
+    return PE_OK;
 }
 namespace posevo {
 bool find_resident(const pe_engine* h, const pe_attestation& a, uint32_t* g_out, uint32_t guess)
@@ -115,7 +112,7 @@ int pe_on_attestation_batch(pe_engine* h, const pe_attestation* atts, uint32_t n
                 return fail(h, PE_ERR_INVALID_ARG, "PE_BITS_RESIDENT: row is not a row of the last pe_aggregate");
             continue;
         }
-        if (a.n_bits > 0x7FFFFFFFu || (uint64_t)a.bits_offset + ((uint64_t)a.n_bits + 7) / 8 > arena_len)
+        if (!att_bits_in_arena(a.bits_offset, a.n_bits, arena_len))
             return fail(h, PE_ERR_INVALID_ARG, "attestation bits exceed the arena");
         word_bound += ((uint64_t)a.n_bits + 31) / 32 + 1;
     }
@@ -296,11 +293,7 @@ int pe_on_attestation_batch(pe_engine* h, const pe_attestation* atts, uint32_t n
             const std::vector<uint32_t>& info = *info_p;
             for (uint32_t k = 0; k < n_rows; ++k) {
                 const uint32_t i = src[k], g = (*res_group_p)[i];
-                if (2 * (size_t)g + 1 >= info.size()) return fail(h, PE_ERR_STATE, "resident aggregate did not complete");
-                const uint32_t cnt = info[2 * g], overlap = info[2 * g + 1];
-                if (overlap) status[i] = PE_ATT_BAD_SIGNATURE;
-                else if (cnt == 0) status[i] = PE_ATT_EMPTY_OR_INVALID_INDICES;
-                if (out_count) out_count[i] = status[i] == PE_ATT_OK ? cnt : 0;
+                PE_TRY(resident_verdict(h, info, g, &status[i], out_count ? &out_count[i] : nullptr));
             }
         }
         return PE_OK;
@@ -322,7 +315,7 @@ int pe_get_indexed_attestations(pe_engine* h, const pe_attestation* atts, uint32
     if (bits_on_device(bits_arena)) return fail(h, PE_ERR_INVALID_ARG, "bits in device memory: only pe_aggregate reads them there");
     uint64_t word_bound = 0;
     for (uint32_t i = 0; i < n; ++i) {
-        if (atts[i].n_bits > 0x7FFFFFFFu || (uint64_t)atts[i].bits_offset + ((uint64_t)atts[i].n_bits + 7) / 8 > arena_len)
+        if (!att_bits_in_arena(atts[i].bits_offset, atts[i].n_bits, arena_len))
             return fail(h, PE_ERR_INVALID_ARG, "attestation bits exceed the arena");
         word_bound += ((uint64_t)atts[i].n_bits + 31) / 32 + 1;
     }
@@ -342,31 +335,25 @@ int pe_get_indexed_attestations(pe_engine* h, const pe_attestation* atts, uint32
         const pe_attestation& a = atts[i];
         int32_t s = PE_ATT_OK;
         CommitteeTable* t = find_table(h, a.target_epoch);
+        Resolved c;
         uint32_t cnt = 0;
         if (!t) s = PE_ATT_NO_COMMITTEE_TABLE;
+        else if (!resolve_committee(h, t, a, &c).exists) s = PE_ATT_COMMITTEE_INDEX_OUT_OF_RANGE;
+        else if (a.n_bits < c.size) s = PE_ATT_BITS_LENGTH_MISMATCH;
+        else if (c.size > 8192) return fail(h, PE_ERR_CAPACITY, "committee larger than 8192 members");
         else {
-            const uint64_t cps = t->n_committees / h->cfg.slots_per_epoch;
-            const uint64_t pos = (a.slot % h->cfg.slots_per_epoch) * cps + a.index;
-            if (pos >= t->n_committees) s = PE_ATT_COMMITTEE_INDEX_OUT_OF_RANGE;
-            else {
-                const uint32_t size = t->offsets[pos + 1] - t->offsets[pos];
-                if (a.n_bits < size) s = PE_ATT_BITS_LENGTH_MISMATCH;
-                else if (size > 8192) return fail(h, PE_ERR_CAPACITY, "committee larger than 8192 members");
-                else {
-                    cnt = size ? pack_bits(bits_arena + a.bits_offset, size, words + n_words) : 0;
-                    AttRow& r = rows[n_rows];
-                    r.member_base = t->offsets[pos];
-                    r.n_bits = size;
-                    r.bits_word = n_words;
-                    r.block_idx = r.epoch_p1 = r.order = r.flag_mask = r.which = r.slot = 0;
-                    r.gate = NONE32;
-                    offs[n_rows] = (uint32_t)total;
-                    n_words += (size + 31) / 32;
-                    row_table.push_back(t);
-                    row_src.push_back(i);
-                    ++n_rows;
-                }
-            }
+            cnt = c.size ? pack_bits(bits_arena + a.bits_offset, c.size, words + n_words) : 0;
+            AttRow& r = rows[n_rows];
+            r.member_base = t->offsets[c.pos];
+            r.n_bits = c.size;
+            r.bits_word = n_words;
+            r.block_idx = r.epoch_p1 = r.order = r.flag_mask = r.which = r.slot = 0;
+            r.gate = NONE32;
+            offs[n_rows] = (uint32_t)total;
+            n_words += (c.size + 31) / 32;
+            row_table.push_back(t);
+            row_src.push_back(i);
+            ++n_rows;
         }
         status[i] = s;
         out_offsets[i] = (uint32_t)total;
@@ -460,7 +447,7 @@ int aggregate_impl(pe_engine* h, const pe_attestation* atts, uint32_t n, const u
     uint64_t lo = ~0ull, hi = 0;                    // byte span of the arena this call reads
     for (uint32_t i = 0; i < n; ++i) {
         const uint64_t b0 = atts[i].bits_offset, b1 = b0 + ((uint64_t)atts[i].n_bits + 7) / 8;
-        if (b1 > arena_len || atts[i].n_bits > 0x7FFFFFFFu) return fail(h, PE_ERR_INVALID_ARG, "attestation bits exceed the arena");
+        if (!att_bits_in_arena(atts[i].bits_offset, atts[i].n_bits, arena_len)) return fail(h, PE_ERR_INVALID_ARG, "attestation bits exceed the arena");
         if (atts[i].n_bits) { lo = std::min(lo, b0); hi = std::max(hi, b1); }
         uint32_t slot = (uint32_t)hash_att(atts[i]) & (tab_size - 1);
         uint32_t g;
@@ -519,14 +506,8 @@ int aggregate_impl(pe_engine* h, const pe_attestation* atts, uint32_t n, const u
             } else {
                 table_pk = t;
             }
-            const uint64_t cps = t->n_committees / h->cfg.slots_per_epoch;
-            if (a.index >= cps) return fail(h, PE_ERR_INVALID_ARG, "committee index out of range");
-            const uint64_t pos = (a.slot % h->cfg.slots_per_epoch) * cps + a.index;
-            const uint32_t size = t->offsets[pos + 1] - t->offsets[pos];
-            if (a.n_bits != size) return fail(h, PE_ERR_INVALID_ARG, "len(aggregation_bits) != len(committee)");  // pe:730
-            gres[g].table = t;
-            gres[g].pos = (uint32_t)pos;
-            gres[g].size = size;
+            if (resolve_committee(h, t, a, &gres[g]).index_over) return fail(h, PE_ERR_INVALID_ARG, "committee index out of range");
+            if (a.n_bits != gres[g].size) return fail(h, PE_ERR_INVALID_ARG, "len(aggregation_bits) != len(committee)");  // pe:730
         }
     }
     // ---- lay everything out in the staging block ----
@@ -553,17 +534,8 @@ int aggregate_impl(pe_engine* h, const pe_attestation* atts, uint32_t n, const u
     // Where do the caller's bits live?  Pageable host memory is copied into the pinned block here; pinned host memory
     // and device memory are copied by the copy engine straight into the device block (no pass over them on the host) --
     // the caller then keeps them unchanged until the call's outputs are complete.
-    int arena_kind = 0;  // 0 pageable host, 1 pinned host, 2 device
-    if (span) {
-        hipPointerAttribute_t pa;
-        if (hipPointerGetAttributes(&pa, bits_arena) == hipSuccess) {
-            if (pa.type == hipMemoryTypeDevice) arena_kind = 2;
-            else if (pa.type == hipMemoryTypeHost) arena_kind = 1;
-        } else {
-            (void)hipGetLastError();  // plain malloc'ed memory is "invalid value" to older runtimes: not an error here
-        }
-    }
-    if (arena_kind == 0) memcpy(st.host<uint8_t>(off_arena), bits_arena + lo, span);
+    const MemKind arena_kind = span ? mem_kind(bits_arena) : MemKind::Pageable;
+    if (arena_kind == MemKind::Pageable) memcpy(st.host<uint8_t>(off_arena), bits_arena + lo, span);
     memset(st.host<uint8_t>(off_arena) + span, 0, 16);
     lap.mark("agg.2b_memcpy_arena");
     UnionGroup* ug = st.host<UnionGroup>(off_ug);
@@ -689,11 +661,11 @@ int aggregate_impl(pe_engine* h, const pe_attestation* atts, uint32_t n, const u
     if (h->A().side_used) HIP_TRY(h, hipStreamWaitEvent(ms, h->ev_join, 0));
     PE_TRY(aux_join(h, ms));  // ... and behind an earlier process_attestation / signature leg of this pipeline (they read
                               // the resident words on the state-transition stream)
-    if (arena_kind == 0) {
+    if (arena_kind == MemKind::Pageable) {
         HIP_TRY(h, st.upload());
     } else {  // the bits by the copy engine from where they lie, then the zero pad and everything behind it
         HIP_TRY(h, hipMemcpyAsync(st.dev<uint8_t>(off_arena), bits_arena + lo, span,
-                                  arena_kind == 2 ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ms));
+                                  arena_kind == MemKind::Device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ms));
         HIP_TRY(h, hipMemcpyAsync(st.dev<uint8_t>(off_arena) + span, st.host<uint8_t>(off_arena) + span,
                                   st.used - (off_arena + span), hipMemcpyHostToDevice, ms));
     }
@@ -911,7 +883,7 @@ int pe_process_attestation_batch(pe_engine* h, const pe_state_ctx* st, const pe_
                 return fail(h, PE_ERR_INVALID_ARG, "PE_BITS_RESIDENT: row is not a row of the last pe_aggregate");
             continue;
         }
-        if (atts[i].n_bits > 0x7FFFFFFFu || (uint64_t)atts[i].bits_offset + ((uint64_t)atts[i].n_bits + 7) / 8 > arena_len)
+        if (!att_bits_in_arena(atts[i].bits_offset, atts[i].n_bits, arena_len))
             return fail(h, PE_ERR_INVALID_ARG, "attestation bits exceed the arena");
         word_bound += ((uint64_t)atts[i].n_bits + 31) / 32 + 1;
     }
@@ -939,19 +911,14 @@ int pe_process_attestation_batch(pe_engine* h, const pe_state_ctx* st, const pe_
         out_numerators[i] = 0;
         int32_t s = PE_ATT_OK;
         CommitteeTable* t = nullptr;
-        uint64_t pos = 0;
-        uint32_t size = 0;
+        Resolved c;
         if (a.target_epoch != prev_epoch && a.target_epoch != cur_epoch) s = PE_ATT_TARGET_EPOCH_NOT_CURRENT_OR_PREVIOUS;  // pe:724
         else if (a.target_epoch != a.slot / spe) s = PE_ATT_TARGET_EPOCH_SLOT_MISMATCH;                                  // pe:725
         else if (!(a.slot + h->cfg.min_attestation_inclusion_delay <= st->slot && st->slot <= a.slot + spe))
             s = PE_ATT_INCLUSION_WINDOW;                                                                                 // pe:726
         else if (!(t = find_table(h, a.target_epoch))) s = PE_ATT_NO_COMMITTEE_TABLE;
-        else if (a.index >= t->n_committees / spe) s = PE_ATT_COMMITTEE_INDEX_OUT_OF_RANGE;                              // pe:727
-        else {
-            pos = (a.slot % spe) * (t->n_committees / spe) + a.index;
-            size = t->offsets[pos + 1] - t->offsets[pos];
-            if (a.n_bits != size) s = PE_ATT_BITS_LENGTH_MISMATCH;                                                       // pe:730
-        }
+        else if (resolve_committee(h, t, a, &c).index_over) s = PE_ATT_COMMITTEE_INDEX_OUT_OF_RANGE;                     // pe:727
+        else if (a.n_bits != c.size) s = PE_ATT_BITS_LENGTH_MISMATCH;                                                    // pe:730
         uint32_t flag_mask = 0;
         if (s == PE_ATT_OK) {
             // get_attestation_participation_flag_indices (A.9)
@@ -974,13 +941,13 @@ int pe_process_attestation_batch(pe_engine* h, const pe_state_ctx* st, const pe_
         }
         if (s == PE_ATT_OK) {
             // resident rows: emptiness / member overlap are settled on the device and reported at completion
-            const uint32_t cnt = resident ? 1u : size ? pack_bits(bits_arena + a.bits_offset, size, words + n_words) : 0;
+            const uint32_t cnt = resident ? 1u : c.size ? pack_bits(bits_arena + a.bits_offset, c.size, words + n_words) : 0;
             if (cnt == 0) s = PE_ATT_EMPTY_OR_INVALID_INDICES;                                 // pe:736
             else if (!(a.flags & PE_ATT_FLAG_SIGNATURE_VALID)) s = PE_ATT_BAD_SIGNATURE;
             if (s == PE_ATT_OK) {
                 Acc e;
-                e.row.member_base = t->offsets[pos];
-                e.row.n_bits = size;
+                e.row.member_base = t->offsets[c.pos];
+                e.row.n_bits = c.size;
                 e.row.bits_word = resident ? h->res_groups[res_group[i]].word : n_words;
                 e.row.gate = resident ? 2 * res_group[i] + 1 : NONE32;
                 e.row.block_idx = 0;
@@ -991,9 +958,9 @@ int pe_process_attestation_batch(pe_engine* h, const pe_state_ctx* st, const pe_
                 e.row.which = a.target_epoch == cur_epoch ? 0u : 1u;                           // pe:739-742
                 e.src = i;
                 e.table = t;
-                e.pos = (uint32_t)pos;
+                e.pos = c.pos;
                 acc.push_back(e);
-                if (!resident) n_words += (size + 31) / 32;
+                if (!resident) n_words += (c.size + 31) / 32;
             }
         }
         status[i] = s;
@@ -1065,12 +1032,8 @@ int pe_process_attestation_batch(pe_engine* h, const pe_state_ctx* st, const pe_
         memcpy(out_numerators, h->arena[ai].h_pin.as<uint8_t>() + ob_base + off_num, 8ull * n);
         if (resident) {
             const std::vector<uint32_t>& info = *info_p;
-            for (uint32_t i : *src_p) {
-                const uint32_t g = (*res_group_p)[i];
-                if (2 * (size_t)g + 1 >= info.size()) return fail(h, PE_ERR_STATE, "resident aggregate did not complete");
-                if (info[2 * g + 1]) status[i] = PE_ATT_BAD_SIGNATURE;
-                else if (info[2 * g] == 0) status[i] = PE_ATT_EMPTY_OR_INVALID_INDICES;
-            }
+            for (uint32_t i : *src_p)
+                PE_TRY(resident_verdict(h, info, (*res_group_p)[i], &status[i]));
         }
         return PE_OK;
     };
@@ -1078,149 +1041,6 @@ int pe_process_attestation_batch(pe_engine* h, const pe_state_ctx* st, const pe_
     rc = finish_call(h, stg, ob, complete);
     lap2.mark("proc.3_wait_d2h");
     return rc;
-}
-
-
-
-int pe_participation_set(pe_engine* h, int which, const uint8_t* flags, uint64_t n)
-{
-    if (!h || !flags || n != h->n_val || (which != 0 && which != 1)) return PE_ERR_INVALID_ARG;
-    PE_TRY(enter(h));
-    DevBuf& b = which ? h->d_part_prev : h->d_part_cur;
-    HIP_TRY(h, hipMemcpyAsync(b.p, flags, n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return PE_OK;
-}
-int pe_participation_get(pe_engine* h, int which, uint8_t* out_flags, uint64_t n)
-{
-    if (!h || !out_flags || n != h->n_val || (which != 0 && which != 1)) return PE_ERR_INVALID_ARG;
-    PE_TRY(enter(h));
-    DevBuf& b = which ? h->d_part_prev : h->d_part_cur;
-    HIP_TRY(h, hipMemcpyAsync(out_flags, b.p, n, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return PE_OK;
-}
-int pe_participation_rotate(pe_engine* h)
-{
-    if (!h) return PE_ERR_INVALID_ARG;
-    (void)hipSetDevice(h->device);
-    std::swap(h->d_part_cur, h->d_part_prev);  // previous = current
-    // on the state stream, behind the flag passes that still write the old arrays (and off the fork-choice stream)
-    // The array that becomes "current" was "previous": its last readers and writers are the flag passes of earlier steps, on
-    // this stream; synchronous readers on the engine's stream (pe_participation_get, pe_ffg_balances) complete before they
-    // return.  So the memset needs no ordering against the engine's stream -- unless a flag pass had to be placed there
-    // (state_stream_begin's fall-back when its fork event could not be recorded): then this rotation forks behind it.
-    hipStream_t ss;
-    if (h->state_work_on_main) {
-        h->state_work_on_main = false;
-        ss = state_stream_begin(h);
-    } else {
-        ss = state_stream_unordered(h);
-    }
-    if (h->n_val) HIP_TRY(h, hipMemsetAsync(h->d_part_cur.p, 0, (h->n_val + 3) & ~uint64_t(3), ss));  // current = 0
-    return PE_OK;
-}
-
-int pe_state_set_validators(pe_engine* h, uint64_t n, const uint64_t* effective_balance, const uint8_t* flags)
-{
-    if (!h || (n && (!effective_balance || !flags))) return PE_ERR_INVALID_ARG;
-    if (n != h->n_val) return fail(h, PE_ERR_INVALID_ARG, "pe_state_set_validators: n differs from the registry size");
-    PE_TRY(enter(h));
-    std::vector<uint16_t> incr(n);
-    const uint64_t inc = h->cfg.effective_balance_increment;
-    for (uint64_t i = 0; i < n; ++i) {
-        const uint64_t q = effective_balance[i] / inc;
-        if (q > 0xFFFF) return fail(h, PE_ERR_INVALID_ARG, "effective_balance / increment exceeds 65535");
-        incr[i] = (uint16_t)q;
-    }
-    const size_t n4 = (n + 3) & ~size_t(3);
-    HIP_TRY(h, h->d_sbalance.ensure(std::max<size_t>(64, n4 * 8)));
-    HIP_TRY(h, h->d_sflags.ensure(std::max<size_t>(64, n4)));
-    HIP_TRY(h, hipMemcpyAsync(h->d_sbalance.p, effective_balance, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_sflags.p, flags, n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_incr.p, incr.data(), n * 2, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->state_view_set = true;
-    return PE_OK;
-}
-
-// Read-back of the working-state view (checkpoint / resume): *out_is_set = 0 while the view still mirrors the registry.
-int pe_state_get_validators(pe_engine* h, uint64_t n, uint64_t* out_effective_balance, uint8_t* out_flags, int* out_is_set)
-{
-    if (!h || !out_is_set || (n && (!out_effective_balance || !out_flags))) return PE_ERR_INVALID_ARG;
-    if (n != h->n_val) return fail(h, PE_ERR_INVALID_ARG, "pe_state_get_validators: n differs from the registry size");
-    PE_TRY(enter(h));
-    *out_is_set = h->state_view_set ? 1 : 0;
-    if (n && h->d_sbalance.p && h->d_sflags.p) {
-        HIP_TRY(h, hipMemcpyAsync(out_effective_balance, h->d_sbalance.p, n * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(out_flags, h->d_sflags.p, n, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    return PE_OK;
-}
-
-// The committee tables the handle holds: epochs first (out_epochs NULL: count only), then one table at a time.
-int pe_get_committee_epochs(pe_engine* h, uint64_t* out_epochs, uint32_t cap, uint32_t* out_n)
-{
-    if (!h || !out_n) return PE_ERR_INVALID_ARG;
-    PE_TRY(enter(h));
-    uint32_t k = 0;
-    for (auto& t : h->tables) {
-        if (!t.n_committees) continue;
-        if (out_epochs) {
-            if (k >= cap) return fail(h, PE_ERR_CAPACITY, "pe_get_committee_epochs: more tables than cap");
-            out_epochs[k] = t.epoch;
-        }
-        ++k;
-    }
-    *out_n = k;
-    return PE_OK;
-}
-int pe_get_committees(pe_engine* h, uint64_t epoch, uint32_t* out_n_committees, uint32_t* out_offsets,
-                      uint32_t offsets_cap, uint32_t* out_members, uint64_t members_cap)
-{
-    if (!h || !out_n_committees) return PE_ERR_INVALID_ARG;
-    PE_TRY(enter(h));
-    CommitteeTable* t = find_table(h, epoch);
-    if (!t) return fail(h, PE_ERR_NO_COMMITTEES, "no committee table for the epoch");
-    *out_n_committees = t->n_committees;
-    if (out_offsets) {
-        if (offsets_cap < t->n_committees + 1) return fail(h, PE_ERR_CAPACITY, "pe_get_committees: offsets_cap too small");
-        memcpy(out_offsets, t->offsets.data(), 4ull * (t->n_committees + 1));
-    }
-    if (out_members) {  // the members live on the device (a table computed by pe_compute_committees never left it)
-        const uint64_t total = t->offsets.empty() ? 0 : t->offsets.back();
-        if (members_cap < total) return fail(h, PE_ERR_CAPACITY, "pe_get_committees: members_cap too small");
-        if (total) {
-            HIP_TRY(h, hipMemcpyAsync(out_members, t->d_members.p, 4ull * total, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-        }
-    }
-    return PE_OK;
-}
-
-int pe_ffg_balances(pe_engine* h, uint64_t out[3])
-{
-    if (!h || !out) return PE_ERR_INVALID_ARG;
-    PE_TRY(enter(h));
-    OutBlock ob(h);
-    const size_t off = ob.alloc(8ull * 3 * 256);
-    PE_TRY(ob.ensure());
-    uint32_t blocks = 0;
-    if (h->n_val) {
-        blocks = launch_ffg_balances(h->stream, h->d_sbalance.as<uint64_t>(), h->d_sflags.as<uint8_t>(),
-                                     h->d_part_cur.as<uint8_t>(), h->d_part_prev.as<uint8_t>(), h->n_val,
-                                     ob.dev<uint64_t>(off));
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, ob.download());
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    uint64_t s[3] = {0, 0, 0};
-    const uint64_t* p = ob.host<uint64_t>(off);
-    for (uint32_t b = 0; b < blocks; ++b)
-        for (int k = 0; k < 3; ++k) s[k] += p[3 * b + k];
-    for (int k = 0; k < 3; ++k) out[k] = std::max<uint64_t>(h->cfg.effective_balance_increment, s[k]);  // get_total_balance
-    return PE_OK;
 }
 
 }  // extern "C"

@@ -1,5 +1,8 @@
-// engine_epoch.cpp -- the epoch boundary over the resident registry: the registry-wide functions of the reference that
-// sit there and whose callers' text it holds.
+// engine_epoch.cpp -- the working-state view and the epoch boundary over the resident registry: the registry-wide functions
+// of the reference that sit there and whose callers' text it holds.
+//   pe_state_set_validators / _get  the view itself: effective balances and flags of the state being processed
+//   pe_participation_set / _get / _rotate   current / previous_epoch_participation (pe:739-742), rotated at the boundary
+//   pe_ffg_balances                 total active / previous-target / current-target balance (k_ffg_balances)
 //   pe_registry_set_epochs / _get   Validator.activation_epoch / exit_epoch (pe:43-44), two u64 arrays in device memory
 //   pe_active_set                   get_active_validator_indices(state, epoch) with its length (pe:467, pe:1234, pe:1267) and
 //                                   get_total_active_balance (pe:1268): k_active_compact (shuffle_kernels.hip)
@@ -42,6 +45,107 @@ int materialise_state_view(pe_engine* h)
 }  // namespace posevo
 
 extern "C" {
+
+int pe_participation_set(pe_engine* h, int which, const uint8_t* flags, uint64_t n)
+{
+    if (!h || !flags || n != h->n_val || (which != 0 && which != 1)) return PE_ERR_INVALID_ARG;
+    PE_TRY(enter(h));
+    DevBuf& b = which ? h->d_part_prev : h->d_part_cur;
+    HIP_TRY(h, hipMemcpyAsync(b.p, flags, n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return PE_OK;
+}
+int pe_participation_get(pe_engine* h, int which, uint8_t* out_flags, uint64_t n)
+{
+    if (!h || !out_flags || n != h->n_val || (which != 0 && which != 1)) return PE_ERR_INVALID_ARG;
+    PE_TRY(enter(h));
+    DevBuf& b = which ? h->d_part_prev : h->d_part_cur;
+    HIP_TRY(h, hipMemcpyAsync(out_flags, b.p, n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return PE_OK;
+}
+int pe_participation_rotate(pe_engine* h)
+{
+    if (!h) return PE_ERR_INVALID_ARG;
+    (void)hipSetDevice(h->device);
+    std::swap(h->d_part_cur, h->d_part_prev);  // previous = current
+    // on the state stream, behind the flag passes that still write the old arrays (and off the fork-choice stream)
+    // The array that becomes "current" was "previous": its last readers and writers are the flag passes of earlier steps, on
+    // this stream; synchronous readers on the engine's stream (pe_participation_get, pe_ffg_balances) complete before they
+    // return.  So the memset needs no ordering against the engine's stream -- unless a flag pass had to be placed there
+    // (state_stream_begin's fall-back when its fork event could not be recorded): then this rotation forks behind it.
+    hipStream_t ss;
+    if (h->state_work_on_main) {
+        h->state_work_on_main = false;
+        ss = state_stream_begin(h);
+    } else {
+        ss = state_stream_unordered(h);
+    }
+    if (h->n_val) HIP_TRY(h, hipMemsetAsync(h->d_part_cur.p, 0, (h->n_val + 3) & ~uint64_t(3), ss));  // current = 0
+    return PE_OK;
+}
+
+int pe_state_set_validators(pe_engine* h, uint64_t n, const uint64_t* effective_balance, const uint8_t* flags)
+{
+    if (!h || (n && (!effective_balance || !flags))) return PE_ERR_INVALID_ARG;
+    if (n != h->n_val) return fail(h, PE_ERR_INVALID_ARG, "pe_state_set_validators: n differs from the registry size");
+    PE_TRY(enter(h));
+    std::vector<uint16_t> incr(n);
+    const uint64_t inc = h->cfg.effective_balance_increment;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t q = effective_balance[i] / inc;
+        if (q > 0xFFFF) return fail(h, PE_ERR_INVALID_ARG, "effective_balance / increment exceeds 65535");
+        incr[i] = (uint16_t)q;
+    }
+    const size_t n4 = (n + 3) & ~size_t(3);
+    HIP_TRY(h, h->d_sbalance.ensure(std::max<size_t>(64, n4 * 8)));
+    HIP_TRY(h, h->d_sflags.ensure(std::max<size_t>(64, n4)));
+    HIP_TRY(h, hipMemcpyAsync(h->d_sbalance.p, effective_balance, n * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_sflags.p, flags, n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_incr.p, incr.data(), n * 2, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->state_view_set = true;
+    return PE_OK;
+}
+
+// Read-back of the working-state view (checkpoint / resume): *out_is_set = 0 while the view still mirrors the registry.
+int pe_state_get_validators(pe_engine* h, uint64_t n, uint64_t* out_effective_balance, uint8_t* out_flags, int* out_is_set)
+{
+    if (!h || !out_is_set || (n && (!out_effective_balance || !out_flags))) return PE_ERR_INVALID_ARG;
+    if (n != h->n_val) return fail(h, PE_ERR_INVALID_ARG, "pe_state_get_validators: n differs from the registry size");
+    PE_TRY(enter(h));
+    *out_is_set = h->state_view_set ? 1 : 0;
+    if (n && h->d_sbalance.p && h->d_sflags.p) {
+        HIP_TRY(h, hipMemcpyAsync(out_effective_balance, h->d_sbalance.p, n * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(out_flags, h->d_sflags.p, n, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    return PE_OK;
+}
+
+int pe_ffg_balances(pe_engine* h, uint64_t out[3])
+{
+    if (!h || !out) return PE_ERR_INVALID_ARG;
+    PE_TRY(enter(h));
+    OutBlock ob(h);
+    const size_t off = ob.alloc(8ull * 3 * 256);
+    PE_TRY(ob.ensure());
+    uint32_t blocks = 0;
+    if (h->n_val) {
+        blocks = launch_ffg_balances(h->stream, h->d_sbalance.as<uint64_t>(), h->d_sflags.as<uint8_t>(),
+                                     h->d_part_cur.as<uint8_t>(), h->d_part_prev.as<uint8_t>(), h->n_val,
+                                     ob.dev<uint64_t>(off));
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, ob.download());
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    uint64_t s[3] = {0, 0, 0};
+    const uint64_t* p = ob.host<uint64_t>(off);
+    for (uint32_t b = 0; b < blocks; ++b)
+        for (int k = 0; k < 3; ++k) s[k] += p[3 * b + k];
+    for (int k = 0; k < 3; ++k) out[k] = std::max<uint64_t>(h->cfg.effective_balance_increment, s[k]);  // get_total_balance
+    return PE_OK;
+}
 
 int pe_registry_set_epochs(pe_engine* h, uint64_t n, const uint64_t* activation_epoch, const uint64_t* exit_epoch)
 {

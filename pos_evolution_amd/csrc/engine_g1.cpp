@@ -523,13 +523,7 @@ int pe_aggregate_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t 
     const uint32_t total = offsets[n_groups];
     for (uint32_t g = 0; g < n_groups; ++g)
         if (offsets[g + 1] < offsets[g]) return fail(h, PE_ERR_INVALID_ARG, "offsets not monotone");
-    auto on_device = [](const void* p) {
-        hipPointerAttribute_t pa;
-        if (p && hipPointerGetAttributes(&pa, p) == hipSuccess) return pa.type == hipMemoryTypeDevice;
-        (void)hipGetLastError();
-        return false;
-    };
-    const bool idx_dev = index && on_device(index);
+    const bool idx_dev = mem_kind(index) == MemKind::Device;
     if (index && !idx_dev) {
         for (uint32_t j = 0; j < total; ++j)
             if (index[j] >= n) return fail(h, PE_ERR_INVALID_ARG, "signature index out of range");
@@ -538,7 +532,7 @@ int pe_aggregate_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t 
     }
     hipStream_t s = h->stream;
     // wire bytes: in place when they lie in device memory at a 16-byte boundary, else through the engine's scratch
-    const bool sig_dev = on_device(signatures96);
+    const bool sig_dev = mem_kind(signatures96) == MemKind::Device;
     const uint8_t* d_in = signatures96;
     if (!(sig_dev && (reinterpret_cast<uintptr_t>(signatures96) & 15) == 0)) {
         HIP_TRY(h, h->d_tmp_be.ensure(std::max<size_t>(96, 96ull * n)));
@@ -659,12 +653,7 @@ int pe_aggregate_signed(pe_engine* h, const pe_attestation* atts, uint32_t n, co
         if (sig_batch_holds(h, h->cur)) PE_TRY(sig_batch_flush(h));
         if (A.leg_used) HIP_TRY(h, hipStreamWaitEvent(h->stream, A.ev_leg, 0));
     }
-    bool sig_on_device = false;
-    {
-        hipPointerAttribute_t pa;
-        if (hipPointerGetAttributes(&pa, signatures) == hipSuccess) sig_on_device = pa.type == hipMemoryTypeDevice;
-        else (void)hipGetLastError();
-    }
+    const bool sig_on_device = mem_kind(signatures) == MemKind::Device;
     // Signatures in HOST memory are brought in during the call, in front of the grouping on the engine's stream: the leg below
     // may be deferred past this call's return (a streaming step holds it back until the next aggregate), and a caller is free
     // to refill a host buffer per step -- as with bits_arena.  Device-resident signatures are read where the leg

@@ -3,14 +3,16 @@
 // include/posevo.h); the device-side interface is kernels.h.
 //
 //   engine_core.cpp    lifecycle, error strings, completion of batch calls, pipelines, profiling hooks
-//   engine_store.cpp   the fork-choice store (pe:889-901) and its handlers, registry, committee tables, get_head
+//   engine_store.cpp   the fork-choice store (pe:889-901) and its handlers, registry, committee tables (set, compute, read
+//                      back), get_head
 //   engine_attest.cpp  on_attestation / process_attestation / aggregation over host rows
 //   engine_resident.cpp the same path over rows resident in device memory (grouping + validation on the device)
 //   engine_g1.cpp      G1 / G2 sums over caller-chosen groups, BLSPubkey / BLSSignature wire formats
 //   engine_dist.cpp    multi-GPU exchange: RCCL owned by the engine, function-table collectives
 //   engine_slash.cpp   slashing detection: the per-validator vote history and its scan (double and surround votes)
-//   engine_epoch.cpp   the epoch boundary: the active set, proposer sampling and the effective-balance hysteresis over the
-//                      resident registry
+//   engine_epoch.cpp   the working-state view (validators, participation flags, FFG balances) and the epoch boundary over
+//                      it: the active set, proposer sampling and the effective-balance hysteresis
+// The row rules host and device share (bits inside the arena, committee position) are att_row.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -35,6 +37,7 @@
 
 #include "../../include/posevo.h"
 #include "../../include/posevo_profile.h"
+#include "att_row.h"
 #include "kernels.h"
 
 namespace posevo {
@@ -783,6 +786,18 @@ struct Resolved {
     uint32_t size = 0;       // committee length
     uint32_t block_idx = 0;  // beacon_block_root
 };
+// The committee (a.slot, a.index) names in table t (att_row.h): table / pos / size are filled where the position exists.
+// Which of `exists` and `index_over` refuses the row, and with what, is the caller's rule.
+inline CommitteePos resolve_committee(const pe_engine* h, CommitteeTable* t, const pe_attestation& a, Resolved* out)
+{
+    const CommitteePos cp = att_committee_pos(t->n_committees, h->cfg.slots_per_epoch, a.slot, a.index);
+    if (cp.exists) {
+        out->table = t;
+        out->pos = cp.pos;
+        out->size = t->offsets[cp.pos + 1] - t->offsets[cp.pos];
+    }
+    return cp;
+}
 
 // Per-call memo for the host-side walks of a batch: consecutive rows mostly name the same few roots.
 struct BatchMemo {
@@ -816,7 +831,11 @@ struct BatchMemo {
 int32_t validate_for_fork_choice(pe_engine* h, const pe_attestation& a, Resolved* out, BatchMemo* memo);
 // rows handed over with PE_BITS_RESIDENT: which group of the last pe_aggregate is this row (engine_attest.cpp)
 bool find_resident(const pe_engine* h, const pe_attestation& a, uint32_t* g_out, uint32_t guess);
-bool bits_on_device(const uint8_t* bits_arena);
+// Where a caller's pointer lives (engine_resident.cpp).  Pageable is also the answer for anything the runtime does not know.
+enum class MemKind { Pageable, Pinned, Device };
+MemKind mem_kind(const void* p);
+// The handlers and pe_get_indexed_attestations re-pack the caller's bits on the host: device memory would fault there.
+inline bool bits_on_device(const uint8_t* bits_arena) { return mem_kind(bits_arena) == MemKind::Device; }
 // slashing detection (engine_slash.cpp): drop every record and table, keep the allocation | free it
 int slasher_reset(pe_engine* h);
 void slasher_release(pe_engine* h);

@@ -180,14 +180,15 @@ int plan_error_to_status(pe_engine* h, uint32_t err, const char* who)
 
 }  // namespace
 
-bool rows_on_device(const void* p)
+MemKind mem_kind(const void* p)
 {
-    if (!p || p == (const void*)PE_ROWS_RESIDENT) return false;
     hipPointerAttribute_t pa;
-    if (hipPointerGetAttributes(&pa, p) == hipSuccess) return pa.type == hipMemoryTypeDevice;
+    if (p && hipPointerGetAttributes(&pa, p) == hipSuccess)
+        return pa.type == hipMemoryTypeDevice ? MemKind::Device : pa.type == hipMemoryTypeHost ? MemKind::Pinned : MemKind::Pageable;
     (void)hipGetLastError();  // plain host memory is "invalid value" to older runtimes: not an error here
-    return false;
+    return MemKind::Pageable;
 }
+bool rows_on_device(const void* p) { return p && p != (const void*)PE_ROWS_RESIDENT && mem_kind(p) == MemKind::Device; }
 
 BlockTableDev block_table_dev(const pe_engine* h)
 {
@@ -258,16 +259,7 @@ int aggregate_resident(pe_engine* h, const pe_attestation* d_rows, uint32_t n, c
     memset(plan_host, 0, sizeof(AttPlan));
     plan_host->error = 0xFFFFFFFFu;  // "k_att_plan has not run": a completion that finds it reports a failed launch
     // ---- device ----
-    int arena_kind = 0;  // 0 pageable host, 1 pinned host, 2 device
-    if (arena_len) {
-        hipPointerAttribute_t pa;
-        if (hipPointerGetAttributes(&pa, bits_arena) == hipSuccess) {
-            if (pa.type == hipMemoryTypeDevice) arena_kind = 2;
-            else if (pa.type == hipMemoryTypeHost) arena_kind = 1;
-        } else {
-            (void)hipGetLastError();
-        }
-    }
+    const MemKind arena_kind = arena_len ? mem_kind(bits_arena) : MemKind::Pageable;
     hipStream_t ms = h->stream;
     // Fork-choice launches held back by the PREVIOUS step of a streaming caller go out pairwise with this aggregate's row
     // kernels (engine_pair.cpp).  Anything else that is held -- launches of THIS pipeline (they read the scratch this
@@ -292,16 +284,16 @@ int aggregate_resident(pe_engine* h, const pe_attestation* d_rows, uint32_t n, c
         ~Unwind() { if (armed) { h->rr.valid = false; if (h->deferred.size() > keep) h->deferred.resize(keep); } }
     } unwind{h, deferred_before};
     bool ingest_copies = false;
-    if (arena_kind == 0) {
+    if (arena_kind == MemKind::Pageable) {
         memcpy(st.host<uint8_t>(off_arena), bits_arena, arena_len);
         memset(st.host<uint8_t>(off_arena) + arena_len, 0, pad_at + 32 - arena_len);
         HIP_TRY(h, st.upload());
     } else if (arena_len) {  // bytes [arena_len, pad_at) may keep old bits: they lie inside the last dword pair only when
                              // arena_len is not a multiple of 4, and then belong to no member (masked by n_bits)
         // device memory at a 16-byte boundary: k_att_ingest brings the bits in itself (no copy command in the chain)
-        if (arena_kind == 2 && (reinterpret_cast<uintptr_t>(bits_arena) & 15) == 0 && n > 0) ingest_copies = true;
+        if (arena_kind == MemKind::Device && (reinterpret_cast<uintptr_t>(bits_arena) & 15) == 0 && n > 0) ingest_copies = true;
         else HIP_TRY(h, hipMemcpyAsync(st.dev<uint8_t>(off_arena), bits_arena, arena_len,
-                                       arena_kind == 2 ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ms));
+                                       arena_kind == MemKind::Device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ms));
     }
     lap.mark("ragg.2_bits");
     uint32_t* cnt_tab = RS.tab.as<uint32_t>() + RS.tab_size;

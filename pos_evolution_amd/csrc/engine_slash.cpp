@@ -131,7 +131,7 @@ int pe_slasher_ingest(pe_engine* h, const pe_attestation* atts, uint32_t n, cons
         if (resident) {
             if (!find_resident(h, a, &res_group[i], i))
                 return fail(h, PE_ERR_INVALID_ARG, "PE_BITS_RESIDENT: row is not a row of the last pe_aggregate");
-        } else if (a.n_bits > 0x7FFFFFFFu || (uint64_t)a.bits_offset + ((uint64_t)a.n_bits + 7) / 8 > arena_len) {
+        } else if (!att_bits_in_arena(a.bits_offset, a.n_bits, arena_len)) {
             return fail(h, PE_ERR_INVALID_ARG, "attestation bits exceed the arena");
         }
         int32_t s = PE_ATT_OK;
@@ -140,21 +140,15 @@ int pe_slasher_ingest(pe_engine* h, const pe_attestation* atts, uint32_t n, cons
         else if (a.target_epoch + H <= W) s = PE_SLASH_TOO_OLD;
         else {
             CommitteeTable* t = find_table(h, a.target_epoch);
+            Resolved c;
             if (!t || !t->is_partition || t->n_val_at_load != h->n_val || !t->d_inv_comm.p) s = PE_ATT_NO_COMMITTEE_TABLE;
+            else if (!resolve_committee(h, t, a, &c).exists) s = PE_ATT_COMMITTEE_INDEX_OUT_OF_RANGE;
+            else if (a.n_bits < c.size) s = PE_ATT_BITS_LENGTH_MISMATCH;
             else {
-                const uint64_t cps = t->n_committees / h->cfg.slots_per_epoch;
-                const uint64_t pos = (a.slot % h->cfg.slots_per_epoch) * cps + a.index;
-                if (pos >= t->n_committees) s = PE_ATT_COMMITTEE_INDEX_OUT_OF_RANGE;
-                else {
-                    const uint32_t size = t->offsets[pos + 1] - t->offsets[pos];
-                    if (a.n_bits < size) s = PE_ATT_BITS_LENGTH_MISMATCH;
-                    else {
-                        acc[i] = {t, (uint32_t)pos, size, 0};
-                        if (std::find(tables.begin(), tables.end(), t) == tables.end()) tables.push_back(t);
-                        if (!resident && !dev_bits) stage_bits += (size + 7) / 8;
-                        ++n_pass;
-                    }
-                }
+                acc[i] = {t, c.pos, c.size, 0};
+                if (std::find(tables.begin(), tables.end(), t) == tables.end()) tables.push_back(t);
+                if (!resident && !dev_bits) stage_bits += (c.size + 7) / 8;
+                ++n_pass;
             }
         }
         status[i] = s;

@@ -5,6 +5,8 @@
 // arrays (latest message, effective balance, flags, pubkey).  Handlers follow the reference line by line where it
 // defines them (on_tick pe:934-955, on_block pe:986-1036, should_update_justified_checkpoint pe:1046-1061,
 // on_attester_slashing pe:1447-1461) and SURVEY.md Appendix A where it only calls them (get_ancestor A.2).
+// The committee tables live here too: pe_set_committees / pe_compute_committees and their read-back (pe_get_committee_epochs,
+// pe_get_committees).
 #include "engine_internal.h"
 
 using namespace posevo;
@@ -661,6 +663,46 @@ int pe_set_committees(pe_engine* h, uint64_t epoch, uint32_t n_committees, const
     t->offsets.assign(offsets, offsets + n_committees + 1);
     t->is_partition = partition;
     t->stamp = ++h->table_stamp;
+    return PE_OK;
+}
+
+// The committee tables the handle holds: epochs first (out_epochs NULL: count only), then one table at a time.
+int pe_get_committee_epochs(pe_engine* h, uint64_t* out_epochs, uint32_t cap, uint32_t* out_n)
+{
+    if (!h || !out_n) return PE_ERR_INVALID_ARG;
+    PE_TRY(enter(h));
+    uint32_t k = 0;
+    for (auto& t : h->tables) {
+        if (!t.n_committees) continue;
+        if (out_epochs) {
+            if (k >= cap) return fail(h, PE_ERR_CAPACITY, "pe_get_committee_epochs: more tables than cap");
+            out_epochs[k] = t.epoch;
+        }
+        ++k;
+    }
+    *out_n = k;
+    return PE_OK;
+}
+int pe_get_committees(pe_engine* h, uint64_t epoch, uint32_t* out_n_committees, uint32_t* out_offsets,
+                      uint32_t offsets_cap, uint32_t* out_members, uint64_t members_cap)
+{
+    if (!h || !out_n_committees) return PE_ERR_INVALID_ARG;
+    PE_TRY(enter(h));
+    CommitteeTable* t = find_table(h, epoch);
+    if (!t) return fail(h, PE_ERR_NO_COMMITTEES, "no committee table for the epoch");
+    *out_n_committees = t->n_committees;
+    if (out_offsets) {
+        if (offsets_cap < t->n_committees + 1) return fail(h, PE_ERR_CAPACITY, "pe_get_committees: offsets_cap too small");
+        memcpy(out_offsets, t->offsets.data(), 4ull * (t->n_committees + 1));
+    }
+    if (out_members) {  // the members live on the device (a table computed by pe_compute_committees never left it)
+        const uint64_t total = t->offsets.empty() ? 0 : t->offsets.back();
+        if (members_cap < total) return fail(h, PE_ERR_CAPACITY, "pe_get_committees: members_cap too small");
+        if (total) {
+            HIP_TRY(h, hipMemcpyAsync(out_members, t->d_members.p, 4ull * total, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+        }
+    }
     return PE_OK;
 }
 

@@ -131,6 +131,10 @@ class _Batch:
         return self.rows
 
 
+# the row whose position (slot % SPE) * CPS + index is 2^64 exactly: 0 in 64-bit arithmetic, committee 0 -- which exists
+WRAP_SLOT_IN_EPOCH, WRAP_INDEX, WRAP_TAG = 3, 2**64 - 6, "index = 2^64 - 6: the position's 64-bit sum wraps to 0"
+assert WRAP_SLOT_IN_EPOCH * CPS + WRAP_INDEX == 2**64
+
 CJ_NAME, PJ_NAME = "A32", "g"  # current_justified = (1, A32), previous_justified = (0, g): they differ
 
 
@@ -265,7 +269,15 @@ def _state_matrix(w, S):
     s, i = take(cur_free, prev_free)
     other = cur if s // SPE == prev else prev
     plain("target epoch of the other admitted epoch (pe:725)", s, i, t_epoch=other)
-    return dict(name=f"state.slot {S}", time=S * 12, state=sc, rows=b.done(), want_status={0, 7},
+    # committee index again (last, so that the rows above keep their numbers): an index no 32-bit committee count reaches --
+    # either side of 2^32 - 1, where the device keeps it out of the position's sum, and two that a 64-bit sum would wrap: at
+    # slot % 32 = 3 with two committees per slot, 2^64 - 6 wraps onto committee 0
+    wrap_slot = max(s for s in range(S - SPE, S) if s % SPE == WRAP_SLOT_IN_EPOCH)
+    plain("index = 2^32 - 2", S - 6, 2**32 - 2)
+    plain("index = 2^32 - 1", S - 6, 2**32 - 1)
+    plain(WRAP_TAG, wrap_slot, WRAP_INDEX)
+    plain("index = 2^64 - 1", S - 6, 2**64 - 1)
+    return dict(name=f"state.slot {S}", time=S * 12, state=sc, rows=b.done(), want_status={0, 7, 9},
                 want_pstatus={0, 1, 2, 9, 13, 14})
 
 

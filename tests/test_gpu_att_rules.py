@@ -177,6 +177,31 @@ def test_boundary_matrix_equals_the_model(world, si, route):
         e.close()
 
 
+def wrap_rows(w):
+    """-> (scenario, [a plain valid row, the row whose position wraps a 64-bit sum onto committee 0]) of state.slot 69."""
+    sc = next(sc for sc in w.scenarios if sc["name"] == "state.slot 69")
+    return sc, [next(r for r in sc["rows"] if r["tag"] == tag) for tag in ("valid", C.WRAP_TAG)]
+
+
+def test_indexed_attestation_of_an_index_that_wraps_a_64_bit_sum(world):
+    """pe_get_indexed_attestations (A.6) asks only for the position to exist: (slot % 32) * 2 + (2^64 - 6) at slot % 32 = 3
+    is 2^64, not committee 0."""
+    w = world
+    sc, rows = wrap_rows(w)
+    cc = C.committee_ctx(sc["time"], resident=False)
+    want = [M.INDEX_RANGE if M.flat_committee(r, cc) >= C.CPS * C.SPE else M.OK for r in rows]
+    assert want == [M.OK, M.INDEX_RANGE]
+    e = _engine(w, sc)
+    try:
+        status, off, idx = e.get_indexed_attestations(packed=_pack(rows))
+        assert [int(x) for x in status] == want
+        com = w.members_of(rows[0]["target"][0], M.flat_committee(rows[0], cc))
+        assert list(off) == [0, rows[0]["popcount"], rows[0]["popcount"]]
+        assert [int(v) for v in idx] == sorted(v for v, b in zip(com, rows[0]["bits"]) if b)
+    finally:
+        e.close()
+
+
 # ---------------------------------------------------------------- A.6 beyond 2048 members
 @pytest.fixture(scope="module")
 def big_engine():

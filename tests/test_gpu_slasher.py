@@ -206,6 +206,30 @@ def test_window(engine_factory):
     p.check_records()
 
 
+def test_an_index_that_wraps_a_64_bit_sum_names_no_committee(engine_factory):
+    """The boundary matrix's own world (tests/att_rules_cases.py: 32 slots per epoch, two committees per slot): the position
+    (slot % 32) * 2 + (2^64 - 6) at slot % 32 = 3 is 2^64, not committee 0 -- the row is refused and leaves no record."""
+    from types import SimpleNamespace
+
+    from tests import att_rules_cases as C
+    from tests import att_rules_model as M
+    from tests.test_gpu_att_rules import _pack, wrap_rows
+
+    w = C.world()
+    sc, rows = wrap_rows(w)
+    cc = C.committee_ctx(sc["time"], resident=False)
+    want = [M.INDEX_RANGE if M.flat_committee(r, cc) >= C.CPS * C.SPE else M.OK for r in rows]
+    assert want == [M.OK, M.INDEX_RANGE]
+    epoch = rows[0]["target"][0]
+    assert all(r["target"][0] == epoch for r in rows)
+    comm = SimpleNamespace(offsets=np.arange(0, C.N_VAL + 1, C.SIZE, dtype=np.uint32),
+                           members=np.array([v for c in w.committees[epoch] for v in c], dtype=np.uint32))
+    p = Pair(engine_factory, C.N_VAL, 4, 16, {epoch: comm}, spe=C.SPE)
+    status, ev, _ = p.ingest(*_pack(rows), epoch)   # (and equal to the slasher's own model)
+    assert status.tolist() == want and len(ev) == 0
+    p.check_records()
+
+
 def test_table_full(engine_factory):
     n_val = 32
     comm = flat_comm(n_val, 4)
