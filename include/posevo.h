@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define PE_ABI_VERSION 10
+#define PE_ABI_VERSION 11
 
 typedef struct pe_engine pe_engine;
 
@@ -773,7 +773,9 @@ int pe_aggregate_exchange(pe_engine* h, pe_attestation* out_atts, uint32_t* out_
  * attestations the node already hands over.  Per validator and per target epoch of a window of history_epochs epochs
  * (W - H, W] it keeps the FIRST AttestationData the validator attested (in hand-over order), and per epoch the table of the
  * distinct AttestationData recorded for it (128 bytes each, compared exactly; at most max_data_per_epoch).  A record names
- * its data as (target_epoch, id).  Device memory: 12 * history_epochs bytes per validator.
+ * its data as (target_epoch, id); ids count the data of an epoch in order of first appearance.  Device memory: 12 *
+ * history_epochs bytes per validator, and ~136-140 * history_epochs * max_data_per_epoch bytes for the data tables of the
+ * device-row form.
  *
  * pe_slasher_enable   (pe:1411-1415: every validator "eventually recognises equivocations" in its own view) allocates the
  *                     history for the registry as loaded (pe_set_validators first; a registry of another size afterwards:
@@ -800,6 +802,19 @@ int pe_aggregate_exchange(pe_engine* h, pe_attestation* out_atts, uint32_t* out_
  *                     on_attester_slashing with attesting_indices = [v] on both sides (pe:1459-1461), exact whatever cap is.
  *                     Rows are host memory; bits host, pinned or device memory, or PE_BITS_RESIDENT with rows of the last
  *                     pe_aggregate's out_atts.  Synchronous; inside a pipeline it first completes the outstanding work.
+ *                     ROWS IN DEVICE MEMORY:
+ *                       pe_slasher_ingest(h, PE_ROWS_RESIDENT, cap_rows, PE_BITS_RESIDENT, 0, current_epoch, flags, status, ...)
+ *                     ingests every group of the last pe_aggregate over rows in device memory, in group order, as the host-row
+ *                     call over that aggregate's out_atts would: same statuses, evidence, records and data ids (the two forms
+ *                     mix on one handle and continue one sequence of ids).  The host reads nothing of the rows.  status holds
+ *                     cap_rows entries; those past the groups formed read 0; fewer than groups: PE_ERR_CAPACITY.  Any other
+ *                     bits_arena: PE_ERR_INVALID_ARG.  No valid resident aggregate, or the store's clock / committee tables
+ *                     changed since it: PE_ERR_STATE, as for the handlers; so is a handle with pe_dist_init* active.  An
+ *                     aggregate that failed ingests nothing and returns its error.  A group whose target epoch is >= 2^32 - 2
+ *                     or whose source epoch is >= 2^32 - 1 fails the whole call (PE_ERR_INVALID_ARG).  A failing call changes
+ *                     nothing.  RESTRICTION of this form: committees are the ones the aggregate resolved, against the tables
+ *                     of the store's current and previous epoch only -- after the window statuses, a group with an older
+ *                     target epoch reads PE_ATT_NO_COMMITTEE_TABLE even where a table for it is loaded.
  * pe_slasher_get_data     the AttestationData behind (target_epoch, id): the leading 128 bytes of *out, the rest zero.
  * pe_slasher_get_records  the records of one target epoch: source epoch and data id per validator, 0xFFFFFFFF = none
  *                         (parity tests, checkpoint).  An epoch outside the window reads as empty. */

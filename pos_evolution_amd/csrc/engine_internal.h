@@ -441,6 +441,14 @@ struct pe_engine {
             std::unordered_map<std::string, uint32_t> id_of;
         };
         std::vector<EpochData> epochs;
+        // The same tables in device memory, for rows that lie there (PE_ROWS_RESIDENT; kernels.h, SlashRowsArgs).  ONE side is
+        // current at a time: `on_device` says which; the other one is rebuilt from it when the route changes (to_device /
+        // to_host, engine_slash.cpp) -- a handle that keeps to one route never builds the other side.
+        bool on_device = false;
+        uint32_t tab_size = 0;               // T: entries of a slot's open-addressing table, a power of two >= 2 D
+        DevBuf d_data, d_count, d_tab;       // u8[H][D][128] | u32[H] | u32[H][T]
+        DevBuf d_work;                       // the scratch of one device-row call
+        std::vector<uint32_t> dev_count;     // host mirror of d_count while the device side is current
     } slasher;
 
     // ---- profiling ----
@@ -878,6 +886,11 @@ int aggregate_resident(pe_engine* h, const pe_attestation* d_rows, uint32_t n, c
 // the pieces pe_aggregate_exchange packs: the resident aggregate's groups, unions and the caller's rows
 struct ResidentParts { const void* rows; const AttGroup* grp; const AttPlan* plan; const uint32_t* res_bits; const uint32_t* res_info; uint32_t n_in; };
 int resident_parts(pe_engine* h, ResidentParts* out);
+// PE_ROWS_RESIDENT: PE_ERR_STATE unless a resident aggregate over device rows is valid and the store's clock and committee
+// tables are the ones it resolved against
+int resident_precheck(pe_engine* h, const char* who);
+// AttPlan::error / last_error (-pe_status, or a row refused on the device) as the call's return value
+int plan_error_to_status(pe_engine* h, uint32_t err, const char* who);
 // the device-side plan (group count, error word) of the last aggregate over rows in device memory
 int resident_plan_dev(pe_engine* h, const AttPlan** out);
 // ... and its grouping lists: group g's member rows are member_row[ug[g].list_start .. + ug[g].n_atts)

@@ -165,6 +165,8 @@ uint32_t g1_target_slots(const pe_engine* h)
     return h->g1_target_slots ? h->g1_target_slots : G1_TARGET_LANES;
 }
 
+}  // namespace
+
 int plan_error_to_status(pe_engine* h, uint32_t err, const char* who)
 {
     switch (err) {
@@ -177,8 +179,6 @@ int plan_error_to_status(pe_engine* h, uint32_t err, const char* who)
                         "target epoch beyond 32 bits, committee index out of range or len(aggregation_bits) != len(committee))");
     }
 }
-
-}  // namespace
 
 MemKind mem_kind(const void* p)
 {
@@ -453,7 +453,7 @@ int resident_lists(pe_engine* h, const UnionGroup** ug, const uint32_t** member_
 }
 
 // ---------------------------------------------------------------- on_attestation x groups of the resident aggregate
-static int resident_precheck(pe_engine* h, const char* who)
+int resident_precheck(pe_engine* h, const char* who)
 {
     if (!h->rr.valid) return fail(h, PE_ERR_STATE, std::string(who) + ": PE_ROWS_RESIDENT without a pe_aggregate over rows in device memory on this handle");
     TablesDev now;

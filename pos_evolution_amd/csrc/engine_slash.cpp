@@ -4,9 +4,16 @@
 // (pe:1411-1415): the view is a per-validator history of the first vote per target epoch over a window of H epochs, in
 // device memory (kernels.h: epoch-major records), scanned by k_slash_scan (slash_kernels.hip).
 //
-// What runs on the host: the window, committee resolution of the rows and the de-duplication of AttestationData -- a hash
-// map per epoch over the batch's rows, so that the device sees (committee, bits, source, target, id) rows only.  That map
-// is the thing to move to the device when device-resident rows (PE_ROWS_RESIDENT) follow.
+// Two routes lead to that scan.  HOST ROWS: the host keeps the window, resolves the rows' committees and de-duplicates
+// AttestationData in a hash map per epoch, so that the device sees (committee, bits, source, target, id) rows only.
+// DEVICE ROWS (PE_ROWS_RESIDENT: the groups of the last pe_aggregate over rows in device memory): the host keeps the window
+// and reads nothing of the rows; the k_slash_rows_* kernels judge the groups, take the ids from per-slot tables in device
+// memory and write the scan's rows and lists (kernels.h, SlashRowsArgs).  Committees are the ones the aggregate resolved:
+// only groups of the store's current and previous epoch take part there.
+//
+// Both routes hand out ONE sequence of ids per epoch slot.  One side of the data tables is current at a time
+// (Slasher::on_device); a call of the other route first rebuilds its side from the current one (to_host: a download and
+// the maps again; to_device: an upload and k_slash_table_build), so a handle that keeps to one route never pays for the other.
 #include "engine_internal.h"
 
 using namespace posevo;
@@ -18,6 +25,8 @@ int slasher_reset(pe_engine* h)
     auto& sl = h->slasher;
     if (!sl.enabled) return PE_OK;
     for (auto& e : sl.epochs) { e.data.clear(); e.id_of.clear(); }
+    sl.on_device = false;  // both sides are empty; the device side is cleared when a call turns to it (to_device)
+    std::fill(sl.dev_count.begin(), sl.dev_count.end(), 0u);
     sl.have_window = false;
     sl.window = 0;
     HIP_TRY(h, hipMemsetAsync(sl.d_rec.p, 0, 8ull * sl.history * sl.n_val, h->stream));
@@ -32,7 +41,13 @@ void slasher_release(pe_engine* h)
     sl.d_ids.release();
     sl.d_counter.release();
     sl.d_evidence.release();
+    sl.d_data.release();
+    sl.d_count.release();
+    sl.d_tab.release();
+    sl.d_work.release();
     sl.epochs.clear();
+    sl.dev_count.clear();
+    sl.on_device = false;
     sl.enabled = false;
     sl.have_window = false;
 }
@@ -52,12 +67,207 @@ int advance_window(pe_engine* h, uint64_t w1)
             const uint64_t slot = (w1 - k) % H;
             sl.epochs[slot].data.clear();
             sl.epochs[slot].id_of.clear();
+            if (sl.on_device) {  // the slot's table goes with its records
+                sl.dev_count[slot] = 0;
+                HIP_TRY(h, hipMemsetAsync(sl.d_count.as<uint32_t>() + slot, 0, 4, h->stream));
+                HIP_TRY(h, hipMemsetAsync(sl.d_tab.as<uint32_t>() + slot * sl.tab_size, 0xFF, 4ull * sl.tab_size, h->stream));
+            }
             HIP_TRY(h, hipMemsetAsync(sl.d_rec.as<uint64_t>() + slot * sl.n_val, 0, 8ull * sl.n_val, h->stream));
         }
     }
     sl.have_window = true;
     sl.window = w1;
     return PE_OK;
+}
+
+// the device side becomes current: the host's data per slot go up, every slot's table is built from them
+int to_device(pe_engine* h)
+{
+    auto& sl = h->slasher;
+    if (sl.on_device) return PE_OK;
+    const uint32_t H = sl.history;
+    for (uint32_t slot = 0; slot < H; ++slot) {
+        const auto& ep = sl.epochs[slot];
+        sl.dev_count[slot] = (uint32_t)ep.data.size();
+        if (!ep.data.empty())
+            HIP_TRY(h, hipMemcpyAsync(sl.d_data.as<uint8_t>() + 128ull * slot * sl.max_data, ep.data.data(), 128ull * ep.data.size(),
+                                      hipMemcpyHostToDevice, h->stream));
+    }
+    HIP_TRY(h, hipMemcpyAsync(sl.d_count.p, sl.dev_count.data(), 4ull * H, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(sl.d_tab.p, 0xFF, 4ull * H * sl.tab_size, h->stream));
+    if (std::any_of(sl.dev_count.begin(), sl.dev_count.end(), [](uint32_t c) { return c != 0; })) {
+        launch_slash_table_build(h->stream, sl.d_data.as<uint8_t>(), sl.d_count.as<uint32_t>(), sl.d_tab.as<uint32_t>(), sl.max_data,
+                                 sl.tab_size - 1, H);
+        HIP_TRY(h, hipGetLastError());
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));  // the uploads read the host's vectors
+    for (auto& e : sl.epochs) { e.data.clear(); e.id_of.clear(); }
+    sl.on_device = true;
+    return PE_OK;
+}
+
+// ... and back: the data of every slot come down and the maps are built again, ids unchanged
+int to_host(pe_engine* h)
+{
+    auto& sl = h->slasher;
+    if (!sl.on_device) return PE_OK;
+    std::string key(128, '\0');
+    for (uint32_t slot = 0; slot < sl.history; ++slot) {
+        auto& ep = sl.epochs[slot];
+        ep.data.assign(sl.dev_count[slot], {});
+        ep.id_of.clear();
+        if (ep.data.empty()) continue;
+        HIP_TRY(h, hipMemcpy(ep.data.data(), sl.d_data.as<uint8_t>() + 128ull * slot * sl.max_data, 128ull * ep.data.size(),
+                             hipMemcpyDeviceToHost));
+        for (uint32_t id = 0; id < ep.data.size(); ++id) {
+            memcpy(&key[0], ep.data[id].data(), 128);
+            ep.id_of.emplace(key, id);
+        }
+    }
+    sl.on_device = false;
+    return PE_OK;
+}
+
+// the scan over the rows and lists of `ka`, and what both routes do with its findings
+int run_scan(pe_engine* h, const SlashArgs& ka, uint32_t flags, pe_slash_evidence* out_evidence, uint32_t cap,
+             uint32_t* out_n_found, std::vector<uint8_t>& flags_back)
+{
+    HIP_TRY(h, hipMemsetAsync(ka.counter, 0, 4, h->stream));
+    launch_slash_scan(h->stream, ka);
+    HIP_TRY(h, hipGetLastError());
+    uint32_t found = 0;
+    HIP_TRY(h, hipMemcpyAsync(&found, ka.counter, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *out_n_found = found;
+    if (found && cap)
+        HIP_TRY(h, hipMemcpy(out_evidence, ka.evidence, sizeof(pe_slash_evidence) * (size_t)std::min(found, cap),
+                             hipMemcpyDeviceToHost));
+    if (found && (flags & PE_SLASH_APPLY)) {  // the host mirror pe_get_validator_flags and the next flag upload read
+        HIP_TRY(h, hipMemcpy(flags_back.data(), h->d_flags.p, h->n_val, hipMemcpyDeviceToHost));
+        for (uint64_t v = 0; v < h->n_val; ++v) h->h_flags[v] |= flags_back[v] & PE_VAL_EQUIVOCATING;
+    }
+    return PE_OK;
+}
+
+// pe_slasher_ingest(h, PE_ROWS_RESIDENT, cap_rows, PE_BITS_RESIDENT, ...): every group of the resident aggregate, in group order
+int ingest_resident_rows(pe_engine* h, uint32_t cap_rows, uint64_t W, uint32_t flags, int32_t* status,
+                         pe_slash_evidence* out_evidence, uint32_t cap, uint32_t* out_n_found)
+{
+    auto& sl = h->slasher;
+    if (h->dist_ready()) return fail(h, PE_ERR_STATE, "pe_slasher_ingest: not on a handle that exchanges with other ranks");
+    PE_TRY(resident_precheck(h, "pe_slasher_ingest"));
+    ResidentParts P;
+    PE_TRY(resident_parts(h, &P));
+    AttPlan plan;
+    HIP_TRY(h, hipMemcpyAsync(&plan, P.plan, sizeof(plan), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (plan.last_error) return plan_error_to_status(h, plan.last_error, "pe_slasher_ingest (PE_ROWS_RESIDENT): the aggregate");
+    const uint32_t ng = plan.n_groups;
+    if (ng > P.n_in) return fail(h, PE_ERR_NO_DEVICE, "k_att_plan returned more groups than rows");
+    if (ng > cap_rows) return fail(h, PE_ERR_CAPACITY, "pe_slasher_ingest: status holds fewer entries than groups were formed");
+    // the call's scratch
+    uint32_t cand = 64;
+    while (cand < 2 * ng) cand <<= 1;
+    const TablesDev& T = h->rr.tables;
+    uint32_t nc[2];
+    for (int t = 0; t < 2; ++t) nc[t] = T.t[t].valid ? T.t[t].n_committees : 0u;
+    const size_t n_keys = (size_t)nc[0] + nc[1] + 1;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 255) & ~size_t(255); return at; };
+    const size_t o_err = take(16), o_status = take(4ull * ng), o_cslot = take(4ull * ng), o_id = take(4ull * ng),
+                 o_rows = take(sizeof(SlashRow) * (size_t)ng), o_cand = take(4ull * cand), o_cnt = take(4 * n_keys),
+                 o_start = take(4 * n_keys), o_cursor = take(4 * n_keys), o_list = take(4ull * ng),
+                 o_tabs = take(2 * sizeof(SlashTable));
+    hipError_t e = sl.d_work.ensure(off);
+    if (e == hipSuccess && cap) e = sl.d_evidence.ensure(sizeof(pe_slash_evidence) * (size_t)cap);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, PE_ERR_OOM, "pe_slasher_ingest: scratch of the call"); }
+    std::vector<uint8_t> flags_back;
+    if (flags & PE_SLASH_APPLY) flags_back.resize(h->n_val);
+    uint8_t* wk = sl.d_work.as<uint8_t>();
+    const uint32_t H = sl.history;
+    SlashRowsArgs ra{};
+    ra.rows = P.rows;
+    ra.grp = P.grp;
+    ra.n_groups = ng;
+    ra.window = W;
+    ra.history = H;
+    ra.max_data = sl.max_data;
+    ra.tab_mask = sl.tab_size - 1;
+    ra.slot_of_table[0] = (uint32_t)(T.t[0].epoch % H);
+    ra.slot_of_table[1] = T.t[1].valid ? (uint32_t)(T.t[1].epoch % H) : ra.slot_of_table[0];
+    ra.data = sl.d_data.as<uint8_t>();
+    ra.count = sl.d_count.as<uint32_t>();
+    ra.tab = sl.d_tab.as<uint32_t>();
+    ra.status = reinterpret_cast<int32_t*>(wk + o_status);
+    ra.err = reinterpret_cast<uint32_t*>(wk + o_err);
+    ra.cand_tab = reinterpret_cast<uint32_t*>(wk + o_cand);
+    ra.cand_mask = cand - 1;
+    ra.cand_slot = reinterpret_cast<uint32_t*>(wk + o_cslot);
+    ra.id = reinterpret_cast<uint32_t*>(wk + o_id);
+    ra.out_rows = reinterpret_cast<SlashRow*>(wk + o_rows);
+
+    // ---- nothing is changed yet: the check pass (it reads no table) and its error word
+    if (ng) {
+        uint32_t err = 0;
+        HIP_TRY(h, hipMemsetAsync(ra.err, 0, 16, h->stream));
+        launch_slash_rows_check(h->stream, ra);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(&err, ra.err, 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (err) return fail(h, PE_ERR_INVALID_ARG, "source and target epoch must fit 32 bits");
+    }
+    PE_TRY(to_device(h));
+    // ---- from here on the call changes the history: the window first
+    PE_TRY(advance_window(h, W));
+    *out_n_found = 0;
+    memset(status, 0, 4ull * cap_rows);  // entries past the groups formed read 0
+    if (ng == 0) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));  // the window's memsets
+        return PE_OK;
+    }
+    HIP_TRY(h, hipMemsetAsync(ra.cand_tab, 0xFF, 4ull * cand, h->stream));
+    launch_slash_rows_lookup(h->stream, ra);
+    launch_slash_rows_ids(h->stream, ra);
+    launch_slash_rows_emit(h->stream, ra);
+    SlashListsArgs la{};
+    SlashArgs ka{};
+    la.rows = ra.out_rows;
+    la.grp = P.grp;
+    la.n_groups = ng;
+    la.cnt = reinterpret_cast<uint32_t*>(wk + o_cnt);
+    la.start = reinterpret_cast<uint32_t*>(wk + o_start);
+    la.cursor = reinterpret_cast<uint32_t*>(wk + o_cursor);
+    for (int t = 0; t < 2; ++t) {
+        la.n_committees[t] = nc[t];
+        if (!nc[t]) continue;
+        la.table_val[la.n_tables++] = SlashTable{T.t[t].inv_comm, T.t[t].inv_pos, la.start + (t ? nc[0] : 0u)};
+        if (CommitteeTable* ct = find_table(h, T.t[t].epoch)) ct->stamp = ++h->table_stamp;
+    }
+    la.crow_list = reinterpret_cast<uint32_t*>(wk + o_list);
+    la.tables = reinterpret_cast<SlashTable*>(wk + o_tabs);
+    HIP_TRY(h, hipMemsetAsync(la.cnt, 0, 4 * n_keys, h->stream));
+    launch_slash_rows_lists(h->stream, la);
+    HIP_TRY(h, hipGetLastError());
+    ka.rows = ra.out_rows;
+    ka.tables = la.tables;
+    ka.n_tables = la.n_tables;
+    ka.crow_list = la.crow_list;
+    ka.bits = reinterpret_cast<const uint8_t*>(P.res_bits);
+    ka.rec = sl.d_rec.as<unsigned long long>();
+    ka.ids = sl.d_ids.as<uint32_t>();
+    ka.history = sl.history;
+    ka.n_val = h->n_val;
+    ka.counter = sl.d_counter.as<uint32_t>();
+    ka.evidence = sl.d_evidence.as<uint32_t>();
+    ka.cap = cap;
+    ka.flags = (flags & PE_SLASH_APPLY) ? h->d_flags.as<uint8_t>() : nullptr;
+    HIP_TRY(h, hipMemcpyAsync(status, ra.status, 4ull * ng, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(sl.dev_count.data(), sl.d_count.p, 4ull * H, hipMemcpyDeviceToHost, h->stream));
+    if (la.n_tables == 0) {  // no group had a committee: nothing to scan
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        return PE_OK;
+    }
+    return run_scan(h, ka, flags, out_evidence, cap, out_n_found, flags_back);
 }
 
 }  // namespace
@@ -77,11 +287,20 @@ int pe_slasher_enable(pe_engine* h, uint32_t history_epochs, uint32_t max_data_p
     hipError_t e = sl.d_rec.ensure(8 * cells, false, nullptr, true);
     if (e == hipSuccess) e = sl.d_ids.ensure(4 * cells, false, nullptr, true);
     if (e == hipSuccess) e = sl.d_counter.ensure(256);
+    // the data tables of the device-row route: per epoch slot D x 128 bytes, a count and T >= 2 D table entries
+    uint64_t tab = 2;
+    while (tab < 2ull * max_data_per_epoch) tab <<= 1;
+    if (e == hipSuccess) e = sl.d_data.ensure(128ull * history_epochs * max_data_per_epoch, false, nullptr, true);
+    if (e == hipSuccess) e = sl.d_tab.ensure(4ull * history_epochs * tab, false, nullptr, true);
+    if (e == hipSuccess) e = sl.d_count.ensure(4ull * history_epochs + 256);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         slasher_release(h);
-        return fail(h, PE_ERR_OOM, "pe_slasher_enable: 12 bytes per validator and epoch of history do not fit");
+        return fail(h, PE_ERR_OOM, "pe_slasher_enable: 12 bytes per validator and epoch of history, and ~136 bytes per "
+                                   "AttestationData and epoch, do not fit");
     }
+    sl.tab_size = (uint32_t)tab;
+    sl.dev_count.assign(history_epochs, 0u);
     sl.history = history_epochs;
     sl.max_data = max_data_per_epoch;
     sl.n_val = h->n_val;
@@ -109,9 +328,13 @@ int pe_slasher_ingest(pe_engine* h, const pe_attestation* atts, uint32_t n, cons
     if (sl.n_val != h->n_val) return fail(h, PE_ERR_STATE, "pe_slasher_ingest: the registry changed size, enable the slasher again");
     if (!out_n_found || (n && (!atts || !bits_arena || !status)) || (cap && !out_evidence) || (flags & ~PE_SLASH_APPLY))
         return PE_ERR_INVALID_ARG;
+    const bool rows_resident = atts == PE_ROWS_RESIDENT;
+    if (rows_resident && bits_arena != PE_BITS_RESIDENT)
+        return fail(h, PE_ERR_INVALID_ARG, "pe_slasher_ingest: PE_ROWS_RESIDENT goes with PE_BITS_RESIDENT");
     if (sl.have_window && current_epoch < sl.window)
         return fail(h, PE_ERR_INVALID_ARG, "pe_slasher_ingest: current_epoch may not decrease");
     if (current_epoch >= 0xFFFFFFFEull) return fail(h, PE_ERR_INVALID_ARG, "current epoch must fit 32 bits");
+    if (rows_resident) return ingest_resident_rows(h, n, current_epoch, flags, status, out_evidence, cap, out_n_found);
     const bool resident = bits_arena == PE_BITS_RESIDENT;
     if (resident && !h->res_valid) return fail(h, PE_ERR_STATE, "PE_BITS_RESIDENT: no pe_aggregate result is resident");
     const bool dev_bits = !resident && n && bits_on_device(bits_arena);
@@ -166,6 +389,7 @@ int pe_slasher_ingest(pe_engine* h, const pe_attestation* atts, uint32_t n, cons
     std::vector<uint8_t> flags_back;
     if (flags & PE_SLASH_APPLY) flags_back.resize(h->n_val);
 
+    PE_TRY(to_host(h));  // the ids continue where calls over device rows left them
     // ---- from here on the call changes the history: the window first
     PE_TRY(advance_window(h, W));
     *out_n_found = 0;
@@ -257,21 +481,7 @@ int pe_slasher_ingest(pe_engine* h, const pe_attestation* atts, uint32_t n, cons
     ka.cap = cap;
     ka.flags = (flags & PE_SLASH_APPLY) ? h->d_flags.as<uint8_t>() : nullptr;
     HIP_TRY(h, st.upload());
-    HIP_TRY(h, hipMemsetAsync(ka.counter, 0, 4, h->stream));
-    launch_slash_scan(h->stream, ka);
-    HIP_TRY(h, hipGetLastError());
-    uint32_t found = 0;
-    HIP_TRY(h, hipMemcpyAsync(&found, ka.counter, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *out_n_found = found;
-    if (found && cap)
-        HIP_TRY(h, hipMemcpy(out_evidence, ka.evidence, sizeof(pe_slash_evidence) * (size_t)std::min(found, cap),
-                             hipMemcpyDeviceToHost));
-    if (found && (flags & PE_SLASH_APPLY)) {  // the host mirror pe_get_validator_flags and the next flag upload read
-        HIP_TRY(h, hipMemcpy(flags_back.data(), h->d_flags.p, h->n_val, hipMemcpyDeviceToHost));
-        for (uint64_t v = 0; v < h->n_val; ++v) h->h_flags[v] |= flags_back[v] & PE_VAL_EQUIVOCATING;
-    }
-    return PE_OK;
+    return run_scan(h, ka, flags, out_evidence, cap, out_n_found, flags_back);
 }
 
 int pe_slasher_get_data(pe_engine* h, uint64_t target_epoch, uint32_t id, pe_attestation* out)
@@ -281,10 +491,15 @@ int pe_slasher_get_data(pe_engine* h, uint64_t target_epoch, uint32_t id, pe_att
     if (!sl.enabled) return fail(h, PE_ERR_STATE, "pe_slasher_get_data: call pe_slasher_enable first");
     if (!sl.have_window || target_epoch > sl.window || target_epoch + sl.history <= sl.window)
         return fail(h, PE_ERR_INVALID_ARG, "pe_slasher_get_data: target epoch outside the window");
-    const auto& ep = sl.epochs[target_epoch % sl.history];
-    if (id >= ep.data.size()) return fail(h, PE_ERR_INVALID_ARG, "pe_slasher_get_data: no such data id");
+    const uint64_t slot = target_epoch % sl.history;
+    const auto& ep = sl.epochs[slot];
+    if (id >= (sl.on_device ? sl.dev_count[slot] : ep.data.size()))
+        return fail(h, PE_ERR_INVALID_ARG, "pe_slasher_get_data: no such data id");
     memset(out, 0, sizeof(*out));
-    memcpy(out, ep.data[id].data(), 128);
+    if (sl.on_device)  // whichever side is current answers; every call that wrote the tables has completed
+        HIP_TRY(h, hipMemcpy(out, sl.d_data.as<uint8_t>() + 128ull * (slot * sl.max_data + id), 128, hipMemcpyDeviceToHost));
+    else
+        memcpy(out, ep.data[id].data(), 128);
     return PE_OK;
 }
 

@@ -362,6 +362,55 @@ struct SlashArgs {
 constexpr int SLASH_NV = 4;       // new votes of one validator held in registers per pass over its history
 void launch_slash_scan(hipStream_t s, const SlashArgs& a);
 
+// pe_slasher_ingest over the groups of a resident aggregate (PE_ROWS_RESIDENT): the rows, tables and lists k_slash_scan
+// reads are formed on the device from AttGroup[] / the caller's device rows, and the AttestationData ids come from tables
+// in device memory.  Per epoch slot s of the window: data[s][id] = the 128 bytes behind id (id < count[s] <= D), and
+// tab[s][T] (T a power of two >= 2 D) = open addressing over slash_data_hash of the 128 bytes, entry = id, NONE32 = empty;
+// a hit is confirmed by comparing all 128 bytes.  A slot's table only ever holds data of ONE target epoch.
+struct SlashRowsArgs {
+    const void* rows;             // the caller's device rows (144 B each): a group's data = 128 leading bytes of row grp[g].rep
+    const AttGroup* grp; uint32_t n_groups;
+    uint64_t window; uint32_t history;  // W, H: the window the statuses are judged against
+    uint32_t max_data, tab_mask;        // D, T - 1
+    uint32_t slot_of_table[2];          // epoch slot of candidate table 0 / 1 (current / previous epoch of the store)
+    uint8_t* data; uint32_t* count; uint32_t* tab;
+    int32_t* status;              // per group: pe_att_status / PE_SLASH_*
+    uint32_t* err;                // check pass: bit 0 = an epoch of some group does not fit 32 bits
+    uint32_t* cand_tab; uint32_t cand_mask;  // the call's candidates (data the slot does not hold yet): entry = lowest group
+    uint32_t* cand_slot;          // per group: its entry of cand_tab, NONE32 = not a candidate
+    uint32_t* id;                 // per group: the id found / handed out, SLASH_ID_FULL = its data did not fit
+    SlashRow* out_rows;           // one per group; n_bits = 0 where the group takes no part
+};
+constexpr uint32_t SLASH_ID_FULL = 0xFFFFFFFEu;
+constexpr uint32_t SLASH_ROWS_WG = 256;
+// one lane per group: the 32-bit epoch checks into *err, then window status -> status_agg -> bits length into status[]
+void launch_slash_rows_check(hipStream_t s, const SlashRowsArgs& a);
+// one lane per passing group: look its data up in its slot's table (read only); unknown data joins cand_tab, where the
+// lowest group index of each distinct data stays (cand_tab all NONE32 on entry)
+void launch_slash_rows_lookup(hipStream_t s, const SlashRowsArgs& a);
+// ONE workgroup walks the groups in tiles of 256: the candidates that cand_tab names are the new data, in group order; new
+// id = count[slot] + rank among the new data of the slot (wave scan -> LDS -> carry over tiles); ids below D are inserted
+// (table, data bytes), the others are SLASH_ID_FULL; count[] is advanced
+void launch_slash_rows_ids(hipStream_t s, const SlashRowsArgs& a);
+// one lane per group: the id of its data (its own, or the inserting group's), PE_SLASH_TABLE_FULL, and its SlashRow
+void launch_slash_rows_emit(hipStream_t s, const SlashRowsArgs& a);
+// the committees' group lists as k_slash_scan wants them, by a counting sort over the groups that take part (the plan's own
+// lists are unordered and leave out a group whose bits are longer than its committee): ONE start array over the committees
+// of table 0, then of table 1 (table t's crow_start begins at its first committee), one list, each committee's groups
+// ascending.  count (a lane per group; cnt zeroed by the caller) -> scan (one workgroup, tiles with a carry; writes
+// tables[]) -> fill (a lane per group, in arrival order) -> sort (a lane per committee, in place).
+struct SlashListsArgs {
+    const SlashRow* rows; const AttGroup* grp; uint32_t n_groups;
+    uint32_t n_committees[2];     // 0 = the table takes no part
+    uint32_t* cnt; uint32_t* start; uint32_t* cursor;  // n_committees[0] + n_committees[1] + 1 entries each
+    uint32_t* crow_list;
+    SlashTable* tables; SlashTable table_val[2]; uint32_t n_tables;
+};
+void launch_slash_rows_lists(hipStream_t s, const SlashListsArgs& a);
+// (re)build the tables of every slot from data[] / count[] (tab all NONE32 on entry): grid (ceil(D / 256), H)
+void launch_slash_table_build(hipStream_t s, const uint8_t* data, const uint32_t* count, uint32_t* tab, uint32_t max_data,
+                              uint32_t tab_mask, uint32_t history);
+
 // The working-state view mirrors the registry (pe_store_init): sflags = active/slashed (+ active-in-previous-epoch),
 // increments = balance / effective_balance_increment.
 void launch_state_view_from_registry(hipStream_t s, const uint8_t* flags, const uint64_t* balance, uint64_t increment,

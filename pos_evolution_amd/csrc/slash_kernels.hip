@@ -8,7 +8,15 @@
 // and compared in ONE pass over the H slots; a validator with more new votes in one call (rare: that many different
 // votes in one batch) takes further passes, each behind the records the previous one wrote.
 // The kernel is a guest beside the G1 accumulation like the flag passes: it does not raise its wave priority.
+//
+// The k_slash_rows_* kernels behind it feed that scan from the groups of a resident aggregate (PE_ROWS_RESIDENT): statuses,
+// AttestationData ids out of the per-slot tables in device memory, one SlashRow per group and the committees' group lists
+// in ascending order (kernels.h, SlashRowsArgs / SlashListsArgs).  What one phase hands to the next crosses a kernel boundary; inside a
+// launch lanes meet only in atomics on table entries (a compare-and-swap claims an entry, atomicMin keeps the lowest
+// group), and no id comes out of an atomic: ids are the slot's count plus an ordered scan over the groups.
+#include <algorithm>
 #include "kernels.h"
+#include "wave64.h"
 
 namespace posevo {
 
@@ -144,6 +152,309 @@ void launch_slash_scan(hipStream_t s, const SlashArgs& a)
 {
     if (a.n_val == 0 || a.history == 0) return;
     hipLaunchKernelGGL(k_slash_scan, dim3((unsigned)((a.n_val + 255) / 256)), dim3(256), 0, s, a);
+}
+
+// ------------------------------------------------------------------ rows, ids and lists from a resident aggregate
+namespace {
+
+constexpr int32_t SL_BITS_LENGTH = 10, SL_FUTURE_TARGET = 32, SL_TOO_OLD = 33, SL_TABLE_FULL = 34;  // include/posevo.h
+
+struct Data8 { uint4 q[8]; };  // one AttestationData as struct pe_attestation lays it out: 128 bytes
+__device__ __forceinline__ void load_data(Data8& d, const uint4* p)
+{
+#pragma unroll
+    for (int k = 0; k < 8; ++k) d.q[k] = p[k];
+}
+__device__ __forceinline__ bool same_data(const Data8& d, const uint4* p)
+{
+    uint32_t diff = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint4 x = p[k];
+        diff |= (x.x ^ d.q[k].x) | (x.y ^ d.q[k].y) | (x.z ^ d.q[k].z) | (x.w ^ d.q[k].w);
+    }
+    return diff == 0;
+}
+__device__ __forceinline__ uint32_t slash_mix(uint32_t h, uint32_t v)
+{
+    h ^= v;
+    h *= 0x9E3779B1u;
+    return h ^ (h >> 15);
+}
+// the key of both tables: the 32 little-endian words of the data, folded in order (tests/test_gpu_slasher_rows.py holds a
+// twin of it to place collisions)
+__device__ __forceinline__ uint32_t slash_data_hash(const Data8& d)
+{
+    uint32_t h = 0x85EBCA6Bu;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        h = slash_mix(h, d.q[k].x);
+        h = slash_mix(h, d.q[k].y);
+        h = slash_mix(h, d.q[k].z);
+        h = slash_mix(h, d.q[k].w);
+    }
+    return h;
+}
+__device__ __forceinline__ const uint4* group_data(const SlashRowsArgs& a, const AttGroup& G)
+{
+    return static_cast<const uint4*>(a.rows) + (size_t)9 * G.rep;
+}
+__device__ __forceinline__ unsigned long long u64_of(uint32_t lo, uint32_t hi) { return ((unsigned long long)hi << 32) | lo; }
+
+}  // namespace
+
+__global__ void __launch_bounds__(256)
+k_slash_rows_check(const SlashRowsArgs a)
+{
+    const uint32_t g = blockIdx.x * SLASH_ROWS_WG + threadIdx.x;
+    if (g >= a.n_groups) return;
+    const AttGroup G = a.grp[g];
+    const uint4* p = group_data(a, G);
+    const uint4 q3 = p[3], q5 = p[5];
+    const unsigned long long sep = u64_of(q3.x, q3.y), tep = u64_of(q5.z, q5.w);
+    if (tep >= 0xFFFFFFFEull || sep >= 0xFFFFFFFFull) atomicOr(a.err, 1u);  // the whole call fails (engine_slash.cpp)
+    int32_t st = 0;
+    if (tep > a.window) st = SL_FUTURE_TARGET;
+    else if (tep + a.history <= a.window) st = SL_TOO_OLD;
+    // no table among the two candidates, or no such committee; the aggregate's own len(bits) != len(committee) is left to the
+    // slasher's rule (bits longer than the committee take part, as with host rows: the group's committee is resolved then)
+    else if (G.status_agg && G.status_agg != (uint32_t)SL_BITS_LENGTH) st = (int32_t)G.status_agg;
+    else if (G.n_bits < G.size) st = SL_BITS_LENGTH;
+    a.status[g] = st;
+}
+
+__global__ void __launch_bounds__(256)
+k_slash_rows_lookup(const SlashRowsArgs a)
+{
+    const uint32_t g = blockIdx.x * SLASH_ROWS_WG + threadIdx.x;
+    if (g >= a.n_groups) return;
+    uint32_t id = NONE32, cslot = NONE32;
+    if (a.status[g] == 0) {
+        const AttGroup G = a.grp[g];
+        Data8 d;
+        load_data(d, group_data(a, G));
+        const uint32_t h = slash_data_hash(d);
+        const uint32_t slot = a.slot_of_table[G.table & 1u];
+        const uint32_t* tab = a.tab + (size_t)slot * (a.tab_mask + 1u);
+        const uint4* data = reinterpret_cast<const uint4*>(a.data) + (size_t)slot * a.max_data * 8;
+        for (uint32_t at = h & a.tab_mask;; at = (at + 1) & a.tab_mask) {  // at most half of the entries are taken
+            const uint32_t e = tab[at];
+            if (e == NONE32) break;
+            if (same_data(d, data + (size_t)e * 8)) { id = e; break; }
+        }
+        if (id == NONE32) {  // new to the slot: the lowest group among those that carry this data will insert it
+            cslot = h & a.cand_mask;
+            for (;;) {
+                const uint32_t prev = atomicCAS(&a.cand_tab[cslot], NONE32, g);
+                if (prev == NONE32) break;
+                if (same_data(d, group_data(a, a.grp[prev]))) {  // any group of the entry carries the entry's data
+                    atomicMin(&a.cand_tab[cslot], g);
+                    break;
+                }
+                cslot = (cslot + 1) & a.cand_mask;
+            }
+        }
+    }
+    a.id[g] = id;
+    a.cand_slot[g] = cslot;
+}
+
+__global__ void __launch_bounds__(256)
+k_slash_rows_ids(const SlashRowsArgs a)
+{
+    __shared__ uint32_t s_wave[SLASH_ROWS_WG / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t slot0 = a.slot_of_table[0], slot1 = a.slot_of_table[1];
+    const uint32_t cnt0 = a.count[slot0], cnt1 = a.count[slot1];
+    uint32_t carry0 = 0, carry1 = 0;  // new data of each slot in the tiles in front of this one
+    for (uint32_t base = 0; base < a.n_groups; base += SLASH_ROWS_WG) {
+        const uint32_t g = base + tid;
+        bool leader = false;
+        uint32_t t = 0;
+        if (g < a.n_groups) {
+            const uint32_t cs = a.cand_slot[g];
+            if (cs != NONE32 && a.cand_tab[cs] == g) { leader = true; t = a.grp[g].table & 1u; }
+        }
+        const uint32_t v = leader ? (t ? 0x10000u : 1u) : 0u;  // both slots' counts in one word: a tile holds <= 256
+        const uint32_t inc = wave_incl_scan(v);
+        __syncthreads();  // the previous tile has read s_wave
+        if (lane == 63) s_wave[wave] = inc;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < SLASH_ROWS_WG / 64; ++w) {
+            const uint32_t x = s_wave[w];
+            if (w < wave) before += x;
+            total += x;
+        }
+        if (leader) {
+            const uint32_t ex = before + inc - v;
+            const uint32_t nid = t ? cnt1 + carry1 + (ex >> 16) : cnt0 + carry0 + (ex & 0xFFFFu);
+            if (nid < a.max_data) {
+                const uint32_t slot = t ? slot1 : slot0;
+                Data8 d;
+                load_data(d, group_data(a, a.grp[g]));
+                uint32_t* tab = a.tab + (size_t)slot * (a.tab_mask + 1u);
+                uint32_t at = slash_data_hash(d) & a.tab_mask;
+                while (atomicCAS(&tab[at], NONE32, nid) != NONE32) at = (at + 1) & a.tab_mask;  // distinct data: claim a free entry
+                uint4* out = reinterpret_cast<uint4*>(a.data) + ((size_t)slot * a.max_data + nid) * 8;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) out[k] = d.q[k];
+                a.id[g] = nid;
+            } else {
+                a.id[g] = SLASH_ID_FULL;
+            }
+        }
+        carry0 += total & 0xFFFFu;
+        carry1 += total >> 16;
+    }
+    // (a slot without new data is left alone: at epoch 0 both candidate tables name the same slot)
+    if (tid == 0 && carry0) a.count[slot0] = min(cnt0 + carry0, a.max_data);
+    if (tid == 0 && carry1) a.count[slot1] = min(cnt1 + carry1, a.max_data);
+}
+
+__global__ void __launch_bounds__(256)
+k_slash_rows_emit(const SlashRowsArgs a)
+{
+    const uint32_t g = blockIdx.x * SLASH_ROWS_WG + threadIdx.x;
+    if (g >= a.n_groups) return;
+    SlashRow r;
+    r.bits_byte = r.n_bits = r.source = r.target = r.id = 0;  // n_bits = 0: no position is below it, the scan skips the row
+    r.pad[0] = r.pad[1] = r.pad[2] = 0;
+    if (a.status[g] == 0) {
+        const uint32_t cs = a.cand_slot[g];
+        const uint32_t id = cs == NONE32 ? a.id[g] : a.id[a.cand_tab[cs]];
+        if (id == SLASH_ID_FULL) {
+            a.status[g] = SL_TABLE_FULL;
+        } else {
+            const AttGroup G = a.grp[g];
+            const uint4* p = group_data(a, G);
+            r.bits_byte = 4u * G.out_word;
+            r.n_bits = G.size;
+            r.source = p[3].x;
+            r.target = p[5].z;
+            r.id = id;
+        }
+    }
+    a.out_rows[g] = r;
+}
+
+namespace {
+// the committee of a group that takes part, in the one index space of both tables; NONE32 = it takes no part
+__device__ __forceinline__ uint32_t list_key(const SlashListsArgs& a, uint32_t g)
+{
+    if (a.rows[g].n_bits == 0) return NONE32;
+    const AttGroup& G = a.grp[g];
+    return ((G.table & 1u) ? a.n_committees[0] : 0u) + G.pos;
+}
+}  // namespace
+
+__global__ void __launch_bounds__(256)
+k_slash_lists_count(const SlashListsArgs a)
+{
+    const uint32_t g = blockIdx.x * SLASH_ROWS_WG + threadIdx.x;
+    if (g >= a.n_groups) return;
+    const uint32_t key = list_key(a, g);
+    if (key != NONE32) atomicAdd(&a.cnt[key], 1u);
+}
+
+__global__ void __launch_bounds__(256)
+k_slash_lists_scan(const SlashListsArgs a)
+{
+    __shared__ uint32_t s_wave[SLASH_ROWS_WG / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t nc = a.n_committees[0] + a.n_committees[1];
+    if (tid == 0)
+        for (uint32_t t = 0; t < a.n_tables; ++t) a.tables[t] = a.table_val[t];
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base <= nc; base += SLASH_ROWS_WG) {  // entry nc: the end mark
+        const uint32_t i = base + tid;
+        const uint32_t v = i < nc ? a.cnt[i] : 0u;
+        const uint32_t inc = wave_incl_scan(v);
+        __syncthreads();  // the previous tile has read s_wave
+        if (lane == 63) s_wave[wave] = inc;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < SLASH_ROWS_WG / 64; ++w) {
+            const uint32_t x = s_wave[w];
+            if (w < wave) before += x;
+            total += x;
+        }
+        if (i <= nc) a.start[i] = a.cursor[i] = carry + before + inc - v;
+        carry += total;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_slash_lists_fill(const SlashListsArgs a)
+{
+    const uint32_t g = blockIdx.x * SLASH_ROWS_WG + threadIdx.x;
+    if (g >= a.n_groups) return;
+    const uint32_t key = list_key(a, g);
+    if (key != NONE32) a.crow_list[atomicAdd(&a.cursor[key], 1u)] = g;  // the committee's own range: start[key] .. start[key + 1]
+}
+
+__global__ void __launch_bounds__(256)
+k_slash_lists_sort(const SlashListsArgs a)
+{
+    const uint32_t c = blockIdx.x * SLASH_ROWS_WG + threadIdx.x;
+    if (c >= a.n_committees[0] + a.n_committees[1]) return;
+    const uint32_t kb = a.start[c], ke = a.start[c + 1];
+    uint32_t* out = a.crow_list;
+    for (uint32_t k = kb + 1; k < ke; ++k) {  // a committee has a handful of groups: insertion sort
+        const uint32_t x = out[k];
+        uint32_t j = k;
+        for (; j > kb && out[j - 1] > x; --j) out[j] = out[j - 1];
+        out[j] = x;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_slash_table_build(const uint8_t* data, const uint32_t* count, uint32_t* tab, uint32_t max_data, uint32_t tab_mask)
+{
+    const uint32_t slot = blockIdx.y, id = blockIdx.x * SLASH_ROWS_WG + threadIdx.x;
+    if (id >= min(count[slot], max_data)) return;
+    Data8 d;
+    load_data(d, reinterpret_cast<const uint4*>(data) + ((size_t)slot * max_data + id) * 8);
+    uint32_t* t = tab + (size_t)slot * (tab_mask + 1u);
+    uint32_t at = slash_data_hash(d) & tab_mask;
+    while (atomicCAS(&t[at], NONE32, id) != NONE32) at = (at + 1) & tab_mask;
+}
+
+static unsigned slash_rows_blocks(uint32_t n) { return (n + SLASH_ROWS_WG - 1) / SLASH_ROWS_WG; }
+void launch_slash_rows_check(hipStream_t s, const SlashRowsArgs& a)
+{
+    if (a.n_groups) hipLaunchKernelGGL(k_slash_rows_check, dim3(slash_rows_blocks(a.n_groups)), dim3(SLASH_ROWS_WG), 0, s, a);
+}
+void launch_slash_rows_lookup(hipStream_t s, const SlashRowsArgs& a)
+{
+    if (a.n_groups) hipLaunchKernelGGL(k_slash_rows_lookup, dim3(slash_rows_blocks(a.n_groups)), dim3(SLASH_ROWS_WG), 0, s, a);
+}
+void launch_slash_rows_ids(hipStream_t s, const SlashRowsArgs& a)
+{
+    if (a.n_groups) hipLaunchKernelGGL(k_slash_rows_ids, dim3(1), dim3(SLASH_ROWS_WG), 0, s, a);
+}
+void launch_slash_rows_emit(hipStream_t s, const SlashRowsArgs& a)
+{
+    if (a.n_groups) hipLaunchKernelGGL(k_slash_rows_emit, dim3(slash_rows_blocks(a.n_groups)), dim3(SLASH_ROWS_WG), 0, s, a);
+}
+void launch_slash_rows_lists(hipStream_t s, const SlashListsArgs& a)
+{
+    const uint32_t nc = a.n_committees[0] + a.n_committees[1];
+    if (!a.n_groups || !nc) return;
+    const dim3 per_group(slash_rows_blocks(a.n_groups)), per_committee(slash_rows_blocks(nc)), wg(SLASH_ROWS_WG);
+    hipLaunchKernelGGL(k_slash_lists_count, per_group, wg, 0, s, a);
+    hipLaunchKernelGGL(k_slash_lists_scan, dim3(1), wg, 0, s, a);
+    hipLaunchKernelGGL(k_slash_lists_fill, per_group, wg, 0, s, a);
+    hipLaunchKernelGGL(k_slash_lists_sort, per_committee, wg, 0, s, a);
+}
+void launch_slash_table_build(hipStream_t s, const uint8_t* data, const uint32_t* count, uint32_t* tab, uint32_t max_data,
+                              uint32_t tab_mask, uint32_t history)
+{
+    if (!max_data || !history) return;
+    hipLaunchKernelGGL(k_slash_table_build, dim3(slash_rows_blocks(max_data), history), dim3(SLASH_ROWS_WG), 0, s, data, count,
+                       tab, max_data, tab_mask);
 }
 
 }  // namespace posevo

@@ -545,17 +545,28 @@ class Engine:
     def slasher_disable(self):
         self._check(self._lib.pe_slasher_disable(self._h))
 
-    def slasher_ingest(self, rows=None, packed=None, current_epoch: int = 0, apply: bool = False, cap: int = 4096):
+    def slasher_ingest(self, rows=None, packed=None, current_epoch: int = 0, apply: bool = False, cap: int = 4096,
+                       cap_rows: int = 0):
         """pe_slasher_ingest -> (status int32[n], evidence): ``evidence`` = the first min(cap, found) pieces as a structured
         array (SLASH_EVIDENCE_DTYPE: validator, kind, target_epoch_1, id_1, target_epoch_2, id_2; ids resolve through
         slasher_data); ``self.slasher_found`` = the number found, which may exceed cap.  ``apply``: every validator with
         evidence joins store.equivocating_indices on the device (PE_SLASH_APPLY).  ``packed=(rows, RESIDENT)``: rows of
-        the last aggregate's result, their OR-ed bits used where they lie."""
+        the last aggregate's result, their OR-ed bits used where they lie.  ``packed=(ROWS_RESIDENT, RESIDENT),
+        cap_rows=c``: every group of the last aggregate over DeviceRows, in group order; status holds c entries (c >= the
+        groups formed; entries past them read 0)."""
         arr, arena = packed if packed is not None else pack_attestations(rows)
-        n = len(rows) if rows is not None else len(arr)
-        status = np.zeros(max(n, 1), dtype=np.int32)
         evidence = np.zeros(max(int(cap), 1), dtype=SLASH_EVIDENCE_DTYPE)
         found = C.c_uint32(0)
+        if arr is ROWS_RESIDENT:
+            status = np.zeros(max(int(cap_rows), 1), dtype=np.int32)
+            self._check(self._lib.pe_slasher_ingest(
+                self._h, _abi.PE_ROWS_RESIDENT, int(cap_rows), _abi.PE_BITS_RESIDENT if arena is RESIDENT else _ptr(arena, C.c_uint8),
+                0, int(current_epoch), _abi.PE_SLASH_APPLY if apply else 0, _ptr(status), _ptr(evidence), int(cap),
+                C.addressof(found)))
+            self.slasher_found = int(found.value)
+            return status[:int(cap_rows)], evidence[:min(int(cap), self.slasher_found)]
+        n = len(rows) if rows is not None else len(arr)
+        status = np.zeros(max(n, 1), dtype=np.int32)
         arena_p = _abi.PE_BITS_RESIDENT if arena is RESIDENT else _ptr(arena, C.c_uint8)
         self._check(self._lib.pe_slasher_ingest(self._h, _att_ptr(arr), n, arena_p, arena.size, int(current_epoch),
                                                 _abi.PE_SLASH_APPLY if apply else 0, _ptr(status), _ptr(evidence), int(cap),

@@ -42,7 +42,7 @@ from typing import Callable, Dict, Iterable, List, Optional, Sequence
 import numpy as np
 
 from . import _abi
-from .engine import AttRow, Engine, EngineError, ZERO_ROOT
+from .engine import ROWS_RESIDENT, AttRow, Engine, EngineError, ZERO_ROOT
 from ._abi import pe_state_ctx
 
 GENESIS_EPOCH = 0
@@ -287,21 +287,27 @@ class AttesterSlashing:
 
 
 def find_attester_slashings(store: Store, attestations: Iterable, *, apply: bool = False,
-                            cap: Optional[int] = None) -> List[AttesterSlashing]:
+                            cap: Optional[int] = None, cap_rows: int = 0) -> List[AttesterSlashing]:
     """The double and surround votes (pe:1128) that ``attestations`` hold against what their validators attested before,
     found on the GPU (Engine.slasher_enable first): one AttesterSlashing per slashable pair of AttestationData
     (is_slashable_attestation_data(d1, d2), pe:1134-1143, in the argument order on_attester_slashing accepts), the sorted
     validators that signed both as ``attesting_indices`` of both sides.  The history is that of the engine's window as of
     get_current_slot(store); the attestations join it.  ``cap`` bounds the pieces of evidence read back (default: four
-    per set bit); more than that raises -- the history has moved on by then, so size it generously."""
+    per set bit); more than that raises -- the history has moved on by then, so size it generously.
+    ``attestations=(ROWS_RESIDENT, RESIDENT), cap_rows=c``: every group of the engine's last aggregate over DeviceRows
+    (c >= the groups formed; ``cap`` then defaults to 65536)."""
     eng = store.engine
-    rows = [_att_row(a) for a in attestations]
+    resident = isinstance(attestations, tuple) and len(attestations) == 2 and attestations[0] is ROWS_RESIDENT
+    rows = [] if resident else [_att_row(a) for a in attestations]
     sc = eng.store_scalars()
     spe, sps = int(eng.cfg.slots_per_epoch), int(eng.cfg.seconds_per_slot)
     current_epoch = (sc["time"] - sc["genesis_time"]) // sps // spe
     if cap is None:
-        cap = 4 * sum(int(np.count_nonzero(r.bits)) for r in rows) + 1024
-    _, evidence = eng.slasher_ingest(rows, current_epoch=current_epoch, apply=apply, cap=cap)
+        cap = 1 << 16 if resident else 4 * sum(int(np.count_nonzero(r.bits)) for r in rows) + 1024
+    if resident:
+        _, evidence = eng.slasher_ingest(packed=attestations, cap_rows=cap_rows, current_epoch=current_epoch, apply=apply, cap=cap)
+    else:
+        _, evidence = eng.slasher_ingest(rows, current_epoch=current_epoch, apply=apply, cap=cap)
     if eng.slasher_found > len(evidence):
         raise EngineError(_abi.PE_ERR_CAPACITY, f"find_attester_slashings: {eng.slasher_found} pieces of evidence, cap {cap}")
     pairs: Dict[tuple, List[int]] = {}
