@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define PE_ABI_VERSION 11
+#define PE_ABI_VERSION 12
 
 typedef struct pe_engine pe_engine;
 
@@ -422,7 +422,7 @@ int pe_compute_proposers(pe_engine* h, const uint8_t* seeds32, uint32_t n_seeds,
                          uint32_t* out_proposers, uint32_t* out_tries);
 
 /* process_effective_balance_updates (pe:122-133) on the working-state view, in place:
- * balances u64[n] = state.balances (host memory); increment = cfg.effective_balance_increment;
+ * balances u64[n] = state.balances (host memory, or PE_BALANCES_RESIDENT); increment = cfg.effective_balance_increment;
  * thresholds = increment / hysteresis_quotient * {downward, upward}_multiplier.
  * If the view still mirrors pe_set_validators, it is first materialised from it, flags included.
  * The justified-checkpoint data that get_head weighs is NOT changed.
@@ -476,6 +476,74 @@ int pe_active_set(pe_engine* h, uint64_t epoch, uint32_t* out_n_active, uint64_t
  * first materialised from it exactly as pe_effective_balance_updates does.  The justified-checkpoint flags get_head
  * weighs (pe_get_validator_flags) are NOT changed.  Without epochs: PE_ERR_STATE.  Synchronous; one GPU. */
 int pe_state_refresh_activity(pe_engine* h, uint64_t current_epoch);
+
+/* ---- rewards and penalties over resident balances -------------------------- */
+/* state.balances, state.inactivity_scores and Validator.withdrawable_epoch of the whole registry, copied into device
+ * memory (three u64[n] arrays, 24 B per validator).  inactivity_scores NULL = zeros; withdrawable_epoch NULL =
+ * FAR_FUTURE_EPOCH (2^64 - 1) everywhere.  n must equal pe_num_validators(h): else PE_ERR_INVALID_ARG and nothing
+ * changes.  The arrays are dropped where the working-state view is: pe_store_init, and a pe_set_validators that changes n.
+ * _get: any output may be NULL; *out_is_set = 0: none held, the arrays are not written.  Checkpoint / resume goes through
+ * this pair (read with _get, hand back with _set), as with pe_registry_get_epochs. */
+int pe_state_set_balances(pe_engine* h, uint64_t n, const uint64_t* balances, const uint64_t* inactivity_scores,
+                          const uint64_t* withdrawable_epoch);
+int pe_state_get_balances(pe_engine* h, uint64_t n, uint64_t* out_balances, uint64_t* out_inactivity_scores,
+                          uint64_t* out_withdrawable_epoch, int* out_is_set);
+
+/* The constants process_inactivity_updates and process_rewards_and_penalties read beside cfg.effective_balance_increment.
+ * The participation flag weights (14, 26, 14) and WEIGHT_DENOMINATOR (64) are the ones process_attestation's flag passes
+ * use (Appendix A.9) and are not parameters. */
+typedef struct pe_rewards_params {
+    uint64_t base_reward_factor;                /* BASE_REWARD_FACTOR */
+    uint64_t inactivity_score_bias;             /* INACTIVITY_SCORE_BIAS */
+    uint64_t inactivity_score_recovery_rate;    /* INACTIVITY_SCORE_RECOVERY_RATE */
+    uint64_t inactivity_penalty_quotient;       /* INACTIVITY_PENALTY_QUOTIENT_* of the fork in force */
+    uint64_t min_epochs_to_inactivity_penalty;  /* MIN_EPOCHS_TO_INACTIVITY_PENALTY */
+} pe_rewards_params;
+/* 64, 4, 16, 2^24, 4.  The quotient is INACTIVITY_PENALTY_QUOTIENT_BELLATRIX (2^24), the value every fork since
+ * Bellatrix keeps; Altair's own was 3 * 2^24 -- set it for an Altair state. */
+void pe_rewards_params_default(pe_rewards_params* out);
+
+#define PE_REWARDS_INACTIVITY 1u  /* process_inactivity_updates: the scores */
+#define PE_REWARDS_DELTAS     2u  /* process_rewards_and_penalties: the four (rewards, penalties) pairs onto the balances */
+typedef struct pe_rewards_stats {
+    uint64_t total_active_balance;    /* get_total_active_balance: the quantity and rule of pe_ffg_balances out[0] */
+    uint64_t unslashed_balance[3];    /* get_total_balance(get_unslashed_participating_indices(f, previous_epoch)), f = 0, 1, 2 */
+    uint64_t n_eligible;              /* len(get_eligible_validator_indices) */
+    uint64_t in_leak;                 /* is_in_inactivity_leak: 0 or 1 */
+    uint64_t rewards;                 /* Gwei credited, all pairs */
+    uint64_t penalties;               /* Gwei actually debited, all pairs (after decrease_balance's cut at 0) */
+    uint64_t n_saturated;             /* validators where at least one subtraction was cut at 0 */
+} pe_rewards_stats;
+
+/* process_inactivity_updates (which & PE_REWARDS_INACTIVITY) and process_rewards_and_penalties (which &
+ * PE_REWARDS_DELTAS) of Altair over the resident arrays, in place; given both, the scores move first, as in
+ * process_epoch.  The rule set is restated in tests/rewards_model.py (the reference holds the fields and the callers of
+ * these functions, not their text).  Reads the working-state view (effective balances; PE_VAL_ACTIVE for the total,
+ * PE_VAL_ACTIVE_PREV and PE_VAL_SLASHED for eligibility and the unslashed sets: set them, or pe_state_refresh_activity
+ * does) and previous_epoch_participation; previous_epoch = max(current_epoch, 1) - 1.  If the view still mirrors
+ * pe_set_validators it is first materialised, as pe_effective_balance_updates does.
+ * in_leak = previous_epoch - finalized_epoch > min_epochs_to_inactivity_penalty.
+ * current_epoch == 0 (GENESIS_EPOCH): nothing is launched, *out_stats = 0.
+ * Two streaming kernels with a host step between them (k_reward_sums, k_reward_apply).  Synchronous (completes open
+ * pipelines first; ordered against the flag passes as pe_ffg_balances is); one GPU.  out_stats may be NULL.
+ * A failing call changes nothing:
+ *   PE_ERR_STATE        no resident balances (pe_state_set_balances), or pe_dist_init* active
+ *   PE_ERR_INVALID_ARG  which is 0 or has other bits; bias * quotient is 0 or exceeds 64 bits; finalized_epoch >
+ *                       previous_epoch; or the reference's uint64 would overflow -- decided on the host in 128 bits from
+ *                       what the first kernel reads back, before the second is launched: INCREMENT * base_reward_factor;
+ *                       total_active_balance / INCREMENT * 64; (largest effective balance among eligible validators /
+ *                       INCREMENT) * per_increment * 26 * (largest of the three unslashed balances / INCREMENT; 1 in a
+ *                       leak); largest effective balance * (largest score among eligible validators + bias, the bias
+ *                       only with PE_REWARDS_INACTIVITY).  The bounds are conservative: they pair maxima that need not
+ *                       meet in one validator.  balance + reward itself is not checked (it needs a balance above
+ *                       2^63 Gwei) and wraps. */
+int pe_rewards_and_penalties(pe_engine* h, uint64_t current_epoch, uint64_t finalized_epoch,
+                             const pe_rewards_params* params, uint32_t which, pe_rewards_stats* out_stats);
+
+/* As `balances` of pe_effective_balance_updates: the resident vector, read by the kernel where pe_state_set_balances /
+ * pe_rewards_and_penalties left it -- no staging, no upload.  n must equal the registry size; without resident balances
+ * the call returns PE_ERR_STATE.  Every other argument and result of that call is as without it. */
+#define PE_BALANCES_RESIDENT ((const uint64_t*)(uintptr_t)1)
 
 /* Plain G1 sum over caller-chosen groups: out[g] = sum_{j in [offsets[g], offsets[g+1])}
  * points[index[j]] (index NULL = identity).  points96 NULL = the validators' pubkeys. */

@@ -11,7 +11,7 @@ the thin Python host layer above it:
 Import never falls back to a CPU implementation: without the built library it raises.
 """
 from . import _abi
-from .engine import ACTIVE_RESIDENT, RESIDENT, ROWS_RESIDENT, AttRow, DeviceArena, DeviceRows, Engine, EngineError, pack_attestations
+from .engine import ACTIVE_RESIDENT, BALANCES_RESIDENT, RESIDENT, ROWS_RESIDENT, AttRow, DeviceArena, DeviceRows, Engine, EngineError, pack_attestations
 
 __all__ = ["Engine", "EngineError", "AttRow", "DeviceArena", "DeviceRows", "pack_attestations", "RESIDENT", "ROWS_RESIDENT",
-           "ACTIVE_RESIDENT", "_abi"]
+           "ACTIVE_RESIDENT", "BALANCES_RESIDENT", "_abi"]

@@ -90,6 +90,21 @@ class pe_prune_stats(C.Structure):
                 ("votes_orphaned", C.c_uint64)]
 
 
+class pe_rewards_params(C.Structure):
+    """struct pe_rewards_params (include/posevo.h): the constants of pe_rewards_and_penalties."""
+    _fields_ = [("base_reward_factor", C.c_uint64), ("inactivity_score_bias", C.c_uint64),
+                ("inactivity_score_recovery_rate", C.c_uint64), ("inactivity_penalty_quotient", C.c_uint64),
+                ("min_epochs_to_inactivity_penalty", C.c_uint64)]
+
+
+class pe_rewards_stats(C.Structure):
+    """struct pe_rewards_stats (include/posevo.h): what one pe_rewards_and_penalties read and did."""
+    _fields_ = [("total_active_balance", C.c_uint64), ("unslashed_balance", C.c_uint64 * 3), ("n_eligible", C.c_uint64),
+                ("in_leak", C.c_uint64), ("rewards", C.c_uint64), ("penalties", C.c_uint64), ("n_saturated", C.c_uint64)]
+
+
+PE_REWARDS_INACTIVITY, PE_REWARDS_DELTAS = 1, 2
+
 _P = C.POINTER
 # Buffer arguments are declared void*: the wrappers pass raw addresses (engine._ptr), which costs 0.5 us per argument
 # against 2.8 us for ndarray.ctypes.data_as -- some twenty pointers cross the boundary per step.
@@ -161,6 +176,11 @@ SIGNATURES = {
     "pe_registry_get_epochs": (C.c_int, [_H, C.c_uint64, _u64p, _u64p, C.c_void_p]),
     "pe_active_set": (C.c_int, [_H, C.c_uint64, C.c_void_p, C.c_void_p, _u32p]),
     "pe_state_refresh_activity": (C.c_int, [_H, C.c_uint64]),
+    "pe_state_set_balances": (C.c_int, [_H, C.c_uint64, _u64p, _u64p, _u64p]),
+    "pe_state_get_balances": (C.c_int, [_H, C.c_uint64, _u64p, _u64p, _u64p, C.c_void_p]),
+    "pe_rewards_params_default": (None, [_P(pe_rewards_params)]),
+    "pe_rewards_and_penalties": (C.c_int, [_H, C.c_uint64, C.c_uint64, _P(pe_rewards_params), C.c_uint32,
+                                           _P(pe_rewards_stats)]),
     "pe_g1_sum": (C.c_int, [_H, _u8p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u8p]),
     "pe_prune": (C.c_int, [_H, C.c_void_p]),
     "pe_set_block_checkpoints": (C.c_int, [_H, C.c_uint32, C.c_uint64, _u8p, C.c_uint64, _u8p]),
@@ -225,6 +245,7 @@ SIGNATURES = {
 PE_ROWS_RESIDENT = 1  # include/posevo.h: "every group of the last pe_aggregate over rows in device memory"
 PE_BITS_RESIDENT = 1  # the address include/posevo.h defines as "bits are where the last pe_aggregate left them"
 PE_ACTIVE_RESIDENT = 1  # ... and as "the active list is where the last pe_active_set left it"
+PE_BALANCES_RESIDENT = 1  # ... and as "the balances are where pe_state_set_balances / pe_rewards_and_penalties left them"
 PE_ATT_FLAG_OVERLAPPING_BITS = 0x4
 PE_VOTE_PRUNED = 0xFFFFFFFE  # block index of a latest message whose block pe_prune removed (its epoch is kept)
 

@@ -545,7 +545,8 @@ void pe_engine_destroy(pe_engine* h)
                       &h->d_tpos, &h->d_tidx, &h->d_direct, &h->d_weights, &h->d_totals, &h->d_head,
                       &h->d_broot_tab, &h->d_broots, &h->d_bslot_pos,
                       &h->d_partials, &h->d_lane_partials, &h->d_out96, &h->d_tmp_points, &h->d_tmp_be, &h->d_tmp_points30,
-                      &h->d_activation_epoch, &h->d_exit_epoch, &h->d_active, &h->d_active_wg})
+                      &h->d_activation_epoch, &h->d_exit_epoch, &h->d_active, &h->d_active_wg,
+                      &h->d_rbalance, &h->d_inactivity, &h->d_withdrawable})
         b->release();
     if (h->ev_active_read) (void)hipEventDestroy(h->ev_active_read);
     for (auto& t : h->tables) {

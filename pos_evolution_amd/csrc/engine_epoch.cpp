@@ -8,11 +8,19 @@
 //                                   get_total_active_balance (pe:1268): k_active_compact (shuffle_kernels.hip)
 //   pe_state_refresh_activity       PE_VAL_ACTIVE / PE_VAL_ACTIVE_PREV of the working-state view from those epochs
 //   pe_compute_proposers            compute_proposer_index (pe:604-618), once per seed: k_proposer_sample (shuffle_kernels.hip)
-//   pe_effective_balance_updates    process_effective_balance_updates (pe:122-133): k_effective_balance_update (fc_kernels.hip)
+//   pe_state_set_balances / _get    state.balances, state.inactivity_scores (pe:112, pe:368-369) and Validator.withdrawable_epoch
+//                                   (pe:45): three u64 arrays in device memory
+//   pe_rewards_params_default       the constants of the two functions below
+//   pe_rewards_and_penalties        process_inactivity_updates and process_rewards_and_penalties (Altair; restated in
+//                                   tests/rewards_model.py) over those arrays: k_reward_sums, a host step, k_reward_apply
+//                                   (reward_kernels.hip; the rule per validator is reward_row.h)
+//   pe_effective_balance_updates    process_effective_balance_updates (pe:122-133): k_effective_balance_update (fc_kernels.hip),
+//                                   over the caller's balances or the resident ones (PE_BALANCES_RESIDENT)
 // All read and write the working-state view (d_sbalance / d_sflags / d_incr) and leave the justified-checkpoint data get_head
 // weighs (d_balance / d_flags) alone.  All are synchronous, single-GPU calls; inputs travel through the arena's pinned
 // staging block, results through its pinned output block.
 #include "engine_internal.h"
+#include "reward_row.h"
 
 using namespace posevo;
 
@@ -23,6 +31,8 @@ void registry_epochs_drop(pe_engine* h)
     h->epochs_set = false;
     h->active_valid = false;  // the buffer stays: a shuffle in flight may still read it, and nothing rewrites it here
 }
+
+void resident_balances_drop(pe_engine* h) { h->balances_set = false; }
 
 int materialise_state_view(pe_engine* h)
 {
@@ -293,6 +303,154 @@ int pe_compute_proposers(pe_engine* h, const uint8_t* seeds32, uint32_t n_seeds,
     return PE_OK;
 }
 
+int pe_state_set_balances(pe_engine* h, uint64_t n, const uint64_t* balances, const uint64_t* inactivity_scores,
+                          const uint64_t* withdrawable_epoch)
+{
+    if (!h || (n && !balances)) return PE_ERR_INVALID_ARG;
+    PE_TRY(enter(h));
+    if (n != h->n_val) return fail(h, PE_ERR_INVALID_ARG, "pe_state_set_balances: n differs from the registry size");
+    const size_t bytes = std::max<size_t>(64, 8 * n);
+    if (h->d_rbalance.cap < bytes || h->d_inactivity.cap < bytes || h->d_withdrawable.cap < bytes) {
+        h->balances_set = false;  // the arrays are re-allocated: what they held is gone whether or not all three succeed
+        HIP_TRY(h, h->d_rbalance.ensure(bytes));
+        HIP_TRY(h, h->d_inactivity.ensure(bytes));
+        HIP_TRY(h, h->d_withdrawable.ensure(bytes));
+    }
+    if (n) {
+        HIP_TRY(h, hipMemcpyAsync(h->d_rbalance.p, balances, 8 * n, hipMemcpyHostToDevice, h->stream));
+        if (inactivity_scores)
+            HIP_TRY(h, hipMemcpyAsync(h->d_inactivity.p, inactivity_scores, 8 * n, hipMemcpyHostToDevice, h->stream));
+        else
+            HIP_TRY(h, hipMemsetAsync(h->d_inactivity.p, 0, 8 * n, h->stream));
+        if (withdrawable_epoch)
+            HIP_TRY(h, hipMemcpyAsync(h->d_withdrawable.p, withdrawable_epoch, 8 * n, hipMemcpyHostToDevice, h->stream));
+        else
+            HIP_TRY(h, hipMemsetAsync(h->d_withdrawable.p, 0xFF, 8 * n, h->stream));  // FAR_FUTURE_EPOCH = 2^64 - 1
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    h->balances_set = true;
+    return PE_OK;
+}
+
+int pe_state_get_balances(pe_engine* h, uint64_t n, uint64_t* out_balances, uint64_t* out_inactivity_scores,
+                          uint64_t* out_withdrawable_epoch, int* out_is_set)
+{
+    if (!h) return PE_ERR_INVALID_ARG;
+    PE_TRY(enter(h));
+    if (n != h->n_val) return fail(h, PE_ERR_INVALID_ARG, "pe_state_get_balances: n differs from the registry size");
+    if (out_is_set) *out_is_set = h->balances_set ? 1 : 0;
+    if (n && h->balances_set) {
+        if (out_balances) HIP_TRY(h, hipMemcpyAsync(out_balances, h->d_rbalance.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
+        if (out_inactivity_scores)
+            HIP_TRY(h, hipMemcpyAsync(out_inactivity_scores, h->d_inactivity.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
+        if (out_withdrawable_epoch)
+            HIP_TRY(h, hipMemcpyAsync(out_withdrawable_epoch, h->d_withdrawable.p, 8 * n, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    return PE_OK;
+}
+
+void pe_rewards_params_default(pe_rewards_params* out)
+{
+    if (!out) return;
+    out->base_reward_factor = 64;
+    out->inactivity_score_bias = 4;
+    out->inactivity_score_recovery_rate = 16;
+    out->inactivity_penalty_quotient = 1ull << 24;  // INACTIVITY_PENALTY_QUOTIENT_BELLATRIX; Altair's own is 3 * 2^24
+    out->min_epochs_to_inactivity_penalty = 4;
+}
+
+int pe_rewards_and_penalties(pe_engine* h, uint64_t current_epoch, uint64_t finalized_epoch, const pe_rewards_params* params,
+                             uint32_t which, pe_rewards_stats* out_stats)
+{
+    if (!h || !params) return PE_ERR_INVALID_ARG;
+    PE_TRY(enter(h));
+    if (h->dist_ready())
+        return fail(h, PE_ERR_STATE, "pe_rewards_and_penalties: the handle exchanges with other ranks (pe_dist_init); "
+                                     "a sharded registry is not supported");
+    if (which == 0 || (which & ~(uint32_t)(PE_REWARDS_INACTIVITY | PE_REWARDS_DELTAS)))
+        return fail(h, PE_ERR_INVALID_ARG, "pe_rewards_and_penalties: which must be PE_REWARDS_INACTIVITY, PE_REWARDS_DELTAS or both");
+    if (!h->balances_set)
+        return fail(h, PE_ERR_STATE, "pe_rewards_and_penalties: no resident balances (pe_state_set_balances first)");
+    const uint64_t inc = h->cfg.effective_balance_increment;
+    const uint64_t bias = params->inactivity_score_bias;
+    uint64_t inactivity_divisor = 0;
+    if (inc == 0 || __builtin_mul_overflow(bias, params->inactivity_penalty_quotient, &inactivity_divisor) || inactivity_divisor == 0)
+        return fail(h, PE_ERR_INVALID_ARG, "pe_rewards_and_penalties: increment and inactivity_score_bias * "
+                                           "inactivity_penalty_quotient must be positive and fit 64 bits");
+    pe_rewards_stats stats;
+    memset(&stats, 0, sizeof stats);
+    if (current_epoch == 0) {  // both functions return at GENESIS_EPOCH
+        if (out_stats) *out_stats = stats;
+        return PE_OK;
+    }
+    const uint64_t previous_epoch = current_epoch - 1;  // get_previous_epoch: current_epoch >= 1 here
+    if (finalized_epoch > previous_epoch)
+        return fail(h, PE_ERR_INVALID_ARG, "pe_rewards_and_penalties: finalized_epoch lies after the previous epoch");
+    const bool in_leak = previous_epoch - finalized_epoch > params->min_epochs_to_inactivity_penalty;
+    const uint64_t n = h->n_val;
+    OutBlock ob(h);
+    const size_t off_sums = ob.alloc(8ull * REWARD_SUMS_Q * REWARD_SUMS_MAX_WG);
+    const size_t off_apply = ob.alloc(8ull * REWARD_APPLY_Q * REWARD_APPLY_MAX_WG);
+    PE_TRY(ob.ensure());
+    PE_TRY(materialise_state_view(h));  // the view still mirrors the registry: a view of its own first, as the balance update does
+
+    // ---- first pass: what the rule divides by, and the maxima its products are bounded with
+    uint64_t sums[REWARD_SUMS_Q] = {0, 0, 0, 0, 0, 0, 0};
+    if (n) {
+        const uint32_t blocks = launch_reward_sums(h->stream, h->d_sbalance.as<uint64_t>(), h->d_sflags.as<uint8_t>(),
+                                                   h->d_part_prev.as<uint8_t>(), h->d_inactivity.as<uint64_t>(),
+                                                   h->d_withdrawable.as<uint64_t>(), n, previous_epoch + 1,
+                                                   ob.dev<uint64_t>(off_sums));
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, ob.download(off_sums, 8ull * REWARD_SUMS_Q * blocks));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        const uint64_t* p = ob.host<uint64_t>(off_sums);
+        for (uint32_t b = 0; b < blocks; ++b)
+            for (int q = 0; q < REWARD_SUMS_Q; ++q) {
+                const uint64_t x = p[(size_t)REWARD_SUMS_Q * b + q];
+                sums[q] = q < 5 ? sums[q] + x : std::max(sums[q], x);
+            }
+    }
+    const uint64_t total_active = std::max(inc, sums[0]);  // get_total_balance's floor (Appendix A.1), as pe_ffg_balances
+    const uint64_t max_eff = sums[5], max_score = sums[6];
+    stats.total_active_balance = total_active;
+    for (int f = 0; f < 3; ++f) stats.unslashed_balance[f] = std::max(inc, sums[1 + f]);
+    stats.n_eligible = sums[4];
+    stats.in_leak = in_leak ? 1 : 0;
+
+    // ---- host step (reward_row.h): the scalars, and every place the reference's uint64 would overflow -- before anything is written
+    RewardScalars S;
+    memset(&S, 0, sizeof S);
+    static const char* const overflow_of[] = {"", "increment * base_reward_factor", "active increments * WEIGHT_DENOMINATOR",
+                                              "base_reward * weight * unslashed increments", "inactivity score + bias",
+                                              "effective_balance * inactivity score"};
+    const int over = reward_scalars_make(inc, params->base_reward_factor, bias, params->inactivity_score_recovery_rate,
+                                         inactivity_divisor, total_active, stats.unslashed_balance, max_eff, max_score,
+                                         previous_epoch, in_leak, which, &S);
+    if (over)
+        return fail(h, PE_ERR_INVALID_ARG, std::string("pe_rewards_and_penalties: ") + overflow_of[over] + " can exceed 64 bits");
+
+    // ---- second pass: the rule per validator
+    if (n) {
+        const uint32_t blocks = launch_reward_apply(h->stream, S, h->d_sbalance.as<uint64_t>(), h->d_sflags.as<uint8_t>(),
+                                                    h->d_part_prev.as<uint8_t>(), h->d_withdrawable.as<uint64_t>(), n,
+                                                    h->d_rbalance.as<uint64_t>(), h->d_inactivity.as<uint64_t>(),
+                                                    ob.dev<uint64_t>(off_apply));
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, ob.download(off_apply, 8ull * REWARD_APPLY_Q * blocks));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        const uint64_t* p = ob.host<uint64_t>(off_apply);
+        for (uint32_t b = 0; b < blocks; ++b) {
+            stats.rewards += p[(size_t)REWARD_APPLY_Q * b + 0];
+            stats.penalties += p[(size_t)REWARD_APPLY_Q * b + 1];
+            stats.n_saturated += p[(size_t)REWARD_APPLY_Q * b + 2];
+        }
+    }
+    if (out_stats) *out_stats = stats;
+    return PE_OK;
+}
+
 int pe_effective_balance_updates(pe_engine* h, uint64_t n, const uint64_t* balances, uint64_t max_effective_balance,
                                  uint64_t hysteresis_quotient, uint64_t downward_multiplier, uint64_t upward_multiplier,
                                  uint64_t* out_n_changed, uint64_t* out_effective_balance)
@@ -303,6 +461,9 @@ int pe_effective_balance_updates(pe_engine* h, uint64_t n, const uint64_t* balan
         return fail(h, PE_ERR_STATE, "pe_effective_balance_updates: the handle exchanges with other ranks (pe_dist_init); "
                                      "a sharded registry is not supported");
     if (n != h->n_val) return fail(h, PE_ERR_INVALID_ARG, "pe_effective_balance_updates: n differs from the registry size");
+    const bool resident = balances == PE_BALANCES_RESIDENT;  // read where pe_state_set_balances / pe_rewards_and_penalties left them
+    if (resident && !h->balances_set)
+        return fail(h, PE_ERR_STATE, "PE_BALANCES_RESIDENT: the handle holds no resident balances (pe_state_set_balances first)");
     const uint64_t inc = h->cfg.effective_balance_increment;
     if (inc == 0 || hysteresis_quotient == 0)
         return fail(h, PE_ERR_INVALID_ARG, "pe_effective_balance_updates: increment and hysteresis quotient must be positive");
@@ -314,9 +475,12 @@ int pe_effective_balance_updates(pe_engine* h, uint64_t n, const uint64_t* balan
     *out_n_changed = 0;
     if (n == 0) return PE_OK;
     Stage st(h);
-    PE_TRY(st.reserve(8ull * n + 1024));
-    const size_t off_bal = st.alloc(8ull * n);
-    memcpy(st.host<uint64_t>(off_bal), balances, 8ull * n);
+    size_t off_bal = 0;
+    if (!resident) {
+        PE_TRY(st.reserve(8ull * n + 1024));
+        off_bal = st.alloc(8ull * n);
+        memcpy(st.host<uint64_t>(off_bal), balances, 8ull * n);
+    }
     OutBlock ob(h);
     const size_t off_cnt = ob.alloc(8);
     const size_t off_eff = out_effective_balance ? ob.alloc(8ull * n) : 0;
@@ -324,7 +488,7 @@ int pe_effective_balance_updates(pe_engine* h, uint64_t n, const uint64_t* balan
     PE_TRY(materialise_state_view(h));  // the view still mirrors the registry: a view of its own first, flags included
     HIP_TRY(h, st.upload());
     HIP_TRY(h, hipMemsetAsync(ob.dev<uint64_t>(off_cnt), 0, 8, h->stream));
-    launch_effective_balance_update(h->stream, st.dev<uint64_t>(off_bal), h->d_sbalance.as<uint64_t>(),
+    launch_effective_balance_update(h->stream, resident ? h->d_rbalance.as<uint64_t>() : st.dev<uint64_t>(off_bal), h->d_sbalance.as<uint64_t>(),
                                     h->d_incr.as<uint16_t>(), n, inc, down, up, max_effective_balance,
                                     ob.dev<uint64_t>(off_cnt));
     HIP_TRY(h, hipGetLastError());

@@ -11,7 +11,8 @@
 //   engine_dist.cpp    multi-GPU exchange: RCCL owned by the engine, function-table collectives
 //   engine_slash.cpp   slashing detection: the per-validator vote history and its scan (double and surround votes)
 //   engine_epoch.cpp   the working-state view (validators, participation flags, FFG balances) and the epoch boundary over
-//                      it: the active set, proposer sampling and the effective-balance hysteresis
+//                      it: the active set, proposer sampling, rewards and penalties over resident balances and the
+//                      effective-balance hysteresis
 // The row rules host and device share (bits inside the arena, committee position) are att_row.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -234,6 +235,9 @@ struct pe_engine {
     uint32_t active_n = 0;
     hipEvent_t ev_active_read = nullptr;  // behind the last pe_compute_committees_async that reads d_active, on its stream
     bool active_read_pending = false;     // ... and the engine's stream has not waited for it yet
+    // ---- resident balances (engine_epoch.cpp: pe_state_set_balances, pe_rewards_and_penalties) ----
+    DevBuf d_rbalance, d_inactivity, d_withdrawable;  // state.balances | state.inactivity_scores | Validator.withdrawable_epoch
+    bool balances_set = false;                        // (pe:112, pe:368-369, pe:45), u64[n_val] each; dropped where the epochs are
 
     // ---- tree snapshot (pre-order) ----
     bool tree_dirty = true;
@@ -600,6 +604,8 @@ inline const uint32_t* active_list_dev(const pe_engine* h, const uint32_t* activ
 }
 // registry epochs and the resident list say nothing about a new store or a registry of another size (engine_epoch.cpp)
 void registry_epochs_drop(pe_engine* h);
+// ... and neither do the resident balances, scores and withdrawable epochs (engine_epoch.cpp)
+void resident_balances_drop(pe_engine* h);
 // a working-state view that still mirrors the registry becomes a view of its own, flags included (engine_epoch.cpp)
 int materialise_state_view(pe_engine* h);
 

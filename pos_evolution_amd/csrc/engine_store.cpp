@@ -354,6 +354,7 @@ int pe_store_init(pe_engine* h, uint64_t genesis_time, uint64_t anchor_slot, con
     for (auto& t : h->tables) { t.n_committees = 0; t.offsets.clear(); t.is_partition = false; t.stamp = 0; }
     h->state_view_set = false;
     registry_epochs_drop(h);
+    resident_balances_drop(h);
     h->res_valid = false;
     h->rr.valid = false;
     PE_TRY(slasher_reset(h));  // what the validators of the previous store attested says nothing about this one
@@ -434,7 +435,10 @@ int pe_set_validators(pe_engine* h, uint64_t n, const uint8_t* pubkeys96, const 
     }
     if (h->d_totals.p) HIP_TRY(h, hipMemsetAsync(h->d_totals.p, 0, h->d_totals.cap, h->stream));  // grid may shrink
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (n != old_n) registry_epochs_drop(h);  // u64[old_n] arrays and a list of the old registry
+    if (n != old_n) {  // u64[old_n] arrays and a list of the old registry
+        registry_epochs_drop(h);
+        resident_balances_drop(h);
+    }
     h->n_val = n;
     return PE_OK;
 }

@@ -479,6 +479,22 @@ void launch_effective_balance_update(hipStream_t s, const uint64_t* balances, ui
                                      uint64_t n_val, uint64_t increment, uint64_t downward_threshold,
                                      uint64_t upward_threshold, uint64_t max_eff, uint64_t* n_changed);
 
+// process_inactivity_updates / process_rewards_and_penalties over the resident balances (reward_kernels.hip; the rule per
+// validator and its scalar block are reward_row.h).  Both return the number of workgroups launched = rows of `partials`.
+//   launch_reward_sums   partials[wg][REWARD_SUMS_Q]: total active balance, the three unslashed participating balances, the
+//                        eligible count (sums), the largest effective balance and score among the eligible (maxima)
+//   launch_reward_apply  scores and balances in place; partials[wg][REWARD_APPLY_Q]: rewards credited, penalties debited,
+//                        validators with a subtraction cut at 0 (sums)
+struct RewardScalars;
+constexpr int REWARD_SUMS_Q = 7, REWARD_APPLY_Q = 3;
+constexpr uint32_t REWARD_SUMS_MAX_WG = 256, REWARD_APPLY_MAX_WG = 2048;
+uint32_t launch_reward_sums(hipStream_t s, const uint64_t* eff_balance, const uint8_t* sflags, const uint8_t* part_prev,
+                            const uint64_t* scores, const uint64_t* withdrawable, uint64_t n_val, uint64_t previous_plus_1,
+                            uint64_t* partials);
+uint32_t launch_reward_apply(hipStream_t s, const RewardScalars& S, const uint64_t* eff_balance, const uint8_t* sflags,
+                             const uint8_t* part_prev, const uint64_t* withdrawable, uint64_t n_val, uint64_t* balances,
+                             uint64_t* scores, uint64_t* partials);
+
 // compute_proposer_index (pe:604-618), one wave per seed (d_seeds_be: 8 big-endian words each): d_out_proposer[s] = the
 // first accepted candidate of seed s, d_out_tries[s] = the i it was accepted at; NONE32 / max_tries when none of the first
 // max_tries candidates was.  total >= 1 entries of d_indices (null = identity), every one an index into d_eff_balance;

@@ -171,6 +171,19 @@ class _ActiveResident:
 ACTIVE_RESIDENT = _ActiveResident()
 
 
+class _BalancesResident:
+    """Sentinel for ``balances`` of ``effective_balance_updates``: the vector ``state_set_balances`` /
+    ``rewards_and_penalties`` left on the device (PE_BALANCES_RESIDENT, include/posevo.h)."""
+
+    def __repr__(self):
+        return "BALANCES_RESIDENT"
+
+
+BALANCES_RESIDENT = _BalancesResident()
+_BALANCES_RESIDENT_ARG = DeviceArena(_abi.PE_BALANCES_RESIDENT, 0)   # the sentinel address, as _ptr passes it on
+REWARDS_INACTIVITY, REWARDS_DELTAS = _abi.PE_REWARDS_INACTIVITY, _abi.PE_REWARDS_DELTAS
+
+
 class AggregateResult(dict):
     """Result of Engine.aggregate; ``res["bits"]`` decodes the OR-ed bitfields on demand."""
 
@@ -806,15 +819,66 @@ class Engine:
     def effective_balance_updates(self, balances, max_effective_balance: int = 32 * 10**9, hysteresis_quotient: int = 4,
                                   downward_multiplier: int = 1, upward_multiplier: int = 5, want_result: bool = True):
         """process_effective_balance_updates (pe:122-133) on the working-state view, in place.  balances: state.balances
-        (one per validator).  -> (n_changed, new effective balances uint64[n] | None when not want_result)."""
-        bal = np.ascontiguousarray(balances, dtype=np.uint64)
-        out = np.empty(max(bal.size, 1), dtype=np.uint64) if want_result else None
+        (one per validator), or BALANCES_RESIDENT: the vector on the device, read where it lies.
+        -> (n_changed, new effective balances uint64[n] | None when not want_result)."""
+        if balances is BALANCES_RESIDENT:
+            bal, n = _BALANCES_RESIDENT_ARG, self.num_validators
+        else:
+            bal = np.ascontiguousarray(balances, dtype=np.uint64)
+            n = bal.size
+            if not n:
+                bal = None
+        out = np.empty(max(n, 1), dtype=np.uint64) if want_result else None
         n_changed = C.c_uint64(0)
-        self._check(self._lib.pe_effective_balance_updates(self._h, bal.size, _ptr(bal if bal.size else None, C.c_uint64),
+        self._check(self._lib.pe_effective_balance_updates(self._h, n, _ptr(bal, C.c_uint64),
                                                            int(max_effective_balance), int(hysteresis_quotient),
                                                            int(downward_multiplier), int(upward_multiplier),
                                                            C.addressof(n_changed), _ptr(out, C.c_uint64)))
-        return int(n_changed.value), (out[:bal.size] if want_result else None)
+        return int(n_changed.value), (out[:n] if want_result else None)
+
+    # -- rewards and penalties over resident balances ----------------------
+    def state_set_balances(self, balances, inactivity_scores=None, withdrawable_epoch=None):
+        """state.balances, state.inactivity_scores (None = zeros) and Validator.withdrawable_epoch (None =
+        FAR_FUTURE_EPOCH everywhere) of the whole registry -> device memory (pe_state_set_balances).  (``set_balances``
+        is pe_set_balances: the justified state's effective balances.)"""
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.uint64)
+                for a in (balances, inactivity_scores, withdrawable_epoch)]
+        n = arrs[0].size
+        assert all(a is None or a.size == n for a in arrs), "one balance, score and withdrawable epoch per validator"
+        self._check(self._lib.pe_state_set_balances(self._h, n, *(_ptr(a if n else None, C.c_uint64) for a in arrs)))
+
+    def state_get_balances(self):
+        """-> (balances, inactivity_scores, withdrawable_epoch: uint64[n] each, is_set); is_set False: the handle holds none."""
+        n = self.num_validators
+        bal, sc, wd = (np.zeros(max(n, 1), dtype=np.uint64) for _ in range(3))
+        is_set = C.c_int(0)
+        self._check(self._lib.pe_state_get_balances(self._h, n, _ptr(bal), _ptr(sc), _ptr(wd), C.addressof(is_set)))
+        return bal[:n], sc[:n], wd[:n], bool(is_set.value)
+
+    def rewards_params(self, **overrides):
+        """pe_rewards_params_default with fields replaced by keyword (base_reward_factor, inactivity_score_bias,
+        inactivity_score_recovery_rate, inactivity_penalty_quotient, min_epochs_to_inactivity_penalty)."""
+        p = _abi.pe_rewards_params()
+        self._lib.pe_rewards_params_default(C.byref(p))
+        for k, v in overrides.items():
+            assert hasattr(p, k), k
+            setattr(p, k, int(v))
+        return p
+
+    def rewards_and_penalties(self, current_epoch: int, finalized_epoch: int, params=None,
+                              which: int = REWARDS_INACTIVITY | REWARDS_DELTAS) -> dict:
+        """process_inactivity_updates (REWARDS_INACTIVITY) and process_rewards_and_penalties (REWARDS_DELTAS) over the
+        resident balances and scores, in place (pe_rewards_and_penalties).  params: ``rewards_params(...)``, a dict of its
+        overrides, or None for the defaults.  -> pe_rewards_stats as a dict."""
+        if params is None or isinstance(params, dict):
+            params = self.rewards_params(**(params or {}))
+        st = _abi.pe_rewards_stats()
+        self._check(self._lib.pe_rewards_and_penalties(self._h, int(current_epoch), int(finalized_epoch), C.byref(params),
+                                                       int(which), C.byref(st)))
+        return {"total_active_balance": int(st.total_active_balance),
+                "unslashed_balance": [int(x) for x in st.unslashed_balance], "n_eligible": int(st.n_eligible),
+                "in_leak": int(st.in_leak), "rewards": int(st.rewards), "penalties": int(st.penalties),
+                "n_saturated": int(st.n_saturated)}
 
     def g1_sum(self, offsets, index=None, points96=None) -> np.ndarray:
         off = np.ascontiguousarray(offsets, dtype=np.uint32)

@@ -15,6 +15,8 @@ pos-evolution.md (``pe:N``):
     process_attestation(state, attestation)                 pe:722-754    (state bound with bind_state)
     compute_proposer_index(state, indices, seed)            pe:604-618    (state bound with bind_state)
     process_effective_balance_updates(state)                pe:122-133    (state bound with bind_state)
+    process_inactivity_updates(state)                       Altair; fields pe:368-369 (state bound with bind_state)
+    process_rewards_and_penalties(state)                    Altair; fields pe:112, pe:45 (state bound with bind_state)
     get_active_validator_indices(state, epoch)              named at pe:467 (state bound with bind_state)
     get_committee_count_per_slot(state, epoch)              pe:461-468
     compute_weak_subjectivity_period(state)                 pe:1257-1287
@@ -541,6 +543,42 @@ def process_effective_balance_updates(state, *, max_effective_balance: int = MAX
     if n_changed:
         for validator, value in zip(state.validators, new):
             validator.effective_balance = int(value)
+
+
+# ----------------------------------------------------------------------------- rewards and penalties
+def _rewards_call(state, which: int, params: dict, who: str) -> dict:
+    """Hand state.balances, state.inactivity_scores and the validators' withdrawable epochs to the engine, run the
+    part(s) of pe_rewards_and_penalties `which` names over the binding's working-state view and write balances and scores
+    back.  (A caller that keeps them on the device between epochs uses Engine.rewards_and_penalties itself.)"""
+    b = _binding(state)
+    assert b is not None, who + ": bind_state(engine, state, ...) first"
+    n = len(state.validators)
+    balances = np.fromiter((int(x) for x in state.balances), dtype=np.uint64, count=n)
+    scores = np.fromiter((int(x) for x in state.inactivity_scores), dtype=np.uint64, count=n)
+    withdrawable = np.fromiter((int(v.withdrawable_epoch) for v in state.validators), dtype=np.uint64, count=n)
+    b.engine.state_set_balances(balances, scores, withdrawable)
+    current_epoch = int(state.slot) // int(b.engine.cfg.slots_per_epoch)
+    stats = b.engine.rewards_and_penalties(current_epoch, int(state.finalized_checkpoint.epoch), params, which)
+    new_balances, new_scores, _, _ = b.engine.state_get_balances()
+    if which & _abi.PE_REWARDS_DELTAS:
+        state.balances[:] = [int(x) for x in new_balances]
+    if which & _abi.PE_REWARDS_INACTIVITY:
+        state.inactivity_scores[:] = [int(x) for x in new_scores]
+    return stats
+
+
+def process_inactivity_updates(state, **params) -> None:
+    """Altair's process_inactivity_updates over ``state.inactivity_scores`` (pe:368-369), on the GPU.  ``state`` must
+    have been bound with ``bind_state`` (activity and slashed flags, effective balances and previous_epoch_participation
+    are the binding's).  Keywords replace fields of pe_rewards_params (inactivity_score_bias, ...)."""
+    state._last_rewards_stats = _rewards_call(state, _abi.PE_REWARDS_INACTIVITY, params, "process_inactivity_updates")
+
+
+def process_rewards_and_penalties(state, **params) -> None:
+    """Altair's process_rewards_and_penalties over ``state.balances`` (pe:112): the three flag-index delta pairs and the
+    inactivity penalties, applied pair by pair.  Call it after ``process_inactivity_updates``, as process_epoch does.
+    ``state`` must have been bound with ``bind_state``.  Keywords replace fields of pe_rewards_params."""
+    state._last_rewards_stats = _rewards_call(state, _abi.PE_REWARDS_DELTAS, params, "process_rewards_and_penalties")
 
 
 # ----------------------------------------------------------------------------- the active set and what is counted from it
