@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define PE_ABI_VERSION 12
+#define PE_ABI_VERSION 13
 
 typedef struct pe_engine pe_engine;
 
@@ -544,6 +544,58 @@ int pe_rewards_and_penalties(pe_engine* h, uint64_t current_epoch, uint64_t fina
  * pe_rewards_and_penalties left it -- no staging, no upload.  n must equal the registry size; without resident balances
  * the call returns PE_ERR_STATE.  Every other argument and result of that call is as without it. */
 #define PE_BALANCES_RESIDENT ((const uint64_t*)(uintptr_t)1)
+
+/* ---- SSZ roots of the resident per-validator lists -------------------------- */
+/* hash_tree_root (named at pe:142, 423, 1016; the reference holds no text of it) by the SSZ specification's rules: chunks of
+ * 32 bytes; basic values packed little-endian, the last chunk zero-padded; Z[0] = 32 zero bytes, Z[k+1] = H(Z[k] || Z[k]);
+ * merkleize(chunks, depth) = the root of the binary tree of 2^depth leaves whose absent leaves are Z[0];
+ * mix_in_length(root, n) = H(root || uint256_le(n)); H = SHA-256.  Restated in tests/ssz_model.py.
+ *
+ * The parts of Validator (pe:36-45) nothing else in the engine reads: pubkey (48 B compressed), withdrawal_credentials
+ * (32 B) and activation_eligibility_epoch of the whole registry.  Kept in device memory as the pubkey's 32-byte leaf
+ * H(pubkey[0:32] || pubkey[32:48] || 0^16) + 32 B + 8 B per validator.  n must equal pe_num_validators(h): else
+ * PE_ERR_INVALID_ARG and nothing changes.  Dropped where the working-state view is: pe_store_init, and a
+ * pe_set_validators that changes n.  _get: any output may be NULL; *out_is_set = 0: none held, nothing is written.
+ * Checkpoint / resume: _get for the credentials and epochs, the caller's own pubkeys, _set -- as with the epochs. */
+int pe_registry_set_static(pe_engine* h, uint64_t n, const uint8_t* pubkeys48, const uint8_t* withdrawal_credentials32,
+                           const uint64_t* activation_eligibility_epoch);
+int pe_registry_get_static(pe_engine* h, uint64_t n, uint8_t* out_pubkey_leaves32, uint8_t* out_withdrawal_credentials32,
+                           uint64_t* out_activation_eligibility_epoch, int* out_is_set);
+
+#define PE_ROOT_BALANCES   1u   /* List[Gwei, 2^limit_log2] over the resident balances (pe_state_set_balances) */
+#define PE_ROOT_INACTIVITY 2u   /* List[uint64, 2^limit_log2] over the resident inactivity scores */
+#define PE_ROOT_PART_PREV  4u   /* List[ParticipationFlags, 2^limit_log2] over previous_epoch_participation */
+#define PE_ROOT_PART_CUR   8u   /* ... over current_epoch_participation */
+#define PE_ROOT_VALIDATORS 16u  /* List[Validator, 2^limit_log2] */
+typedef struct pe_state_root_set {
+    uint8_t balances[32];
+    uint8_t inactivity_scores[32];
+    uint8_t previous_epoch_participation[32];
+    uint8_t current_epoch_participation[32];
+    uint8_t validators[32];
+} pe_state_root_set;
+/* The hash_tree_root of the BeaconState fields (pe:354-369) named by `which`, from the arrays where they lie in device
+ * memory; the fields of *out not asked for are left as they were.  Combining them with the state's other field roots into
+ * hash_tree_root(state) is a handful of hashes and stays with the caller.
+ * limit_log2: log2 of VALIDATOR_REGISTRY_LIMIT (0 = 40).  Tree depths: limit_log2 - 2 for the uint64 lists, limit_log2 - 5
+ * for the uint8 lists, limit_log2 for validators; each root is mixed with n = pe_num_validators(h).
+ * Validator: effective_balance and slashed (PE_VAL_SLASHED) are the working-state view's (pe_state_set_validators; the
+ * pe_set_validators data while the view mirrors it), activation / exit epochs the resident ones (pe_registry_set_epochs),
+ * withdrawable_epoch the one of pe_state_set_balances, the rest pe_registry_set_static's.
+ * out_validator_leaves (may be NULL; V x 32 B): hash_tree_root(Validator) of every validator, with PE_ROOT_VALIDATORS.
+ * Read-only: no resident array changes, the view is not materialised.  Synchronous (completes open pipelines first;
+ * ordered against the flag passes as pe_ffg_balances is); one GPU.  A failing call writes nothing to *out:
+ *   PE_ERR_INVALID_ARG  which is 0 or has other bits; limit_log2 above 64, below 5, or 2^limit_log2 < n
+ *   PE_ERR_STATE        an array `which` asks for is not resident (PE_ROOT_VALIDATORS needs the epochs, the balances and
+ *                       the static part), or pe_dist_init* active */
+int pe_state_roots(pe_engine* h, uint32_t which, uint32_t limit_log2, pe_state_root_set* out, uint8_t* out_validator_leaves);
+
+/* merkleize(chunks, depth) of n_chunks 32-byte chunks in host memory -- block_roots, state_roots, randao_mixes, any Vector
+ * or List of Bytes32 or of packed basic values -- through the same kernel.  mix_length >= 0: the root is mixed with that
+ * length; < 0: no mix-in.  n_chunks = 0 gives Z[depth].  n_chunks > 2^depth or depth > 64: PE_ERR_INVALID_ARG, out_root
+ * is not written.  Synchronous. */
+int pe_ssz_merkleize(pe_engine* h, const uint8_t* chunks32, uint64_t n_chunks, uint32_t depth, int64_t mix_length,
+                     uint8_t out_root[32]);
 
 /* Plain G1 sum over caller-chosen groups: out[g] = sum_{j in [offsets[g], offsets[g+1])}
  * points[index[j]] (index NULL = identity).  points96 NULL = the validators' pubkeys. */

@@ -97,6 +97,13 @@ class pe_rewards_params(C.Structure):
                 ("min_epochs_to_inactivity_penalty", C.c_uint64)]
 
 
+class pe_state_root_set(C.Structure):
+    """struct pe_state_root_set (include/posevo.h): the five per-validator field roots of BeaconState."""
+    _fields_ = [("balances", C.c_uint8 * 32), ("inactivity_scores", C.c_uint8 * 32),
+                ("previous_epoch_participation", C.c_uint8 * 32), ("current_epoch_participation", C.c_uint8 * 32),
+                ("validators", C.c_uint8 * 32)]
+
+
 class pe_rewards_stats(C.Structure):
     """struct pe_rewards_stats (include/posevo.h): what one pe_rewards_and_penalties read and did."""
     _fields_ = [("total_active_balance", C.c_uint64), ("unslashed_balance", C.c_uint64 * 3), ("n_eligible", C.c_uint64),
@@ -104,6 +111,7 @@ class pe_rewards_stats(C.Structure):
 
 
 PE_REWARDS_INACTIVITY, PE_REWARDS_DELTAS = 1, 2
+PE_ROOT_BALANCES, PE_ROOT_INACTIVITY, PE_ROOT_PART_PREV, PE_ROOT_PART_CUR, PE_ROOT_VALIDATORS = 1, 2, 4, 8, 16
 
 _P = C.POINTER
 # Buffer arguments are declared void*: the wrappers pass raw addresses (engine._ptr), which costs 0.5 us per argument
@@ -181,6 +189,10 @@ SIGNATURES = {
     "pe_rewards_params_default": (None, [_P(pe_rewards_params)]),
     "pe_rewards_and_penalties": (C.c_int, [_H, C.c_uint64, C.c_uint64, _P(pe_rewards_params), C.c_uint32,
                                            _P(pe_rewards_stats)]),
+    "pe_registry_set_static": (C.c_int, [_H, C.c_uint64, _u8p, _u8p, _u64p]),
+    "pe_registry_get_static": (C.c_int, [_H, C.c_uint64, _u8p, _u8p, _u64p, C.c_void_p]),
+    "pe_state_roots": (C.c_int, [_H, C.c_uint32, C.c_uint32, _P(pe_state_root_set), _u8p]),
+    "pe_ssz_merkleize": (C.c_int, [_H, _u8p, C.c_uint64, C.c_uint32, C.c_int64, _u8p]),
     "pe_g1_sum": (C.c_int, [_H, _u8p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u8p]),
     "pe_prune": (C.c_int, [_H, C.c_void_p]),
     "pe_set_block_checkpoints": (C.c_int, [_H, C.c_uint32, C.c_uint64, _u8p, C.c_uint64, _u8p]),

@@ -10,6 +10,7 @@
 //   engine_g1.cpp      G1 / G2 sums over caller-chosen groups, BLSPubkey / BLSSignature wire formats
 //   engine_dist.cpp    multi-GPU exchange: RCCL owned by the engine, function-table collectives
 //   engine_slash.cpp   slashing detection: the per-validator vote history and its scan (double and surround votes)
+//   engine_ssz.cpp     SSZ hash_tree_root of the resident per-validator lists, merkleize of caller chunks
 //   engine_epoch.cpp   the working-state view (validators, participation flags, FFG balances) and the epoch boundary over
 //                      it: the active set, proposer sampling, rewards and penalties over resident balances and the
 //                      effective-balance hysteresis
@@ -238,6 +239,16 @@ struct pe_engine {
     // ---- resident balances (engine_epoch.cpp: pe_state_set_balances, pe_rewards_and_penalties) ----
     DevBuf d_rbalance, d_inactivity, d_withdrawable;  // state.balances | state.inactivity_scores | Validator.withdrawable_epoch
     bool balances_set = false;                        // (pe:112, pe:368-369, pe:45), u64[n_val] each; dropped where the epochs are
+    // ---- SSZ roots (engine_ssz.cpp) ----
+    // the static part of Validator (pe:37-38, 41): H(pubkey) u8[n_val][32] | withdrawal_credentials u8[n_val][32] |
+    // activation_eligibility_epoch u64[n_val]; dropped where the epochs are
+    DevBuf d_pubkey_leaf, d_withdrawal_credentials, d_activation_eligibility;
+    bool static_set = false;
+    DevBuf d_ssz_zero;             // Z[0 .. 64], word form
+    bool ssz_zero_ready = false;
+    DevBuf d_ssz_validator_roots;  // hash_tree_root(Validator) of every validator, u8[n_val][32]: the leaves of `validators`
+    DevBuf d_ssz_level[2];         // the nodes between two passes of k_ssz_merkle, word form
+    DevBuf d_ssz_chunks;           // pe_ssz_merkleize: the caller's chunks
 
     // ---- tree snapshot (pre-order) ----
     bool tree_dirty = true;
@@ -378,6 +389,8 @@ struct pe_engine {
         int sig_batch = env("POSEVO_SIG_BATCH", 8);
         // pe_engine_create asks the device which of its streams share a hardware queue and keeps four that do not (engine_core.cpp)
         int queue_probe = env("POSEVO_QUEUE_PROBE", 1);
+        // log2 of the nodes one workgroup of k_ssz_merkle reduces per pass; for measurement
+        uint32_t ssz_tile_log2 = (uint32_t)std::min<int>(SSZ_TILE_LOG2, std::max<int>(SSZ_TILE_LOG2_MIN, env("POSEVO_SSZ_TILE_LOG2", SSZ_TILE_LOG2)));
     } tune;
 
     // ---- device-resident hand-over of the last pe_aggregate (PE_BITS_RESIDENT) ----
@@ -606,6 +619,8 @@ inline const uint32_t* active_list_dev(const pe_engine* h, const uint32_t* activ
 void registry_epochs_drop(pe_engine* h);
 // ... and neither do the resident balances, scores and withdrawable epochs (engine_epoch.cpp)
 void resident_balances_drop(pe_engine* h);
+// ... nor the static part of the validators (engine_ssz.cpp)
+void registry_static_drop(pe_engine* h);
 // a working-state view that still mirrors the registry becomes a view of its own, flags included (engine_epoch.cpp)
 int materialise_state_view(pe_engine* h);
 

@@ -355,6 +355,7 @@ int pe_store_init(pe_engine* h, uint64_t genesis_time, uint64_t anchor_slot, con
     h->state_view_set = false;
     registry_epochs_drop(h);
     resident_balances_drop(h);
+    registry_static_drop(h);
     h->res_valid = false;
     h->rr.valid = false;
     PE_TRY(slasher_reset(h));  // what the validators of the previous store attested says nothing about this one
@@ -438,6 +439,7 @@ int pe_set_validators(pe_engine* h, uint64_t n, const uint8_t* pubkeys96, const 
     if (n != old_n) {  // u64[old_n] arrays and a list of the old registry
         registry_epochs_drop(h);
         resident_balances_drop(h);
+        registry_static_drop(h);
     }
     h->n_val = n;
     return PE_OK;

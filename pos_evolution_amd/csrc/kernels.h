@@ -527,4 +527,33 @@ void launch_activity_flags(hipStream_t s, const uint64_t* d_activation_epoch, co
 int launch_shuffle(hipStream_t s, const uint32_t* d_seed_be, uint32_t n, uint32_t rounds, uint32_t* d_source,
                    uint32_t* d_pivots, const uint32_t* d_indices, uint32_t* d_members);
 
+// SSZ merkleisation (ssz_kernels.hip).  A node is 8 words; between passes nodes travel as SHA's big-endian
+// words ("word form"), the first pass of a list reads the bytes where they lie.
+constexpr uint32_t SSZ_TILE_LOG2 = 10;     // T = 1024 nodes per workgroup and pass, 512 lanes
+constexpr uint32_t SSZ_TILE_LOG2_MIN = 6;  // the smallest tile POSEVO_SSZ_TILE_LOG2 may ask for (one wave)
+constexpr uint32_t SSZ_ZERO_HASHES = 65;   // Z[0] .. Z[64]
+// One pass: the nodes of height `base` in src -> the ceil(m / 2^levels) nodes of height base + levels in out (word form),
+// m = ceil(n_bytes / 32), levels <= SSZ_TILE_LOG2.  raw = 1: src is little-endian list bytes (packed basics or Bytes32
+// chunks), read in place, every byte at or beyond n_bytes taken as zero (whole 4-byte words of src are read up to the one
+// that holds byte n_bytes - 1); raw = 0: src is word-form nodes, n_bytes = 32 m.  A node without a right sibling pairs with
+// zero_words[8 * height ..]; a node with no child is not computed.  m >= 1.
+void launch_ssz_merkle(hipStream_t s, const void* src, uint64_t n_bytes, int raw, uint32_t base, uint32_t levels,
+                       const uint32_t* zero_words, uint32_t* out);
+// The 48 -> 32-byte pubkey leaf H(pk[0:32] || pk[32:48] || 0^16) of n keys, written as digest bytes.
+void launch_ssz_pubkey_roots(hipStream_t s, const uint8_t* pubkeys48, uint64_t n, uint8_t* out_leaves32);
+// hash_tree_root(Validator) (pe:36-45) of every validator, written as digest bytes: out_roots32[32 v ..].
+struct SszValidatorArgs {
+    const uint8_t* pubkey_leaf32;            // launch_ssz_pubkey_roots' output
+    const uint8_t* withdrawal_credentials32;
+    const uint64_t* effective_balance;       // the working-state view
+    const uint8_t* sflags;                   // ... its flags: VAL_SLASHED is Validator.slashed
+    const uint64_t* activation_eligibility_epoch;
+    const uint64_t* activation_epoch;
+    const uint64_t* exit_epoch;
+    const uint64_t* withdrawable_epoch;
+    uint64_t n_val;
+    uint8_t* out_roots32;
+};
+void launch_ssz_validator_roots(hipStream_t s, const SszValidatorArgs& a);
+
 }  // namespace posevo

@@ -182,6 +182,12 @@ class _BalancesResident:
 BALANCES_RESIDENT = _BalancesResident()
 _BALANCES_RESIDENT_ARG = DeviceArena(_abi.PE_BALANCES_RESIDENT, 0)   # the sentinel address, as _ptr passes it on
 REWARDS_INACTIVITY, REWARDS_DELTAS = _abi.PE_REWARDS_INACTIVITY, _abi.PE_REWARDS_DELTAS
+ROOT_BALANCES, ROOT_INACTIVITY, ROOT_PART_PREV, ROOT_PART_CUR, ROOT_VALIDATORS = (
+    _abi.PE_ROOT_BALANCES, _abi.PE_ROOT_INACTIVITY, _abi.PE_ROOT_PART_PREV, _abi.PE_ROOT_PART_CUR, _abi.PE_ROOT_VALIDATORS)
+ROOT_ALL = ROOT_BALANCES | ROOT_INACTIVITY | ROOT_PART_PREV | ROOT_PART_CUR | ROOT_VALIDATORS
+_ROOT_FIELDS = ((ROOT_BALANCES, "balances"), (ROOT_INACTIVITY, "inactivity_scores"),
+                (ROOT_PART_PREV, "previous_epoch_participation"), (ROOT_PART_CUR, "current_epoch_participation"),
+                (ROOT_VALIDATORS, "validators"))
 
 
 class AggregateResult(dict):
@@ -879,6 +885,54 @@ class Engine:
                 "unslashed_balance": [int(x) for x in st.unslashed_balance], "n_eligible": int(st.n_eligible),
                 "in_leak": int(st.in_leak), "rewards": int(st.rewards), "penalties": int(st.penalties),
                 "n_saturated": int(st.n_saturated)}
+
+    # -- SSZ roots of the resident lists ------------------------------------
+    def registry_set_static(self, pubkeys48, withdrawal_credentials, activation_eligibility_epoch):
+        """Validator.pubkey (n x 48 B compressed), withdrawal_credentials (n x 32 B) and activation_eligibility_epoch of
+        the whole registry -> device memory (pe_registry_set_static); the pubkeys are kept as their 32-byte leaves."""
+        pk = np.ascontiguousarray(pubkeys48, dtype=np.uint8).reshape(-1, 48)
+        wc = np.ascontiguousarray(withdrawal_credentials, dtype=np.uint8).reshape(-1, 32)
+        el = np.ascontiguousarray(activation_eligibility_epoch, dtype=np.uint64)
+        n = el.size
+        assert pk.shape[0] == n and wc.shape[0] == n, "one pubkey, one credential and one epoch per validator"
+        self._check(self._lib.pe_registry_set_static(self._h, n, _ptr(pk if n else None, C.c_uint8),
+                                                     _ptr(wc if n else None, C.c_uint8), _ptr(el if n else None, C.c_uint64)))
+
+    def registry_static(self):
+        """-> (pubkey leaves uint8[n, 32], withdrawal_credentials uint8[n, 32], activation_eligibility_epoch uint64[n],
+        is_set); is_set False: the handle holds none."""
+        n = self.num_validators
+        leaf, wc = np.zeros((max(n, 1), 32), dtype=np.uint8), np.zeros((max(n, 1), 32), dtype=np.uint8)
+        el, is_set = np.zeros(max(n, 1), dtype=np.uint64), C.c_int(0)
+        self._check(self._lib.pe_registry_get_static(self._h, n, _ptr(leaf), _ptr(wc), _ptr(el), C.addressof(is_set)))
+        return leaf[:n], wc[:n], el[:n], bool(is_set.value)
+
+    def state_roots(self, which: int = ROOT_ALL, limit_log2: int = 40, want_leaves: bool = False) -> dict:
+        """hash_tree_root of the BeaconState fields named by ``which`` (ROOT_* bits) from the resident arrays
+        (pe_state_roots).  -> {field name: 32 bytes} for the fields asked for; with want_leaves and ROOT_VALIDATORS also
+        "validator_leaves": uint8[n, 32], hash_tree_root(Validator) of every validator."""
+        out = _abi.pe_state_root_set()
+        leaves = None
+        if want_leaves and (which & ROOT_VALIDATORS):
+            leaves = np.zeros((max(self.num_validators, 1), 32), dtype=np.uint8)
+        self._check(self._lib.pe_state_roots(self._h, int(which), int(limit_log2), C.byref(out), _ptr(leaves, C.c_uint8)))
+        res = {name: bytes(getattr(out, name)) for bit, name in _ROOT_FIELDS if which & bit}
+        if leaves is not None:
+            res["validator_leaves"] = leaves[:self.num_validators]
+        return res
+
+    def ssz_merkleize(self, chunks, depth: int, mix_length: Optional[int] = None) -> bytes:
+        """merkleize(chunks, depth) of 32-byte chunks in host memory (bytes, or a uint8 array of n x 32) on the GPU;
+        mix_length: mix_in_length with it (None = no mix-in).  -> the 32-byte root."""
+        if isinstance(chunks, (bytes, bytearray, memoryview)):
+            ch = np.frombuffer(bytes(chunks), dtype=np.uint8)
+        else:
+            ch = np.ascontiguousarray(chunks, dtype=np.uint8).reshape(-1)
+        assert ch.size % 32 == 0, "chunks are 32 bytes each"
+        out = np.zeros(32, dtype=np.uint8)
+        self._check(self._lib.pe_ssz_merkleize(self._h, _ptr(ch if ch.size else None, C.c_uint8), ch.size // 32, int(depth),
+                                               -1 if mix_length is None else int(mix_length), _ptr(out, C.c_uint8)))
+        return out.tobytes()
 
     def g1_sum(self, offsets, index=None, points96=None) -> np.ndarray:
         off = np.ascontiguousarray(offsets, dtype=np.uint32)
