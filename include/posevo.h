@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define PE_ABI_VERSION 13
+#define PE_ABI_VERSION 14
 
 typedef struct pe_engine pe_engine;
 
@@ -544,6 +544,83 @@ int pe_rewards_and_penalties(pe_engine* h, uint64_t current_epoch, uint64_t fina
  * pe_rewards_and_penalties left it -- no staging, no upload.  n must equal the registry size; without resident balances
  * the call returns PE_ERR_STATE.  Every other argument and result of that call is as without it. */
 #define PE_BALANCES_RESIDENT ((const uint64_t*)(uintptr_t)1)
+
+/* ---- registry updates and slashings over the resident registry -------------- */
+/* The constants process_registry_updates reads. */
+typedef struct pe_registry_params {
+    uint64_t max_effective_balance;                 /* MAX_EFFECTIVE_BALANCE */
+    uint64_t ejection_balance;                      /* EJECTION_BALANCE */
+    uint64_t max_seed_lookahead;                    /* MAX_SEED_LOOKAHEAD */
+    uint64_t min_validator_withdrawability_delay;   /* MIN_VALIDATOR_WITHDRAWABILITY_DELAY */
+    uint64_t min_per_epoch_churn_limit;             /* MIN_PER_EPOCH_CHURN_LIMIT */
+    uint64_t churn_limit_quotient;                  /* CHURN_LIMIT_QUOTIENT */
+    uint64_t max_per_epoch_activation_churn_limit;  /* MAX_PER_EPOCH_ACTIVATION_CHURN_LIMIT; 0 = none (pre-Deneb); Deneb: 8 */
+} pe_registry_params;
+/* 32e9, 16e9, 4, 256, 4, 65536, 0 */
+void pe_registry_params_default(pe_registry_params* out);
+
+typedef struct pe_registry_stats {
+    uint64_t n_active;                /* len(get_active_validator_indices(state, current_epoch)) */
+    uint64_t churn_limit;             /* get_validator_churn_limit: max(min_per_epoch_churn_limit, n_active / quotient) */
+    uint64_t activation_churn_limit;  /* min(max_per_epoch_activation_churn_limit, churn_limit); the cap 0 = none */
+    uint64_t n_marked_eligible;       /* validators whose activation_eligibility_epoch became current_epoch + 1 */
+    uint64_t n_ejected;               /* validators whose exit was initiated (it was FAR_FUTURE_EPOCH before) */
+    uint64_t first_exit_epoch;        /* the exit epoch of the first of them in index order; 0 when n_ejected == 0 */
+    uint64_t last_exit_epoch;         /* ... of the last; 0 when n_ejected == 0 */
+    uint64_t queue_len;               /* the activation queue */
+    uint64_t n_activated;             /* min(activation_churn_limit, queue_len) */
+    uint64_t activation_epoch;        /* current_epoch + 1 + max_seed_lookahead: what they were given */
+} pe_registry_stats;
+
+/* process_registry_updates over the resident arrays, in place (the rule set is restated in
+ * tests/registry_updates_model.py: the reference holds the fields, pe:36-45, and names get_validator_churn_limit,
+ * pe:1261/1270, not the function's text).  For every validator, comparisons unsigned 64-bit, FAR = 2^64 - 1:
+ *   mark    activation_eligibility_epoch == FAR and effective_balance == max_effective_balance:
+ *           activation_eligibility_epoch = current_epoch + 1
+ *   eject   active at current_epoch, effective_balance <= ejection_balance and exit_epoch == FAR: initiate_validator_exit.
+ *           With E0 = max(largest exit epoch set, current_epoch + 1 + max_seed_lookahead), c0 = validators whose exit
+ *           epoch is E0 and (base, fill) = (E0 + 1, 0) if c0 >= churn_limit else (E0, c0), the k-th such validator in
+ *           index order gets exit_epoch = base + (fill + k) / churn_limit -- the sequential loop's closed form -- and
+ *           withdrawable_epoch = exit_epoch + min_validator_withdrawability_delay
+ *   queue   activation_eligibility_epoch <= finalized_epoch and activation_epoch == FAR, as read before the marks of this
+ *           call (a validator marked now has current_epoch + 1 > finalized_epoch): the first activation_churn_limit by
+ *           (activation_eligibility_epoch, index) get activation_epoch = current_epoch + 1 + max_seed_lookahead
+ * Reads the working-state view's effective balances as they are (the view is not materialised), the resident epochs
+ * (pe_registry_set_epochs), withdrawable epochs (pe_state_set_balances) and eligibility epochs (pe_registry_set_static).
+ * PE_VAL_ACTIVE / PE_VAL_ACTIVE_PREV are not touched: pe_state_refresh_activity stays the caller's step.  If an
+ * activation or exit epoch was written the resident active list is dropped, as pe_registry_set_epochs drops it; else it
+ * is kept.  pe_registry_get_epochs, pe_state_get_balances and pe_registry_get_static read the new values back and
+ * pe_state_roots hashes them with no further call.
+ * Read-only passes (k_registry_census, k_registry_select, k_registry_ties), a host step, one writing pass
+ * (k_registry_apply).  Synchronous (completes open pipelines first); one GPU.  out may be NULL.
+ * A failing call changes nothing:
+ *   PE_ERR_STATE        the epochs, the balances or the static part are not resident, or pe_dist_init* active
+ *   PE_ERR_INVALID_ARG  churn_limit_quotient == 0; current_epoch + 1 + max_seed_lookahead wraps or reaches FAR; the last
+ *                       exit epoch + min_validator_withdrawability_delay wraps or reaches FAR (decided on the host in 128
+ *                       bits before anything is written) */
+int pe_registry_updates(pe_engine* h, uint64_t current_epoch, uint64_t finalized_epoch, const pe_registry_params* params,
+                        pe_registry_stats* out);
+
+typedef struct pe_slashings_stats {
+    uint64_t total_active_balance;             /* get_total_active_balance: the quantity and rule of pe_ffg_balances out[0] */
+    uint64_t adjusted_total_slashing_balance;  /* min(sum_slashings * multiplier, total_active_balance) */
+    uint64_t n_penalised;                      /* slashed validators whose withdrawable epoch is the target */
+    uint64_t penalties;                        /* Gwei actually debited (after decrease_balance's cut at 0) */
+    uint64_t n_saturated;                      /* validators whose penalty exceeded the balance */
+} pe_slashings_stats;
+
+/* process_slashings over the resident balances, in place: every validator with PE_VAL_SLASHED in the working-state view
+ * and withdrawable_epoch == current_epoch + epochs_per_slashings_vector / 2 loses
+ * effective_balance / INCREMENT * adjusted / total * INCREMENT, cut at its balance.  total = get_total_active_balance over
+ * the view's PE_VAL_ACTIVE (k_ffg_balances' sum); sum_slashings = sum(state.slashings), the caller's scalar -- the vector
+ * and its reset stay with the caller.  Writes the resident balances alone; the view is read as it is.
+ * Synchronous (completes open pipelines first); one GPU.  out may be NULL.  A failing call changes nothing:
+ *   PE_ERR_STATE        no resident balances (pe_state_set_balances), or pe_dist_init* active
+ *   PE_ERR_INVALID_ARG  sum_slashings * multiplier exceeds 64 bits; current_epoch + epochs_per_slashings_vector / 2 wraps;
+ *                       (the largest effective balance of a penalised validator / INCREMENT) * adjusted exceeds 64 bits */
+int pe_process_slashings(pe_engine* h, uint64_t current_epoch, uint64_t sum_slashings,
+                         uint64_t proportional_slashing_multiplier, uint64_t epochs_per_slashings_vector,
+                         pe_slashings_stats* out);
 
 /* ---- SSZ roots of the resident per-validator lists -------------------------- */
 /* hash_tree_root (named at pe:142, 423, 1016; the reference holds no text of it) by the SSZ specification's rules: chunks of

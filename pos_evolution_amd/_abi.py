@@ -110,6 +110,27 @@ class pe_rewards_stats(C.Structure):
                 ("in_leak", C.c_uint64), ("rewards", C.c_uint64), ("penalties", C.c_uint64), ("n_saturated", C.c_uint64)]
 
 
+class pe_registry_params(C.Structure):
+    """struct pe_registry_params (include/posevo.h): the constants of pe_registry_updates."""
+    _fields_ = [("max_effective_balance", C.c_uint64), ("ejection_balance", C.c_uint64), ("max_seed_lookahead", C.c_uint64),
+                ("min_validator_withdrawability_delay", C.c_uint64), ("min_per_epoch_churn_limit", C.c_uint64),
+                ("churn_limit_quotient", C.c_uint64), ("max_per_epoch_activation_churn_limit", C.c_uint64)]
+
+
+class pe_registry_stats(C.Structure):
+    """struct pe_registry_stats (include/posevo.h): what one pe_registry_updates read and did."""
+    _fields_ = [("n_active", C.c_uint64), ("churn_limit", C.c_uint64), ("activation_churn_limit", C.c_uint64),
+                ("n_marked_eligible", C.c_uint64), ("n_ejected", C.c_uint64), ("first_exit_epoch", C.c_uint64),
+                ("last_exit_epoch", C.c_uint64), ("queue_len", C.c_uint64), ("n_activated", C.c_uint64),
+                ("activation_epoch", C.c_uint64)]
+
+
+class pe_slashings_stats(C.Structure):
+    """struct pe_slashings_stats (include/posevo.h): what one pe_process_slashings read and did."""
+    _fields_ = [("total_active_balance", C.c_uint64), ("adjusted_total_slashing_balance", C.c_uint64),
+                ("n_penalised", C.c_uint64), ("penalties", C.c_uint64), ("n_saturated", C.c_uint64)]
+
+
 PE_REWARDS_INACTIVITY, PE_REWARDS_DELTAS = 1, 2
 PE_ROOT_BALANCES, PE_ROOT_INACTIVITY, PE_ROOT_PART_PREV, PE_ROOT_PART_CUR, PE_ROOT_VALIDATORS = 1, 2, 4, 8, 16
 
@@ -189,6 +210,9 @@ SIGNATURES = {
     "pe_rewards_params_default": (None, [_P(pe_rewards_params)]),
     "pe_rewards_and_penalties": (C.c_int, [_H, C.c_uint64, C.c_uint64, _P(pe_rewards_params), C.c_uint32,
                                            _P(pe_rewards_stats)]),
+    "pe_registry_params_default": (None, [_P(pe_registry_params)]),
+    "pe_registry_updates": (C.c_int, [_H, C.c_uint64, C.c_uint64, _P(pe_registry_params), _P(pe_registry_stats)]),
+    "pe_process_slashings": (C.c_int, [_H, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _P(pe_slashings_stats)]),
     "pe_registry_set_static": (C.c_int, [_H, C.c_uint64, _u8p, _u8p, _u64p]),
     "pe_registry_get_static": (C.c_int, [_H, C.c_uint64, _u8p, _u8p, _u64p, C.c_void_p]),
     "pe_state_roots": (C.c_int, [_H, C.c_uint32, C.c_uint32, _P(pe_state_root_set), _u8p]),

@@ -545,7 +545,7 @@ void pe_engine_destroy(pe_engine* h)
                       &h->d_tpos, &h->d_tidx, &h->d_direct, &h->d_weights, &h->d_totals, &h->d_head,
                       &h->d_broot_tab, &h->d_broots, &h->d_bslot_pos,
                       &h->d_partials, &h->d_lane_partials, &h->d_out96, &h->d_tmp_points, &h->d_tmp_be, &h->d_tmp_points30,
-                      &h->d_activation_epoch, &h->d_exit_epoch, &h->d_active, &h->d_active_wg,
+                      &h->d_activation_epoch, &h->d_exit_epoch, &h->d_active, &h->d_active_wg, &h->d_registry_wg,
                       &h->d_rbalance, &h->d_inactivity, &h->d_withdrawable,
                       &h->d_pubkey_leaf, &h->d_withdrawal_credentials, &h->d_activation_eligibility, &h->d_ssz_zero,
                       &h->d_ssz_validator_roots, &h->d_ssz_level[0], &h->d_ssz_level[1], &h->d_ssz_chunks})

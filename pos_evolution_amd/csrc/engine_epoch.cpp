@@ -14,12 +14,20 @@
 //   pe_rewards_and_penalties        process_inactivity_updates and process_rewards_and_penalties (Altair; restated in
 //                                   tests/rewards_model.py) over those arrays: k_reward_sums, a host step, k_reward_apply
 //                                   (reward_kernels.hip; the rule per validator is reward_row.h)
+//   pe_registry_params_default      the constants of the function below
+//   pe_registry_updates             process_registry_updates (restated in tests/registry_updates_model.py) over the resident
+//                                   epochs: k_registry_census, a host step, the selection of the activation queue's head
+//                                   (k_registry_select, k_registry_ties), k_registry_apply (registry_kernels.hip; the rule
+//                                   per validator is registry_row.h)
+//   pe_process_slashings            process_slashings over the resident balances: k_ffg_balances' total, k_slashings_census,
+//                                   a host step, k_slashings_apply
 //   pe_effective_balance_updates    process_effective_balance_updates (pe:122-133): k_effective_balance_update (fc_kernels.hip),
 //                                   over the caller's balances or the resident ones (PE_BALANCES_RESIDENT)
 // All read and write the working-state view (d_sbalance / d_sflags / d_incr) and leave the justified-checkpoint data get_head
 // weighs (d_balance / d_flags) alone.  All are synchronous, single-GPU calls; inputs travel through the arena's pinned
 // staging block, results through its pinned output block.
 #include "engine_internal.h"
+#include "registry_row.h"
 #include "reward_row.h"
 
 using namespace posevo;
@@ -446,6 +454,239 @@ int pe_rewards_and_penalties(pe_engine* h, uint64_t current_epoch, uint64_t fina
             stats.penalties += p[(size_t)REWARD_APPLY_Q * b + 1];
             stats.n_saturated += p[(size_t)REWARD_APPLY_Q * b + 2];
         }
+    }
+    if (out_stats) *out_stats = stats;
+    return PE_OK;
+}
+
+void pe_registry_params_default(pe_registry_params* out)
+{
+    if (!out) return;
+    out->max_effective_balance = 32000000000ull;
+    out->ejection_balance = 16000000000ull;
+    out->max_seed_lookahead = 4;
+    out->min_validator_withdrawability_delay = 256;
+    out->min_per_epoch_churn_limit = 4;
+    out->churn_limit_quotient = 65536;
+    out->max_per_epoch_activation_churn_limit = 0;  // none: the limit of the forks before Deneb (Deneb: 8)
+}
+
+int pe_registry_updates(pe_engine* h, uint64_t current_epoch, uint64_t finalized_epoch, const pe_registry_params* params,
+                        pe_registry_stats* out_stats)
+{
+    if (!h || !params) return PE_ERR_INVALID_ARG;
+    PE_TRY(enter(h));
+    if (h->dist_ready())
+        return fail(h, PE_ERR_STATE, "pe_registry_updates: the handle exchanges with other ranks (pe_dist_init); "
+                                     "a sharded registry is not supported");
+    if (!h->epochs_set) return fail(h, PE_ERR_STATE, "pe_registry_updates: no registry epochs (pe_registry_set_epochs first)");
+    if (!h->balances_set)
+        return fail(h, PE_ERR_STATE, "pe_registry_updates: no resident withdrawable epochs (pe_state_set_balances first)");
+    if (!h->static_set)
+        return fail(h, PE_ERR_STATE, "pe_registry_updates: no resident eligibility epochs (pe_registry_set_static first)");
+    const uint64_t n = h->n_val;
+    if (n && h->d_sbalance.cap < 8 * n)
+        return fail(h, PE_ERR_STATE, "pe_registry_updates: the working-state view does not cover the registry");
+    typedef unsigned __int128 u128;
+    const u128 far = (u128)REGISTRY_FAR_FUTURE_EPOCH;
+    if (params->churn_limit_quotient == 0) return fail(h, PE_ERR_INVALID_ARG, "pe_registry_updates: churn_limit_quotient is 0");
+    const u128 activation_wide = (u128)current_epoch + 1 + params->max_seed_lookahead;
+    if (activation_wide >= far)
+        return fail(h, PE_ERR_INVALID_ARG, "pe_registry_updates: current_epoch + 1 + max_seed_lookahead reaches FAR_FUTURE_EPOCH");
+    const uint64_t activation_exit_epoch = (uint64_t)activation_wide;
+
+    const uint32_t n_wg = (uint32_t)((n + REGISTRY_WG - 1) / REGISTRY_WG);
+    HIP_TRY(h, h->d_registry_wg.ensure(std::max<size_t>(64, registry_scratch_bytes(n))));
+    OutBlock ob(h);
+    const size_t off_census = ob.alloc(sizeof(RegistryTotals));
+    const size_t off_ties = ob.alloc(sizeof(RegistryTotals));
+    const size_t off_hist = ob.alloc(8 * 256 * sizeof(uint32_t));  // one histogram per byte of an epoch
+    const size_t off_activated = ob.alloc(std::max<size_t>(4, 4ull * n_wg));
+    PE_TRY(ob.ensure());
+    uint64_t* const d_elig = h->d_activation_eligibility.as<uint64_t>();
+    uint64_t* const d_act = h->d_activation_epoch.as<uint64_t>();
+    uint64_t* const d_exit = h->d_exit_epoch.as<uint64_t>();
+
+    // ---- census (read-only): the counts, the exit queue's end, the ejected validators' offsets
+    RegistryTotals tot;
+    memset(&tot, 0, sizeof tot);
+    if (n) {
+        launch_registry_census(h->stream, d_elig, d_act, d_exit, h->d_sbalance.as<uint64_t>(), n, current_epoch, finalized_epoch,
+                               params->max_effective_balance, params->ejection_balance, h->d_registry_wg.p,
+                               ob.dev<RegistryTotals>(off_census));
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, ob.download(off_census, sizeof(RegistryTotals)));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        tot = *ob.host<RegistryTotals>(off_census);
+        if (tot.n_active > n || tot.n_marked > n || tot.n_queue > n || tot.n_counted > n || tot.n_at_max > n)
+            return fail(h, PE_ERR_NO_DEVICE, "k_registry_scan returned more validators than the registry holds");
+    }
+
+    // ---- host step: the limits, the exit queue's closed form, every refusal -- before anything is written
+    pe_registry_stats stats;
+    memset(&stats, 0, sizeof stats);
+    stats.n_active = tot.n_active;
+    stats.churn_limit = registry_churn_limit(tot.n_active, params->min_per_epoch_churn_limit, params->churn_limit_quotient);
+    if (stats.churn_limit == 0)
+        return fail(h, PE_ERR_INVALID_ARG, "pe_registry_updates: the churn limit is 0 (min_per_epoch_churn_limit)");
+    stats.activation_churn_limit = registry_activation_churn_limit(stats.churn_limit, params->max_per_epoch_activation_churn_limit);
+    stats.n_marked_eligible = tot.n_marked;
+    stats.n_ejected = tot.n_counted;
+    stats.queue_len = tot.n_queue;
+    stats.activation_epoch = activation_exit_epoch;
+    RegistryScalars S;
+    memset(&S, 0, sizeof S);
+    registry_exit_start(tot.max_exit, tot.n_at_max, tot.n_at_max != 0, activation_exit_epoch, stats.churn_limit, &S.exit_base,
+                        &S.exit_fill);
+    if (stats.n_ejected) {
+        const u128 last = (u128)S.exit_base + (S.exit_fill + (stats.n_ejected - 1)) / stats.churn_limit;
+        if (last + params->min_validator_withdrawability_delay >= far)
+            return fail(h, PE_ERR_INVALID_ARG, "pe_registry_updates: the last exit epoch + min_validator_withdrawability_delay "
+                                               "reaches FAR_FUTURE_EPOCH");
+        stats.first_exit_epoch = S.exit_base;
+        stats.last_exit_epoch = (uint64_t)last;
+    }
+    S.current_epoch = current_epoch;
+    S.finalized_epoch = finalized_epoch;
+    S.max_effective_balance = params->max_effective_balance;
+    S.ejection_balance = params->ejection_balance;
+    S.eligibility_mark = current_epoch + 1;
+    S.by_churn_limit = u64_div_make(stats.churn_limit);
+    S.withdrawability_delay = params->min_validator_withdrawability_delay;
+    S.activation_epoch = activation_exit_epoch;
+    const uint64_t want = std::min(stats.activation_churn_limit, stats.queue_len);
+    S.take_all = stats.queue_len <= stats.activation_churn_limit ? 1u : 0u;
+
+    // ---- the head of the queue by (eligibility epoch, index): the threshold epoch byte by byte from the top (read-only).
+    // Every queued epoch is <= finalized_epoch, so the bytes above its highest one are 0 in all of them.
+    if (!S.take_all) {
+        uint32_t top = 0;
+        while (top < 7 && (finalized_epoch >> (8 * (top + 1)))) ++top;
+        HIP_TRY(h, hipMemsetAsync(ob.dev<uint32_t>(off_hist), 0, 8 * 256 * sizeof(uint32_t), h->stream));
+        uint64_t prefix = 0, need = want;  // the need-th smallest epoch among the queued that agree with prefix
+        for (int byte = (int)top; byte >= 0; --byte) {
+            const size_t off = off_hist + (size_t)byte * 256 * sizeof(uint32_t);
+            launch_registry_select(h->stream, d_elig, d_act, n, finalized_epoch, (uint32_t)byte, prefix, ob.dev<uint32_t>(off));
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, ob.download(off, 256 * sizeof(uint32_t)));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            const uint32_t* hist = ob.host<uint32_t>(off);
+            uint64_t below = 0;
+            uint32_t b = 0;
+            while (b < 256 && below + hist[b] < need) below += hist[b++];
+            if (b == 256) return fail(h, PE_ERR_NO_DEVICE, "k_registry_select counted fewer queued validators than the census");
+            need -= below;
+            prefix = (prefix << 8) | b;
+        }
+        S.threshold = prefix;
+        S.threshold_take = need;
+        launch_registry_ties(h->stream, d_elig, d_act, n, finalized_epoch, S.threshold, h->d_registry_wg.p,
+                             ob.dev<RegistryTotals>(off_ties));
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, ob.download(off_ties, sizeof(RegistryTotals)));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (ob.host<RegistryTotals>(off_ties)->n_counted < need)
+            return fail(h, PE_ERR_NO_DEVICE, "k_registry_ties counted fewer validators at the threshold than the selection");
+    }
+
+    // ---- the writes
+    if (stats.n_marked_eligible || stats.n_ejected || want) {
+        uint32_t rows = 0;
+        const uint32_t* d_activated = launch_registry_apply(h->stream, S, h->d_sbalance.as<uint64_t>(), n, h->d_registry_wg.p, d_elig,
+                                                            d_act, d_exit, h->d_withdrawable.as<uint64_t>(), &rows);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(ob.host<uint32_t>(off_activated), d_activated, 4ull * rows, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        const uint32_t* p = ob.host<uint32_t>(off_activated);
+        for (uint32_t b = 0; b < rows; ++b) stats.n_activated += p[b];
+        if (stats.n_ejected || stats.n_activated) h->active_valid = false;  // compacted from the previous epochs
+    }
+    if (out_stats) *out_stats = stats;
+    return PE_OK;
+}
+
+int pe_process_slashings(pe_engine* h, uint64_t current_epoch, uint64_t sum_slashings, uint64_t proportional_slashing_multiplier,
+                         uint64_t epochs_per_slashings_vector, pe_slashings_stats* out_stats)
+{
+    if (!h) return PE_ERR_INVALID_ARG;
+    PE_TRY(enter(h));
+    if (h->dist_ready())
+        return fail(h, PE_ERR_STATE, "pe_process_slashings: the handle exchanges with other ranks (pe_dist_init); "
+                                     "a sharded registry is not supported");
+    if (!h->balances_set) return fail(h, PE_ERR_STATE, "pe_process_slashings: no resident balances (pe_state_set_balances first)");
+    const uint64_t n = h->n_val;
+    if (n && (h->d_sbalance.cap < 8 * n || h->d_sflags.cap < n))
+        return fail(h, PE_ERR_STATE, "pe_process_slashings: the working-state view does not cover the registry");
+    const uint64_t inc = h->cfg.effective_balance_increment;
+    uint64_t scaled = 0, target_epoch = 0;
+    if (inc == 0) return fail(h, PE_ERR_INVALID_ARG, "pe_process_slashings: the increment must be positive");
+    if (__builtin_mul_overflow(sum_slashings, proportional_slashing_multiplier, &scaled))
+        return fail(h, PE_ERR_INVALID_ARG, "pe_process_slashings: sum_slashings * proportional_slashing_multiplier exceeds 64 bits");
+    if (__builtin_add_overflow(current_epoch, epochs_per_slashings_vector / 2, &target_epoch))
+        return fail(h, PE_ERR_INVALID_ARG, "pe_process_slashings: current_epoch + epochs_per_slashings_vector / 2 exceeds 64 bits");
+    OutBlock ob(h);
+    const size_t off_ffg = ob.alloc(8ull * 3 * 256);
+    const size_t off_census = ob.alloc(8ull * SLASHINGS_CENSUS_Q * SLASHINGS_CENSUS_MAX_WG);
+    const size_t off_apply = ob.alloc(8ull * SLASHINGS_APPLY_Q * SLASHINGS_APPLY_MAX_WG);
+    PE_TRY(ob.ensure());
+
+    // ---- read-only: get_total_active_balance (pe_ffg_balances' reduction), who is penalised and the largest of them
+    uint64_t total = 0, n_penalised = 0, max_eff = 0;
+    if (n) {
+        const uint32_t ffg_blocks = launch_ffg_balances(h->stream, h->d_sbalance.as<uint64_t>(), h->d_sflags.as<uint8_t>(),
+                                                        h->d_part_cur.as<uint8_t>(), h->d_part_prev.as<uint8_t>(), n,
+                                                        ob.dev<uint64_t>(off_ffg));
+        HIP_TRY(h, hipGetLastError());
+        const uint32_t blocks = launch_slashings_census(h->stream, h->d_sbalance.as<uint64_t>(), h->d_sflags.as<uint8_t>(),
+                                                        h->d_withdrawable.as<uint64_t>(), n, target_epoch,
+                                                        ob.dev<uint64_t>(off_census));
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, ob.download(off_ffg, 8ull * 3 * ffg_blocks));
+        HIP_TRY(h, ob.download(off_census, 8ull * SLASHINGS_CENSUS_Q * blocks));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        const uint64_t* f = ob.host<uint64_t>(off_ffg);
+        for (uint32_t b = 0; b < ffg_blocks; ++b) total += f[3 * b];
+        const uint64_t* p = ob.host<uint64_t>(off_census);
+        for (uint32_t b = 0; b < blocks; ++b) {
+            n_penalised += p[(size_t)SLASHINGS_CENSUS_Q * b];
+            max_eff = std::max(max_eff, p[(size_t)SLASHINGS_CENSUS_Q * b + 1]);
+        }
+    }
+    total = std::max(inc, total);  // get_total_balance's floor (Appendix A.1), as pe_ffg_balances
+
+    // ---- host step
+    pe_slashings_stats stats;
+    memset(&stats, 0, sizeof stats);
+    stats.total_active_balance = total;
+    stats.adjusted_total_slashing_balance = std::min(scaled, total);
+    stats.n_penalised = n_penalised;
+    if ((unsigned __int128)(max_eff / inc) * stats.adjusted_total_slashing_balance > (unsigned __int128)UINT64_MAX)
+        return fail(h, PE_ERR_INVALID_ARG, "pe_process_slashings: effective_balance / increment * the adjusted slashing balance "
+                                           "can exceed 64 bits");
+    SlashingScalars S;
+    memset(&S, 0, sizeof S);
+    S.target_epoch = target_epoch;
+    S.adjusted = stats.adjusted_total_slashing_balance;
+    S.increment = inc;
+    S.by_increment = u64_div_make(inc);
+    S.by_total = u64_div_make(total);
+
+    // ---- the one writing pass
+    if (n_penalised) {
+        const uint32_t blocks = launch_slashings_apply(h->stream, S, h->d_sbalance.as<uint64_t>(), h->d_sflags.as<uint8_t>(),
+                                                       h->d_withdrawable.as<uint64_t>(), n, h->d_rbalance.as<uint64_t>(),
+                                                       ob.dev<uint64_t>(off_apply));
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, ob.download(off_apply, 8ull * SLASHINGS_APPLY_Q * blocks));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        const uint64_t* p = ob.host<uint64_t>(off_apply);
+        uint64_t seen = 0;
+        for (uint32_t b = 0; b < blocks; ++b) {
+            seen += p[(size_t)SLASHINGS_APPLY_Q * b + 0];
+            stats.penalties += p[(size_t)SLASHINGS_APPLY_Q * b + 1];
+            stats.n_saturated += p[(size_t)SLASHINGS_APPLY_Q * b + 2];
+        }
+        stats.n_penalised = seen;
     }
     if (out_stats) *out_stats = stats;
     return PE_OK;

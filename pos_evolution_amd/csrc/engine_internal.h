@@ -239,6 +239,7 @@ struct pe_engine {
     // ---- resident balances (engine_epoch.cpp: pe_state_set_balances, pe_rewards_and_penalties) ----
     DevBuf d_rbalance, d_inactivity, d_withdrawable;  // state.balances | state.inactivity_scores | Validator.withdrawable_epoch
     bool balances_set = false;                        // (pe:112, pe:368-369, pe:45), u64[n_val] each; dropped where the epochs are
+    DevBuf d_registry_wg;  // pe_registry_updates: the per-workgroup counts and offsets of one call (registry_scratch_bytes)
     // ---- SSZ roots (engine_ssz.cpp) ----
     // the static part of Validator (pe:37-38, 41): H(pubkey) u8[n_val][32] | withdrawal_credentials u8[n_val][32] |
     // activation_eligibility_epoch u64[n_val]; dropped where the epochs are

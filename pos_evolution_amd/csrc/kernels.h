@@ -522,6 +522,55 @@ void launch_active_compact(hipStream_t s, const uint64_t* d_activation_epoch, co
 void launch_activity_flags(hipStream_t s, const uint64_t* d_activation_epoch, const uint64_t* d_exit_epoch,
                            uint64_t current_epoch, uint64_t previous_epoch, uint64_t n_val, uint8_t* sflags);
 
+// process_registry_updates over the resident registry (registry_kernels.hip; the predicates, the exit queue's closed form and
+// the scalar block are registry_row.h).  One lane per validator, REGISTRY_WG per workgroup; d_wg: scratch of
+// registry_scratch_bytes(n_val) bytes that the launches of one call share.  n_val >= 1 launches; 0 launches nothing.
+//   launch_registry_census  read-only: per-workgroup counts and the (largest exit epoch set, holders) pair, then one scan
+//                           workgroup: the ejected validators' exclusive offsets and *d_totals (n_counted = fresh ejections)
+//   launch_registry_select  read-only: d_hist[256] (zeroed by the caller) += the histogram of byte `byte` of the eligibility
+//                           epoch over the queued validators with eligibility >> 8 (byte + 1) == prefix (byte 7: no prefix)
+//   launch_registry_ties    read-only: the queued validators at `threshold` per workgroup, their exclusive offsets,
+//                           d_totals->n_counted = how many there are (the other fields 0)
+//   launch_registry_apply   the writes; -> the device array of validators activated per workgroup, *out_n_wg entries
+struct RegistryScalars;
+constexpr int REGISTRY_WG = 256;  // validators per workgroup, one lane each; the scans take ACTIVE_SCAN_TILE counts per pass
+struct RegistryWgCensus {
+    uint32_t n_active, n_marked, n_eject, n_queue;
+    unsigned long long max_exit;  // the largest exit epoch below FAR_FUTURE_EPOCH among the workgroup's validators ...
+    uint32_t n_at_max, pad;       // ... and how many hold it; 0: none has an exit epoch set
+};
+struct RegistryTotals {
+    unsigned long long n_active, n_marked, n_queue;
+    unsigned long long n_counted;  // the total of the scanned column
+    unsigned long long max_exit, n_at_max;
+};
+size_t registry_scratch_bytes(uint64_t n_val);
+void launch_registry_census(hipStream_t s, const uint64_t* d_eligibility, const uint64_t* d_activation_epoch,
+                            const uint64_t* d_exit_epoch, const uint64_t* d_eff_balance, uint64_t n_val, uint64_t current_epoch,
+                            uint64_t finalized_epoch, uint64_t max_effective_balance, uint64_t ejection_balance, void* d_wg,
+                            RegistryTotals* d_totals);
+void launch_registry_select(hipStream_t s, const uint64_t* d_eligibility, const uint64_t* d_activation_epoch, uint64_t n_val,
+                            uint64_t finalized_epoch, uint32_t byte, uint64_t prefix, uint32_t* d_hist);
+void launch_registry_ties(hipStream_t s, const uint64_t* d_eligibility, const uint64_t* d_activation_epoch, uint64_t n_val,
+                          uint64_t finalized_epoch, uint64_t threshold, void* d_wg, RegistryTotals* d_totals);
+const uint32_t* launch_registry_apply(hipStream_t s, const RegistryScalars& S, const uint64_t* d_eff_balance, uint64_t n_val,
+                                      void* d_wg, uint64_t* d_eligibility, uint64_t* d_activation_epoch, uint64_t* d_exit_epoch,
+                                      uint64_t* d_withdrawable, uint32_t* out_n_wg);
+
+// process_slashings over the resident balances (registry_kernels.hip; registry_row.h).  Both return the number of workgroups
+// launched = rows of `partials`.
+//   launch_slashings_census  partials[wg][SLASHINGS_CENSUS_Q]: validators the penalty falls on (sum), the largest effective
+//                            balance among them (maximum)
+//   launch_slashings_apply   balances in place; partials[wg][SLASHINGS_APPLY_Q]: validators penalised, Gwei debited,
+//                            subtractions cut at 0 (sums)
+struct SlashingScalars;
+constexpr int SLASHINGS_CENSUS_Q = 2, SLASHINGS_APPLY_Q = 3;
+constexpr uint32_t SLASHINGS_CENSUS_MAX_WG = 256, SLASHINGS_APPLY_MAX_WG = 2048;
+uint32_t launch_slashings_census(hipStream_t s, const uint64_t* eff_balance, const uint8_t* sflags, const uint64_t* withdrawable,
+                                 uint64_t n_val, uint64_t target_epoch, uint64_t* partials);
+uint32_t launch_slashings_apply(hipStream_t s, const SlashingScalars& S, const uint64_t* eff_balance, const uint8_t* sflags,
+                                const uint64_t* withdrawable, uint64_t n_val, uint64_t* balances, uint64_t* partials);
+
 // compute_committee / compute_shuffled_index (pe:495-534) for a whole list: members[i] = indices[shuffled(i)].
 // d_source: rounds * ceil(n/256) * 8 words scratch; d_pivots: rounds words; d_indices null = identity.
 int launch_shuffle(hipStream_t s, const uint32_t* d_seed_be, uint32_t n, uint32_t rounds, uint32_t* d_source,

@@ -886,6 +886,41 @@ class Engine:
                 "in_leak": int(st.in_leak), "rewards": int(st.rewards), "penalties": int(st.penalties),
                 "n_saturated": int(st.n_saturated)}
 
+    # -- registry updates and slashings over the resident registry ----------
+    def registry_params(self, **overrides):
+        """pe_registry_params_default with fields replaced by keyword (max_effective_balance, ejection_balance,
+        max_seed_lookahead, min_validator_withdrawability_delay, min_per_epoch_churn_limit, churn_limit_quotient,
+        max_per_epoch_activation_churn_limit)."""
+        p = _abi.pe_registry_params()
+        self._lib.pe_registry_params_default(C.byref(p))
+        for k, v in overrides.items():
+            assert hasattr(p, k), k
+            setattr(p, k, int(v))
+        return p
+
+    def registry_updates(self, current_epoch: int, finalized_epoch: int, params=None) -> dict:
+        """process_registry_updates over the resident epochs, in place (pe_registry_updates): eligibility marks, ejections
+        through the exit queue, the head of the activation queue.  params: ``registry_params(...)``, a dict of its
+        overrides, or None for the defaults.  -> pe_registry_stats as a dict.  The resident active list is dropped when an
+        activation or exit epoch was written."""
+        if params is None or isinstance(params, dict):
+            params = self.registry_params(**(params or {}))
+        st = _abi.pe_registry_stats()
+        self._check(self._lib.pe_registry_updates(self._h, int(current_epoch), int(finalized_epoch), C.byref(params),
+                                                  C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in _abi.pe_registry_stats._fields_}
+
+    def process_slashings(self, current_epoch: int, sum_slashings: int, proportional_slashing_multiplier: int = 3,
+                          epochs_per_slashings_vector: int = 8192) -> dict:
+        """process_slashings over the resident balances, in place (pe_process_slashings).  sum_slashings =
+        sum(state.slashings); the multiplier is PROPORTIONAL_SLASHING_MULTIPLIER of the fork in force (Bellatrix: 3).
+        -> pe_slashings_stats as a dict."""
+        st = _abi.pe_slashings_stats()
+        self._check(self._lib.pe_process_slashings(self._h, int(current_epoch), int(sum_slashings),
+                                                   int(proportional_slashing_multiplier), int(epochs_per_slashings_vector),
+                                                   C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in _abi.pe_slashings_stats._fields_}
+
     # -- SSZ roots of the resident lists ------------------------------------
     def registry_set_static(self, pubkeys48, withdrawal_credentials, activation_eligibility_epoch):
         """Validator.pubkey (n x 48 B compressed), withdrawal_credentials (n x 32 B) and activation_eligibility_epoch of

@@ -17,6 +17,8 @@ pos-evolution.md (``pe:N``):
     process_effective_balance_updates(state)                pe:122-133    (state bound with bind_state)
     process_inactivity_updates(state)                       Altair; fields pe:368-369 (state bound with bind_state)
     process_rewards_and_penalties(state)                    Altair; fields pe:112, pe:45 (state bound with bind_state)
+    process_registry_updates(state)                         fields pe:36-45; churn limit pe:1261 (state bound with bind_state)
+    process_slashings(state)                                fields pe:359/397 (state bound with bind_state)
     get_active_validator_indices(state, epoch)              named at pe:467 (state bound with bind_state)
     get_committee_count_per_slot(state, epoch)              pe:461-468
     compute_weak_subjectivity_period(state)                 pe:1257-1287
@@ -579,6 +581,58 @@ def process_rewards_and_penalties(state, **params) -> None:
     inactivity penalties, applied pair by pair.  Call it after ``process_inactivity_updates``, as process_epoch does.
     ``state`` must have been bound with ``bind_state``.  Keywords replace fields of pe_rewards_params."""
     state._last_rewards_stats = _rewards_call(state, _abi.PE_REWARDS_DELTAS, params, "process_rewards_and_penalties")
+
+
+# ----------------------------------------------------------------------------- registry updates and slashings
+def _u64_of(items, count: int) -> np.ndarray:
+    return np.fromiter((int(x) for x in items), dtype=np.uint64, count=count)
+
+
+def process_registry_updates(state, **params) -> None:
+    """process_registry_updates over ``state.validators``, on the GPU: eligibility marks, ejections through the exit queue
+    and the head of the activation queue (pe_registry_updates).  ``state`` must have been bound with ``bind_state``
+    (effective balances are the binding's).  The validators' epochs, pubkeys and credentials are handed to the engine, the
+    four epochs that can change are written back.  Keywords replace fields of pe_registry_params (ejection_balance,
+    churn_limit_quotient, max_per_epoch_activation_churn_limit, ...).
+    Every call moves the whole registry both ways: the epochs, balances, pubkeys and credentials go up (112 B per validator
+    and the pubkeys' hashing), the four epochs come back.  There is no host route.  The path without any transfer is
+    ``Engine.registry_updates`` over arrays that stay resident between epochs."""
+    b = _binding(state)
+    assert b is not None, "process_registry_updates: bind_state(engine, state, ...) first"
+    vals, n, e = state.validators, len(state.validators), b.engine
+    e.registry_set_epochs(_u64_of((v.activation_epoch for v in vals), n), _u64_of((v.exit_epoch for v in vals), n))
+    b.epochs_resident = True
+    scores = getattr(state, "inactivity_scores", None)
+    e.state_set_balances(_u64_of(state.balances, n), None if scores is None else _u64_of(scores, n),
+                         _u64_of((v.withdrawable_epoch for v in vals), n))
+    e.registry_set_static(np.frombuffer(b"".join(bytes(v.pubkey) for v in vals), dtype=np.uint8).reshape(n, 48),
+                          np.frombuffer(b"".join(bytes(v.withdrawal_credentials) for v in vals), dtype=np.uint8).reshape(n, 32),
+                          _u64_of((v.activation_eligibility_epoch for v in vals), n))
+    current_epoch = int(state.slot) // int(e.cfg.slots_per_epoch)
+    state._last_registry_stats = e.registry_updates(current_epoch, int(state.finalized_checkpoint.epoch), params)
+    act, ext, _ = e.registry_get_epochs()
+    wdr = e.state_get_balances()[2]
+    elig = e.registry_static()[2]
+    for v, a, x, w, g in zip(vals, act, ext, wdr, elig):
+        v.activation_epoch, v.exit_epoch, v.withdrawable_epoch, v.activation_eligibility_epoch = int(a), int(x), int(w), int(g)
+
+
+def process_slashings(state, *, proportional_slashing_multiplier: int = 3, epochs_per_slashings_vector: int = 8192) -> None:
+    """process_slashings over ``state.balances``, on the GPU (pe_process_slashings): the correlated penalty of every slashed
+    validator half a slashings vector before its withdrawable epoch.  ``state`` must have been bound with ``bind_state``
+    (activity and slashed flags and effective balances are the binding's); ``sum(state.slashings)`` is taken here, the
+    vector itself is left alone.  Every call uploads the balances and withdrawable epochs and downloads the balances; the
+    path without any transfer is ``Engine.process_slashings`` over resident balances."""
+    b = _binding(state)
+    assert b is not None, "process_slashings: bind_state(engine, state, ...) first"
+    n, e = len(state.validators), b.engine
+    scores = getattr(state, "inactivity_scores", None)
+    e.state_set_balances(_u64_of(state.balances, n), None if scores is None else _u64_of(scores, n),
+                         _u64_of((v.withdrawable_epoch for v in state.validators), n))
+    current_epoch = int(state.slot) // int(e.cfg.slots_per_epoch)
+    state._last_slashings_stats = e.process_slashings(current_epoch, sum(int(x) for x in state.slashings),
+                                                      proportional_slashing_multiplier, epochs_per_slashings_vector)
+    state.balances[:] = [int(x) for x in e.state_get_balances()[0]]
 
 
 # ----------------------------------------------------------------------------- the active set and what is counted from it
