@@ -974,7 +974,8 @@ int pe_process_attestation_batch(pe_engine* h, const pe_state_ctx* st, const pe_
     {
         // round = how many earlier attestations of this batch hit the same (table, committee); a flat counter per
         // table replaces a hash map (the common case is one attestation per committee: everything in round 0)
-        std::vector<std::vector<uint16_t>> cnt(h->tables.size());
+        // (32 bits: a call holds at most 2^32 - 1 rows, and nothing limits how many of them name one committee)
+        std::vector<std::vector<uint32_t>> cnt(h->tables.size());
         for (size_t k = 0; k < acc.size(); ++k) {
             uint32_t r;
             if (acc[k].table->is_partition) {

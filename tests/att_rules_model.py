@@ -11,9 +11,10 @@ tests/test_att_rules_model.py pins every case of the boundary matrix (tests/att_
 
 An attestation is a dict: slot, index, beacon_block_root, source = (epoch, root), target = (epoch, root), from_block,
 n_bits, sig_valid, popcount, overlap.  The store is `blocks`: root -> (parent_root, slot), and its current slot.  The state
-is a StateCtx.  Committees are a CommitteeCtx: committees per slot, the (uniform) committee size, and which epochs have a
-table loaded -- the one notion here that the spec does not have (a state always knows its committees;
-PE_ATT_NO_COMMITTEE_TABLE, include/posevo.h)."""
+is a StateCtx.  Committees are a CommitteeCtx: committees per slot, the committee size -- one int where every committee
+has it, else a function (epoch, flat committee id) -> size -- and which epochs have a table loaded: the one notion here
+that the spec does not have (a state always knows its committees; PE_ATT_NO_COMMITTEE_TABLE, include/posevo.h).
+Nothing here asks a table to be a partition: members_of (Run.batch) may name a validator in several committees."""
 import os
 import re
 from collections import namedtuple
@@ -83,9 +84,10 @@ def _committee_status(att, cc, k, state_side):
         return INDEX_RANGE
     if flat_committee(att, cc, k) >= cc.cps * k.spe:
         return INDEX_RANGE
-    if att["n_bits"] < cc.size:  # pe:730; for the fork choice bits[i] is read for every committee position (A.6)
+    size = cc.size(att["target"][0], flat_committee(att, cc, k)) if callable(cc.size) else cc.size
+    if att["n_bits"] < size:  # pe:730; for the fork choice bits[i] is read for every committee position (A.6)
         return BITS_LENGTH
-    if att["n_bits"] > cc.size:
+    if att["n_bits"] > size:
         if state_side:  # pe:730
             return BITS_LENGTH
         # A.6 reads the committee's length of them and ignores the rest; the engine does so for bits in host memory and
@@ -162,14 +164,17 @@ def state_status(att, blocks, sc, cc, k=MAINNET):
     return st, (mask if st == OK else 0), which
 
 
-def update_latest_messages(latest, attesters, att, equivocating=()):
-    """pe:1435-1441 on `latest`: validator -> (epoch, root)."""
+def update_latest_messages(latest, attesters, att, equivocating=(), slots=None):
+    """pe:1435-1441 on `latest`: validator -> (epoch, root).  `slots` (vote-expiry variant, pe:1585-1596): validator ->
+    data.slot of the attestation its latest message came from."""
     t_epoch = att["target"][0]
     for v in attesters:
         if v in equivocating:
             continue
         if v not in latest or t_epoch > latest[v][0]:
             latest[v] = (t_epoch, att["beacon_block_root"])
+            if slots is not None:
+                slots[v] = att["slot"]
 
 
 def apply_flags(participation, attesters, mask, increments, base_reward_per_increment):
@@ -184,10 +189,13 @@ def apply_flags(participation, attesters, mask, increments, base_reward_per_incr
 
 
 class Run:
-    """What a sequence of batches leaves behind: latest messages and both participation arrays."""
+    """What a sequence of batches leaves behind: latest messages (with the slot each came from) and both participation
+    arrays.  `equivocating` is store.equivocating_indices: add to it between batches."""
 
     def __init__(self, n_validators, increments, base_reward_per_increment, k=MAINNET):
         self.latest = {}
+        self.slots = {}
+        self.equivocating = set()
         self.part = ([0] * n_validators, [0] * n_validators)  # [0] current, [1] previous
         self.increments = increments
         self.brpi = base_reward_per_increment
@@ -204,7 +212,7 @@ class Run:
             out["count"].append(a["popcount"] if st == OK else 0)
             if st == OK:
                 com = members_of(a["target"][0], flat_committee(a, cc, self.k))
-                update_latest_messages(self.latest, [v for v, b in zip(com, a["bits"]) if b], a)
+                update_latest_messages(self.latest, [v for v, b in zip(com, a["bits"]) if b], a, self.equivocating, self.slots)
         for a in atts:
             st, mask, which = state_status(a, blocks, sc, cc, self.k)
             num = 0

@@ -218,3 +218,168 @@ def test_first_accepted_row_of_a_committee_earns_the_flag():
     assert both and only2
     assert out["numerator"][i + 1] == sum(w.increments[v] * w.brpi * 14 for v in both) + \
         sum(w.increments[v] * w.brpi * 54 for v in only2)
+
+
+# ---------------------------------------------------------------- order inside a batch: tests/lmd_flag_cases.py
+# The model's extensions -- committees of differing sizes, a table that is no partition, equivocating indices, the slot of
+# the winning row -- pinned by running the spec's own on_attestation and process_attestation, row after row, over every
+# batch of tests/lmd_flag_cases.py.  The world's committees are hand-made, so get_beacon_committee answers from its
+# tables; everything that decides order (update_latest_messages, the flag loop) is the spec's text.
+def _lmd_flag_cases(w):
+    from tests import lmd_flag_cases as L
+
+    for k in (2, 3, 5):
+        for rot in range(k):
+            for inter in (False, True):
+                yield f"equal epochs k={k} rotation {rot} interleaved={inter}", L.equal_epochs(w, k, rot, inter)[0]
+    for variant in ("sequence", "later first", "earlier first"):
+        yield f"stored message, {variant}", L.stored_message(w, variant)
+    for later_first in (True, False):
+        for inter in (False, True):
+            yield f"two tables, later first={later_first} interleaved={inter}", L.two_tables(w, later_first, inter)
+    for between in (False, True):
+        yield f"equivocating, between={between}", L.equivocating(w, between)
+    for r, orders in L.FLAG_ORDERS.items():
+        for masks in orders:
+            for rot in range(r):
+                for inter in (False, True):
+                    yield f"flag rounds {masks} rotation {rot} interleaved={inter}", L.flag_rounds(w, masks, rot, inter)
+    for at in (False, True):
+        yield f"straddle at_threshold={at}", L.straddle(w, at)
+    rows, groups = L.voided_group(w)
+    yield "voided group", [("batch", groups)]
+
+
+@pytest.mark.parametrize("hot,n_val,overlapping", [(64, 4096, False), (129, 4100, False), (65, 4096, True), (1, 4096, True)])
+def test_order_cases_against_the_spec(monkeypatch, hot, n_val, overlapping):
+    from tests import lmd_flag_cases as L
+    from tests.scenario import genesis
+
+    w = L.world(hot, n_val, overlapping)
+    with C.preset():
+        assert spec.SLOTS_PER_EPOCH == L.SPE
+        anchor_state, block = genesis(8)   # the store's anchor; the state the rows are processed on is another object
+        genesis_state, _ = genesis(8)
+        rewards = []
+        monkeypatch.setattr(spec, "get_beacon_committee",
+                            lambda st, slot, index: list(w.members_of(slot // L.SPE, (slot % L.SPE) * L.CPS + index)))
+        monkeypatch.setattr(spec, "get_committee_count_per_slot", lambda st, ep: L.CPS)
+        monkeypatch.setattr(spec, "get_base_reward", lambda st, i: w.increments[i] * w.brpi)
+        monkeypatch.setattr(spec, "get_beacon_proposer_index", lambda st: 0)
+        monkeypatch.setattr(spec, "increase_balance", lambda st, i, delta: rewards.append(delta))
+        monkeypatch.setattr(spec, "VOTE_EXPIRY_SLOTS", 200)   # the variant that records the slot of a latest message
+        denominator = (spec.WEIGHT_DENOMINATOR - spec.PROPOSER_WEIGHT) * spec.WEIGHT_DENOMINATOR // spec.PROPOSER_WEIGHT
+        n_cases = 0
+        for name, steps in _lmd_flag_cases(w):
+            n_cases += 1
+            store = spec.get_forkchoice_store(anchor_state, block)
+            for bname, parent, slot in w.chain:
+                store.blocks[spec.Root(w.R[bname])] = spec.BeaconBlock(
+                    slot=slot, parent_root=spec.Root(w.R[parent]) if parent else spec.ZERO_ROOT)
+            clock = L.S0
+            state = _spec_state(w, genesis_state, w.sc[clock])
+            state.current_epoch_participation = [0] * n_val
+            state.previous_epoch_participation = [0] * n_val
+            monkeypatch.setattr(spec, "store_target_checkpoint_state",
+                                lambda store, target: store.checkpoint_states.__setitem__(target, state))
+            model = M.Run(n_val, w.increments, w.brpi)
+            for si, step in enumerate(steps):
+                if step[0] == "mark":
+                    store.equivocating_indices.update(step[1])
+                    model.equivocating.update(step[1])
+                    continue
+                if step[0] == "tick":
+                    clock = L.S1
+                    state = _spec_state(w, genesis_state, w.sc[clock])
+                    state.previous_epoch_participation = state.current_epoch_participation
+                    state.current_epoch_participation = [0] * n_val
+                    model.part = ([0] * n_val, model.part[0])
+                    continue
+                store.time = clock * spec.SECONDS_PER_SLOT
+                want = model.batch(step[1], w.blocks, clock, w.sc[clock], w.committee_ctx(clock, False), w.members_of)
+                for i, r in enumerate(step[1]):
+                    where = f"{name}, step {si}, row {i} ({r['tag']})"
+                    att = _attestation(r)
+                    if r["overlap"]:   # an aggregate whose members share a bit never verifies (A.8)
+                        att.signature_valid = False
+                    try:
+                        spec.on_attestation(store, att)
+                        accepted = True
+                    except AssertionError:
+                        accepted = False
+                    assert accepted == (want["status"][i] == M.OK), where
+                for i, r in enumerate(step[1]):
+                    where = f"{name}, step {si}, row {i} ({r['tag']})"
+                    att = _attestation(r)
+                    if r["overlap"]:
+                        att.signature_valid = False
+                    before = (list(state.current_epoch_participation), list(state.previous_epoch_participation))
+                    del rewards[:]
+                    try:
+                        spec.process_attestation(state, att)
+                        accepted = True
+                    except AssertionError:
+                        accepted = False
+                    assert accepted == (want["pstatus"][i] == M.OK), where
+                    after = (state.current_epoch_participation, state.previous_epoch_participation)
+                    paid = sum(w.increments[v] * w.brpi * weight
+                               for a, b in zip(before, after) for v in range(n_val) if a[v] != b[v]
+                               for f, weight in enumerate(M.FLAG_WEIGHTS) if (b[v] & ~a[v]) >> f & 1)
+                    assert want["numerator"][i] == paid, where
+                    assert rewards == ([want["numerator"][i] // denominator] if accepted else []), where
+                got = {int(v): (int(m.epoch), bytes(m.root)) for v, m in store.latest_messages.items()}
+                assert got == model.latest, f"{name}, step {si}: latest messages"
+                assert {int(v): int(s) for v, s in store.__dict__.get("latest_message_slots", {}).items()} == model.slots, \
+                    f"{name}, step {si}: slots of the latest messages"
+                assert list(state.current_epoch_participation) == model.part[0], f"{name}, step {si}"
+                assert list(state.previous_epoch_participation) == model.part[1], f"{name}, step {si}"
+            assert model.latest, name
+        assert n_cases > 60
+
+
+def test_order_cases_do_what_they_claim():
+    """The first of the competing rows gives the message and the winner moves with the rotation; a later row of a flag
+    round pays less than it would alone; equivocating validators and a voided group leave nothing."""
+    from tests import lmd_flag_cases as L
+
+    for overlapping in (False, True):
+        w = L.world(65, 4096, overlapping)
+        v = L.specials(w.n_val)[0]
+        for k in (2, 3, 5):
+            winners = set()
+            for rot in range(k):
+                for inter in (False, True):
+                    steps, first = L.equal_epochs(w, k, rot, inter)
+                    model = M.Run(w.n_val, w.increments, w.brpi)
+                    out = L.replay(model, w, steps, False)
+                    assert set(out[0]["status"]) == {M.OK} and set(out[0]["pstatus"]) == {M.OK}
+                    assert model.latest[v] == (2, first["beacon_block_root"]) and model.slots[v] == first["slot"]
+                    winners.add(model.latest[v][1])
+            assert len(winners) == k
+        for masks in ([1, 3, 7], [7, 3, 1], [1, 1, 3, 3, 7], [7, 3, 3, 1, 1]):
+            for rot in range(len(masks)):
+                steps = L.flag_rounds(w, masks, rot, False)
+                model = M.Run(w.n_val, w.increments, w.brpi)
+                out = L.replay(model, w, steps, False)[0]
+                assert sorted(out["mask"]) == sorted(masks) and set(out["pstatus"]) == {M.OK}
+                alone = [M.apply_flags([0] * w.n_val, [x for x, b in zip(w.members_of(2, r["slot"] % L.SPE), r["bits"]) if b],
+                                       m, w.increments, w.brpi) for r, m in zip(steps[0][1], out["mask"])]
+                assert out["numerator"][0] == alone[0] and all(a <= b for a, b in zip(out["numerator"], alone))
+                assert any(a < b for a, b in zip(out["numerator"][1:], alone[1:]))
+                assert model.part[0][v] == 7 if 7 in masks else 3
+        model = M.Run(w.n_val, w.increments, w.brpi)
+        L.replay(model, w, L.equivocating(w, False), False)
+        assert v not in model.latest and model.part[0][v]
+        model = M.Run(w.n_val, w.increments, w.brpi)
+        L.replay(model, w, L.equivocating(w, True), False)
+        assert model.latest[v][0] == 1
+    w = L.world(64)
+    rows, groups = L.voided_group(w)
+    model = M.Run(w.n_val, w.increments, w.brpi)
+    out = L.replay(model, w, [("batch", groups)], True)[0]
+    assert out["status"] == [M.OK, M.BAD_SIGNATURE, M.OK, M.OK] and out["pstatus"] == out["status"]
+    for at in (False, True):
+        model = M.Run(w.n_val, w.increments, w.brpi)
+        L.replay(model, w, L.straddle(w, at), False)
+        one = w.committees[1][L.ONE][0]
+        assert model.latest[one] == (1, w.R["P35"]) and model.latest[w.committees[1][L.P127][0]] == (1, w.R["P35"])

@@ -224,7 +224,8 @@ def test_results_are_deterministic_run_to_run(engine_factory):
         atts, arena, _ = synth.epoch_attestations(comm, tree, E, spe, seed=33, density=0.8, parts=3,
                                                   source=(0, tree.roots[0].tobytes()), vote_recent=40)
         agg = e.aggregate(packed=(atts, arena), want_aggregate_pubkeys=True)
-        # the un-aggregated rows too: overlapping committees in one batch exercise the atomicMax tie-break path
+        # the un-aggregated rows too: several rows per committee in one batch.  With 3 x 60000 bits for 60000 validators on
+        # a partition table they take the validator-major LMD route (k_lmd_validator_major), not the atomicMax one
         st_raw, _, _ = e.on_attestation_batch(packed=(atts, arena))
         st_agg, pk, cnt = e.on_attestation_batch(packed=(agg["atts"], agg["out_arena"]), want_aggregate_pubkeys=True)
         ctx = pe_state_ctx()
