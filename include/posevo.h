@@ -208,7 +208,9 @@ int pe_on_attester_slashing(pe_engine* h,
  * (slot, index) of that epoch (Appendix A.6 / compute_committee pe:495-504), as CSR:
  * committee id = (slot % SLOTS_PER_EPOCH) * committees_per_slot + index,
  * members[offsets[id] .. offsets[id+1]).  n_committees must be a multiple of
- * SLOTS_PER_EPOCH.  The engine keeps the cfg.max_committee_tables most recently used epochs. */
+ * SLOTS_PER_EPOCH.  The engine keeps the cfg.max_committee_tables most recently used epochs.
+ * A table that partitions the registry also gets the sum of every committee's pubkeys, enqueued behind the call on the
+ * stream all tables' sums share (not the shuffles') (aggregates in which a majority attests are then summed as that sum minus the absentees; POSEVO_COMMITTEE_SUMS=0: never). */
 int pe_set_committees(pe_engine* h, uint64_t epoch, uint32_t n_committees,
                       const uint32_t* offsets, const uint32_t* members);
 
@@ -219,7 +221,8 @@ int pe_set_committees(pe_engine* h, uint64_t epoch, uint32_t n_committees,
  * accessor); the active set is the caller's list, or PE_ACTIVE_RESIDENT = the list pe_active_set left on the device
  * (below); active_indices NULL = validators 0 .. n_active - 1 (every validator active).  Registers
  * the table for `epoch` like pe_set_committees and KEEPS IT ON THE DEVICE; out_offsets (n_committees + 1) and
- * out_members (n_active) are optional copies of the result (NULL: nothing is read back). */
+ * out_members (n_active) are optional copies of the result (NULL: nothing is read back).
+ * The per-committee pubkey sums of the table (see pe_set_committees) are enqueued behind it; the call does not wait for them. */
 int pe_compute_committees(pe_engine* h, uint64_t epoch, const uint8_t seed[32], const uint32_t* active_indices,
                           uint32_t n_active, uint32_t n_committees, uint32_t shuffle_round_count,
                           uint32_t* out_offsets, uint32_t* out_members);
@@ -229,7 +232,11 @@ int pe_compute_committees(pe_engine* h, uint64_t epoch, const uint8_t seed[32], 
  * MIN_SEED_LOOKAHEAD, get_seed pe:481-486 -- so it is enqueued an epoch before the calls that read it), the table is
  * registered at once, and the first call that reads it makes the engine's stream wait for the shuffle.  A caller that streams with lag depth L keeps
  * max_committee_tables >= L + 3: the least recently used table is rewritten in place, and if work in flight may still
- * read it the call first completes everything in flight. */
+ * read it the call first completes everything in flight.
+ * The table's per-committee pubkey sums are NOT enqueued with the shuffle: the first pe_aggregate over rows in device memory that
+ * has the table as a candidate and finds the table complete and no shuffle in flight builds them (a caller that shuffles inside
+ * every step keeps the direct sums and pays nothing).  The call sizes their buffers; the first call per table shape may wait
+ * for an earlier build once while it grows them. */
 int pe_compute_committees_async(pe_engine* h, uint64_t epoch, const uint8_t seed[32], const uint32_t* active_indices,
                                 uint32_t n_active, uint32_t n_committees, uint32_t shuffle_round_count);
 

@@ -52,6 +52,10 @@ int pe_profile_queue_classes(pe_engine* h, int32_t out_class[4]);
  * since it was created.  Every such growth inside a stream of steps is milliseconds of allocation or a drained pipeline; after the
  * first step of a stream of like steps the count must stand still, whatever the lag depth. */
 int pe_profile_arena_growths(const pe_engine* h, uint64_t* out);
+/* Which route the aggregate pubkeys take (POSEVO_COMMITTEE_SUMS): how many of the handle's committee tables hold valid
+ * per-committee pubkey sums, and how many groups of the last COMPLETED pe_aggregate over rows in device memory were summed by
+ * complement (committee sum minus the absentees) instead of directly. */
+int pe_profile_committee_sums(const pe_engine* h, uint32_t* out_tables_with_sums, uint32_t* out_groups_by_complement);
 /* The shader clock each k_g1_accumulate launch ran at, in MHz, for the launches since pe_profile_reset made while profiling was
  * on (the last 4096 of them), in launch order: workgroup 0 of every launch counts shader cycles against the fixed 100 MHz counter.
  * out_n = how many there are; at most cap are written.  The clock is the power management's and a multiplier-bound kernel follows

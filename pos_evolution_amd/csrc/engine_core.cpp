@@ -511,7 +511,10 @@ void pe_engine_destroy(pe_engine* h)
     if (h->aux_owned) (void)hipStreamSynchronize(h->aux_owned);
     if (h->prep_stream) { (void)hipStreamSynchronize(h->prep_stream); (void)hipStreamDestroy(h->prep_stream); }
     if (h->prof_base) (void)hipEventDestroy(h->prof_base);
+    if (h->sums_stream) { (void)hipStreamSynchronize(h->sums_stream); (void)hipStreamDestroy(h->sums_stream); }
     h->d_shuffle_scratch.release();
+    h->d_sum_groups.release();
+    h->d_sum_lane.release();
     h->d_points30.release();
     slasher_release(h);
     if (h->comm && rccl().ok) (void)rccl().CommDestroy(h->comm);
@@ -555,6 +558,8 @@ void pe_engine_destroy(pe_engine* h)
         t.d_members.release(); t.d_offsets.release(); t.d_inv_comm.release(); t.d_inv_pos.release();
         t.d_stage.release(); t.h_stage.release();
         if (t.ev_ready) (void)hipEventDestroy(t.ev_ready);
+        t.d_sums.release();
+        if (t.ev_sums) (void)hipEventDestroy(t.ev_sums);
     }
     h->h_head.release();
     for (auto& p : h->prof)
@@ -729,6 +734,15 @@ int pe_profile_arena_growths(const pe_engine* h, uint64_t* out)
 {
     if (!h || !out) return PE_ERR_INVALID_ARG;
     *out = h->arena_growths;
+    return PE_OK;
+}
+int pe_profile_committee_sums(const pe_engine* h, uint32_t* out_tables_with_sums, uint32_t* out_groups_by_complement)
+{
+    if (!h || !out_tables_with_sums || !out_groups_by_complement) return PE_ERR_INVALID_ARG;
+    uint32_t n = 0;
+    for (const auto& t : h->tables) n += t.n_committees && t.sums_valid ? 1u : 0u;
+    *out_tables_with_sums = n;
+    *out_groups_by_complement = h->last_cmpl_groups;
     return PE_OK;
 }
 int pe_profile_queue_classes(pe_engine* h, int32_t out_class[4])

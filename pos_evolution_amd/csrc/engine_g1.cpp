@@ -36,7 +36,7 @@ int build_points30(pe_engine* h, uint64_t n)
 int launch_g1_planned(pe_engine* h, const uint32_t* d_points, const uint32_t* d_members, const uint32_t* d_bits,
                       const G1Group* d_groups, const G1Plan& plan, uint8_t* d_out96, uint32_t* dev_jac,
                       hipStream_t s, hipStream_t fin, DevBuf* partials, DevBuf* lane_partials, const AttPlan* plan_dev,
-                      const uint32_t* d_members1, uint64_t caller_rows)
+                      const uint32_t* d_members1, uint64_t caller_rows, const G1Complement* cm)
 {
     if (plan.n_groups == 0) return PE_OK;
     if (!s) s = h->stream;
@@ -90,7 +90,8 @@ int launch_g1_planned(pe_engine* h, const uint32_t* d_points, const uint32_t* d_
             }
         }
         launch_g1_accumulate(s, d_points30, d_members, d_bits, d_groups, plan.n_groups, plan.n_slots,
-                             lane_partials->as<uint32_t>(), partials->as<uint32_t>(), plan_dev, d_members1, exclusive, clock_rec);
+                             lane_partials->as<uint32_t>(), partials->as<uint32_t>(), plan_dev, d_members1, exclusive, clock_rec,
+                             cm ? cm->cmpl : nullptr);
     }
     hipStream_t ts = fin;  // (on the accumulation's own stream the tree measured 0.433 vs 0.338 ms per step, round 3)
     if (ts != s) {
@@ -112,12 +113,90 @@ int launch_g1_planned(pe_engine* h, const uint32_t* d_points, const uint32_t* d_
         HIP_TRY(h, hipEventRecord(h->ev_tree, ts));
         HIP_TRY(h, hipStreamWaitEvent(fin, h->ev_tree, 0));
     }
+    if (cm)  // the finish is the committee sums' only reader: nothing in front of it waits for their build
+        for (int t = 0; t < 2; ++t)
+            if (cm->ev[t]) HIP_TRY(h, hipStreamWaitEvent(ns, cm->ev[t], 0));
     {
         ProfScope ps(h, PE_KERNEL_G1_NORMALISE, ns);
-        launch_g1_finish(ns, partials->as<uint32_t>(), d_groups, plan.n_groups, 0, 0, d_out96, dev_jac, plan_dev);
+        launch_g1_finish(ns, partials->as<uint32_t>(), d_groups, plan.n_groups, 0, 0, d_out96, dev_jac, plan_dev,
+                         cm ? cm->cmpl : nullptr, cm ? cm->sums[0] : nullptr, cm ? cm->sums[1] : nullptr);
     }
     HIP_TRY(h, hipGetLastError());
     return PE_OK;
+}
+
+// The sum of every committee of table t, by the kernels of every other sum: the committees as ungated groups in uniform blocks
+// (k_g1_committee_groups), one accumulation, one tree -- which leaves partial c = committee c's XYZZ words in t->d_sums.  On a
+// stream of their own: neither a streaming step's chain nor the next epoch's shuffle ever stands behind it, and only
+// k_g1_finish waits for ev_sums.
+void committee_sums_drop(pe_engine* h)
+{
+    for (auto& t : h->tables) t.sums_valid = t.sums_wanted = false;
+    if (h->sums_stream) (void)hipStreamSynchronize(h->sums_stream);  // a build in flight reads d_points30 and the tables
+}
+int build_committee_sums(pe_engine* h, CommitteeTable* t, bool defer)
+{
+    t->sums_valid = false;
+    t->sums_wanted = false;
+    if (!h->tune.committee_sums || !t->is_partition || !h->have_points || !h->points30_valid || h->dist_ready()) return PE_OK;
+    if (t->n_committees == 0 || t->n_val_at_load != h->n_val || t->offsets.size() != (size_t)t->n_committees + 1) return PE_OK;
+    const uint32_t C = t->n_committees;
+    uint64_t total = t->offsets.back();
+    uint32_t max_size = 0;
+    for (uint32_t c = 0; c < C; ++c) max_size = std::max(max_size, t->offsets[c + 1] - t->offsets[c]);
+    if (total == 0) return PE_OK;
+    // every committee inside ONE block of at most 256 lanes: the tree then leaves exactly one partial per committee
+    const uint32_t k = (uint32_t)std::max<uint64_t>({(uint64_t)G1_MIN_K, (total + G1_TARGET_LANES - 1) / G1_TARGET_LANES,
+                                                     ((uint64_t)max_size + G1_WG - 1) / G1_WG});
+    const uint32_t tasks = (max_size + k - 1) / k;
+    uint32_t l2 = 0;
+    while ((1u << l2) < tasks) ++l2;
+    const uint64_t slots = (uint64_t)C << l2;
+    if (slots > 4ull * G1_TARGET_LANES) return PE_OK;  // a table of very uneven committees: no sums, the direct route
+    if (!h->sums_stream) {
+        // least priority: the build is needed one finish later at the earliest, the shuffle beside it by the next step's row chain
+        // (at equal priority k_shuffle_indices_lds ran 310 us beside a build where it takes 150, profiles/NOTES_r12.md 3)
+        int least = 0, greatest = 0;
+        HIP_TRY(h, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(h, hipStreamCreateWithPriority(&h->sums_stream, hipStreamNonBlocking, least));
+    }
+    hipStream_t ps = h->sums_stream;
+    // the three buffers may still be read by an earlier build (scratch) or an earlier finish (the sums of the table this slot
+    // held: the caller has completed what was in flight against it); growing one waits for the sums' stream first
+    const size_t lane_bytes = (size_t)G1_LANE_PARTIAL_BYTES * G1_WG * ((slots + G1_WG - 1) / G1_WG);
+    if (sizeof(G1Group) * (size_t)C > h->d_sum_groups.cap || lane_bytes > h->d_sum_lane.cap ||
+        (size_t)PE_G1_PARTIAL_BYTES * C > t->d_sums.cap)
+        HIP_TRY(h, hipStreamSynchronize(ps));
+    HIP_TRY(h, h->d_sum_groups.ensure(sizeof(G1Group) * (size_t)C));
+    HIP_TRY(h, h->d_sum_lane.ensure(lane_bytes));
+    HIP_TRY(h, t->d_sums.ensure((size_t)PE_G1_PARTIAL_BYTES * C));
+    if (defer) {  // sized now, built by the first aggregate that finds no shuffle in flight (committee_sums_build_wanted)
+        t->sums_wanted = true;
+        return PE_OK;
+    }
+    HIP_TRY(h, hipMemsetAsync(t->d_sums.p, 0, (size_t)PE_G1_PARTIAL_BYTES * C, ps));  // an empty committee: infinity
+    G1Group* d_groups = h->d_sum_groups.as<G1Group>();
+    launch_g1_committee_groups(ps, t->d_offsets.as<uint32_t>(), C, k, l2, d_groups);
+    launch_g1_accumulate(ps, h->d_points30.as<uint32_t>(), t->d_members.as<uint32_t>(), nullptr, d_groups, C, (uint32_t)slots,
+                         h->d_sum_lane.as<uint32_t>(), t->d_sums.as<uint32_t>());
+    launch_g1_tree(ps, h->d_sum_lane.as<uint32_t>(), d_groups, C, (uint32_t)slots, t->d_sums.as<uint32_t>());
+    HIP_TRY(h, hipGetLastError());
+    if (!t->ev_sums) HIP_TRY(h, hipEventCreateWithFlags(&t->ev_sums, hipEventDisableTiming));
+    HIP_TRY(h, hipEventRecord(t->ev_sums, ps));
+    t->sums_valid = true;
+    return PE_OK;
+}
+
+// The deferred build of an asynchronously shuffled table, from an aggregate that has the table as a candidate: only once the
+// table is complete and the shuffles' stream is idle.  A build enqueued WITH the shuffle lands inside the steps of a caller
+// that shuffles in every step -- a full accumulation + tree beside each step's own: 0.475 -> 0.56-0.65 ms per step by
+// placement (profiles/NOTES_r12.md 3); such a caller's aggregates find a shuffle in flight every time and stay direct.
+int committee_sums_build_wanted(pe_engine* h, CommitteeTable* t)
+{
+    if (!t->sums_wanted || t->sums_valid || t->ready_pending) return PE_OK;
+    if (t->ev_ready && hipEventQuery(t->ev_ready) != hipSuccess) { (void)hipGetLastError(); return PE_OK; }
+    if (h->prep_stream && hipStreamQuery(h->prep_stream) != hipSuccess) { (void)hipGetLastError(); return PE_OK; }
+    return build_committee_sums(h, t, false);
 }
 
 // The collected signature legs (pe_aggregate_signed), launched: one decompression over all of them, then per leg the subgroup
@@ -350,6 +429,7 @@ int pe_set_pubkeys_compressed(pe_engine* h, uint64_t n, const uint8_t* pubkeys48
     HIP_TRY(h, h->d_points.ensure(4ull * G1_ROW_WORDS * n));
     h->have_points = false;
     h->points30_valid = false;
+    committee_sums_drop(h);
     uint64_t n_bad = 0;
     int rc = g1_decompress_common(h, pubkeys48, n, h->d_points.as<uint32_t>(), nullptr, status, &n_bad);
     if (rc) return rc;

@@ -147,6 +147,14 @@ struct CommitteeTable {
     DevBuf d_stage;                 // ... and their device copy
     hipEvent_t ev_ready = nullptr;  // pe_compute_committees_async: recorded behind the shuffle on the stream it ran on
     bool ready_pending = false;     // ... and not yet waited for by the engine's stream
+    // The sum of every committee's pubkeys (engine_g1.cpp: build_committee_sums): n_committees x 48 words XYZZ in the form
+    // k_g1_finish reads.  Built on the sums' stream behind the table; a group that goes by complement subtracts its absentees
+    // from it.  sums_valid: enqueued for THIS table over the registry's present points (ev_sums marks their end); dropped by
+    // anything that changes a point or the table (committee_sums_drop, the table's rewrite).
+    DevBuf d_sums;
+    bool sums_valid = false;
+    bool sums_wanted = false;       // pe_compute_committees_async: sized, to be built by a later aggregate (engine_g1.cpp)
+    hipEvent_t ev_sums = nullptr;
 };
 
 // Diagnostic only (POSEVO_HOST_TRACE=1): wall time of host phases, printed at pe_engine_destroy.
@@ -328,6 +336,13 @@ struct pe_engine {
     hipStream_t aux_owned = nullptr;    // the stream created for it (aux_stream may alias another one: Tune::state_on)
     hipStream_t prep_stream = nullptr;  // pe_compute_committees_async: next epochs' shuffles, beside everything else
     DevBuf d_shuffle_scratch;           // ... and their hash tables (the synchronous call uses d_tmp_be)
+    // committee sums (build_committee_sums): a stream of their own -- on the prep stream a build stood between two shuffles of a
+    // caller that shuffles inside every step, and the next shuffle (which the next step's row chain waits for) behind it:
+    // 0.47 -> 0.65 ms per step (profiles/NOTES_r12.md 3) -- and the descriptors | lane partials of one build (the builds
+    // follow each other on that stream)
+    hipStream_t sums_stream = nullptr;
+    DevBuf d_sum_groups, d_sum_lane;
+    uint32_t last_cmpl_groups = 0;      // groups of the last completed device-row aggregate that went by complement
     hipEvent_t ev_aux_fork = nullptr;
     hipEvent_t ev_aux_switch = nullptr;  // state_stream_begin: the state-transition work changes its stream (Tune::state_on = 2)
     static constexpr uint32_t STATE_ON_SIDE_MAX_ROWS = 1024;  // steps over at most this many rows: flag passes on the accumulation's stream
@@ -390,6 +405,8 @@ struct pe_engine {
         int sig_batch = env("POSEVO_SIG_BATCH", 8);
         // pe_engine_create asks the device which of its streams share a hardware queue and keeps four that do not (engine_core.cpp)
         int queue_probe = env("POSEVO_QUEUE_PROBE", 1);
+        // per-committee pubkey sums with every committee table, and aggregates by complement against them (0 = neither)
+        int committee_sums = env("POSEVO_COMMITTEE_SUMS", 1);
         // log2 of the nodes one workgroup of k_ssz_merkle reduces per pass; for measurement
         uint32_t ssz_tile_log2 = (uint32_t)std::min<int>(SSZ_TILE_LOG2, std::max<int>(SSZ_TILE_LOG2_MIN, env("POSEVO_SSZ_TILE_LOG2", SSZ_TILE_LOG2)));
     } tune;
@@ -803,11 +820,28 @@ void plan_g1(uint32_t n_groups, SizeFn size_of, G1Group* out, G1Plan* plan, uint
 
 void g1_stream_guard(pe_engine* h, hipStream_t s);
 int build_points30(pe_engine* h, uint64_t n);  // after the registry's points changed (n rows)
+// The complement route of one launch: the groups' verdicts (UnionArgs::cmpl) and the candidate tables' committee sums with
+// the events that mark their builds' ends (null where a table has none: its groups' verdicts are NONE32)
+struct G1Complement {
+    const uint32_t* cmpl = nullptr;
+    const uint32_t* sums[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
 int launch_g1_planned(pe_engine* h, const uint32_t* d_points, const uint32_t* d_members, const uint32_t* d_bits,
                       const G1Group* d_groups, const G1Plan& plan, uint8_t* d_out96, uint32_t* dev_jac,
                       hipStream_t s = nullptr, hipStream_t fin = nullptr, DevBuf* partials = nullptr,
                       DevBuf* lane_partials = nullptr, const AttPlan* plan_dev = nullptr,
-                      const uint32_t* d_members1 = nullptr, uint64_t caller_rows = 0);
+                      const uint32_t* d_members1 = nullptr, uint64_t caller_rows = 0, const G1Complement* cm = nullptr);
+// The per-committee sums of table t, enqueued on the sums' stream; the table must be complete (a synchronous table call, or the
+// deferred build).  defer: size the buffers and mark the table only (pe_compute_committees_async: the first such call per shape
+// may wait for the sums' stream once while it grows the scratch; the build itself then allocates nothing).  Builds
+// nothing (and leaves the table without sums) where the knob is off, the table does not partition the registry, no points are
+// loaded, the handle exchanges with other ranks, or the uniform plan would outgrow its scratch.
+int build_committee_sums(pe_engine* h, CommitteeTable* t, bool defer);
+int committee_sums_build_wanted(pe_engine* h, CommitteeTable* t);  // the deferred build, if the moment allows it
+// a point or the registry's size changed (synchronous calls): no table's sums hold any more, and a build still in flight has
+// finished reading the points before the caller rewrites them
+void committee_sums_drop(pe_engine* h);
 
 // ------------------------------------------------------------------ attestation resolution
 struct Resolved {

@@ -31,6 +31,7 @@ struct RrLayout {  // typed views into PipeArena::d_rr
     G1Group* g1;
     AttRow *rows_fc, *rows_st;
     int32_t *status_fc, *status_st;
+    uint32_t* cmpl;  // per group: the complement verdict (UnionArgs::cmpl)
     uint32_t *crow_start[2], *crow_cursor[2], *crow_cnt[2], *crow_list[2];
     size_t bytes;
 };
@@ -59,6 +60,7 @@ RrLayout rr_layout(uint8_t* base, uint32_t cap_n, uint32_t cap_c)
     L.rows_st = reinterpret_cast<AttRow*>(take(sizeof(AttRow) * (size_t)cap_n));
     L.status_fc = reinterpret_cast<int32_t*>(take(4ull * cap_n));
     L.status_st = reinterpret_cast<int32_t*>(take(4ull * cap_n));
+    L.cmpl = reinterpret_cast<uint32_t*>(take(4ull * cap_n));
     for (int t = 0; t < 2; ++t) {
         L.crow_start[t] = reinterpret_cast<uint32_t*>(take(4ull * (cap_c + 1)));
         L.crow_cursor[t] = reinterpret_cast<uint32_t*>(take(4ull * (cap_c + 1)));
@@ -246,7 +248,23 @@ int aggregate_resident(pe_engine* h, const pe_attestation* d_rows, uint32_t n, c
     const size_t off_obits = ob.alloc(words_cap * 4);
     const size_t off_oinfo = ob.alloc(8ull * n);
     const size_t off_opk = out_aggpk96 ? ob.alloc(96ull * n) : 0;
+    // By complement: a group of a candidate table that holds valid committee sums may be summed as S_c minus its absentees;
+    // k_bits_union decides per group (UnionArgs::cmpl).  Not for the partials of a validator-range shard (partial committees),
+    // not for the exchanged aggregate, not on a handle that exchanges with other ranks.
+    G1Complement cm;
+    bool by_cmpl = false;
+    if (out_aggpk96 && !dev_partials && set == 0 && h->tune.committee_sums && !h->dist_ready())
+        for (int t = 0; t < 2; ++t) {
+            if (tabs[t]) PE_TRY(committee_sums_build_wanted(h, tabs[t]));  // an asynchronously shuffled table's deferred build
+            if (tabs[t] && tabs[t]->sums_valid && tabs[t]->d_sums.p && tabs[t]->ev_sums) {
+                cm.sums[t] = tabs[t]->d_sums.as<uint32_t>();
+                cm.ev[t] = tabs[t]->ev_sums;
+                by_cmpl = true;
+            }
+        }
+    const size_t off_ocm = by_cmpl ? ob.alloc(4ull * n) : 0;
     PE_TRY(ob.ensure());
+    if (by_cmpl) cm.cmpl = L.cmpl;
     if (want_pk) {  // scratch of the G1 chain, sized by the bounds before anything is in flight
         PE_TRY(ensure_quiesced_arenas(h, &pe_engine::PipeArena::d_partials, std::max<size_t>(PE_G1_PARTIAL_BYTES, (size_t)PE_G1_PARTIAL_BYTES * n)));
         PE_TRY(ensure_quiesced_arenas(h, &pe_engine::PipeArena::d_lane_partials, (size_t)G1_LANE_PARTIAL_BYTES * slot_cap));
@@ -330,7 +348,9 @@ int aggregate_resident(pe_engine* h, const pe_attestation* d_rows, uint32_t n, c
                          L.member_row, group_of ? ob.host<uint32_t>(off_gof) : nullptr, ob.host<uint8_t>(off_rows), n_dev,
                          L.g1, {L.crow_cursor[0], L.crow_cursor[1]}, {L.crow_list[0], L.crow_list[1]}};
     const UnionArgs ua{L.ug, n, L.ubytes, st.dev<uint8_t>(off_arena), RS.bits.as<uint32_t>(), RS.info.as<uint32_t>(),
-                       ob.host<uint32_t>(off_obits), ob.host<uint32_t>(off_oinfo), L.plan};
+                       ob.host<uint32_t>(off_obits), ob.host<uint32_t>(off_oinfo), L.plan,
+                       by_cmpl ? L.cmpl : nullptr, by_cmpl ? ob.host<uint32_t>(off_ocm) : nullptr, L.grp,
+                       {cm.sums[0] ? 1u : 0u, cm.sums[1] ? 1u : 0u}};
     // ingest -> plan -> members -> union, each one beside the held-back fork-choice kernel of the previous step if there is one
     PE_TRY(launch_rows_paired(h, ia, pa, ma, ua));
     HIP_TRY(h, hipGetLastError());
@@ -348,7 +368,7 @@ int aggregate_resident(pe_engine* h, const pe_attestation* d_rows, uint32_t n, c
         bound.n_partials = n;
         const G1Group* d_groups = L.g1;
         const AttPlan* d_plan = L.plan;
-        auto launch_g1 = [h, arena, d_points, tables, d_union, d_groups, bound, out_pk, on_side, d_plan, dev_partials]() -> int {
+        auto launch_g1 = [h, arena, d_points, tables, d_union, d_groups, bound, out_pk, on_side, d_plan, dev_partials, cm, by_cmpl]() -> int {
             hipStream_t gs = on_side ? h->side_stream : h->stream;
             if (on_side) {  // behind everything enqueued on the engine's stream so far (see aggregate_impl)
                 HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
@@ -361,7 +381,8 @@ int aggregate_resident(pe_engine* h, const pe_attestation* d_rows, uint32_t n, c
             }
             PE_TRY(launch_g1_planned(h, d_points, tables.t[0].members, d_union, d_groups, bound, out_pk, dev_partials, gs,
                                      on_side ? h->fin_stream : gs, on_side ? &arena->d_partials : nullptr,
-                                     on_side ? &arena->d_lane_partials : nullptr, d_plan, tables.t[1].members));
+                                     on_side ? &arena->d_lane_partials : nullptr, d_plan, tables.t[1].members, 0,
+                                     by_cmpl ? &cm : nullptr));
             if (on_side) {
                 HIP_TRY(h, hipEventRecord(h->ev_join, h->g1_tail()));
                 h->side_busy = true;
@@ -389,8 +410,8 @@ int aggregate_resident(pe_engine* h, const pe_attestation* d_rows, uint32_t n, c
     ++h->rr.generation;
     const size_t base = ob.base;
     const int ai = h->cur;
-    auto complete = [h, ai, base, off_plan, off_rows, off_gof, off_obits, off_oinfo, off_opk, n, out_atts, out_n_groups,
-                     group_of, out_bits_arena, out_aggpk96, out_count]() -> int {
+    auto complete = [h, ai, base, off_plan, off_rows, off_gof, off_obits, off_oinfo, off_opk, off_ocm, by_cmpl, n, out_atts,
+                     out_n_groups, group_of, out_bits_arena, out_aggpk96, out_count]() -> int {
         const uint8_t* pin = h->arena[ai].h_pin.as<uint8_t>() + base;
         const AttPlan P = *reinterpret_cast<const AttPlan*>(pin + off_plan);
         if (P.error) return plan_error_to_status(h, P.error == 0xFFFFFFFFu ? 1u : P.error, "pe_aggregate (rows in device memory)");
@@ -413,6 +434,11 @@ int aggregate_resident(pe_engine* h, const pe_attestation* d_rows, uint32_t n, c
                 o.flags = (o.flags & ~(uint32_t)PE_ATT_FLAG_SIGNATURE_VALID) | PE_ATT_FLAG_OVERLAPPING_BITS;
         }
         if (out_aggpk96) memcpy(out_aggpk96, pin + off_opk, 96ull * ng);
+        h->last_cmpl_groups = 0;  // which route the sums took (pe_profile_committee_sums)
+        if (by_cmpl) {
+            const uint32_t* ocm = reinterpret_cast<const uint32_t*>(pin + off_ocm);
+            for (uint32_t g = 0; g < ng; ++g) h->last_cmpl_groups += ocm[g] != NONE32 ? 1u : 0u;
+        }
         return PE_OK;
     };
     HostLap lap2(&h->trace);

@@ -351,7 +351,7 @@ int pe_store_init(pe_engine* h, uint64_t genesis_time, uint64_t anchor_slot, con
     h->index_of.clear();
     // nothing of the previous store may resolve against the new one: committee tables (get_beacon_committee of the old
     // chain's states), the working-state view and its participation arrays, the resident aggregate
-    for (auto& t : h->tables) { t.n_committees = 0; t.offsets.clear(); t.is_partition = false; t.stamp = 0; }
+    for (auto& t : h->tables) { t.n_committees = 0; t.offsets.clear(); t.is_partition = false; t.stamp = 0; t.sums_valid = t.sums_wanted = false; }
     h->state_view_set = false;
     registry_epochs_drop(h);
     resident_balances_drop(h);
@@ -418,6 +418,7 @@ int pe_set_validators(pe_engine* h, uint64_t n, const uint8_t* pubkeys96, const 
     if (pubkeys96 && n) {
         HIP_TRY(h, h->d_points.ensure(4ull * G1_ROW_WORDS * n));
         h->points30_valid = false;
+        committee_sums_drop(h);  // sums over the old points (a build in flight is waited for); the next table build makes new ones
         // convert in chunks through a bounded device staging buffer
         const uint64_t chunk = std::min<uint64_t>(n, 1u << 20);
         HIP_TRY(h, h->d_tmp_be.ensure(96ull * chunk));
@@ -437,6 +438,7 @@ int pe_set_validators(pe_engine* h, uint64_t n, const uint8_t* pubkeys96, const 
     if (h->d_totals.p) HIP_TRY(h, hipMemsetAsync(h->d_totals.p, 0, h->d_totals.cap, h->stream));  // grid may shrink
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (n != old_n) {  // u64[old_n] arrays and a list of the old registry
+        committee_sums_drop(h);
         registry_epochs_drop(h);
         resident_balances_drop(h);
         registry_static_drop(h);
@@ -651,6 +653,8 @@ int pe_set_committees(pe_engine* h, uint64_t epoch, uint32_t n_committees, const
                                    [](const CommitteeTable& a, const CommitteeTable& b) { return a.stamp < b.stamp; });
         }
     }
+    t->sums_valid = t->sums_wanted = false;
+    if (t->ev_sums) HIP_TRY(h, hipStreamWaitEvent(h->stream, t->ev_sums, 0));  // an earlier build still reads the arrays rewritten below
     HIP_TRY(h, t->d_members.ensure(std::max<size_t>(64, 4ull * total)));
     HIP_TRY(h, t->d_offsets.ensure(4ull * (n_committees + 1)));
     HIP_TRY(h, hipMemcpyAsync(t->d_members.p, members, 4ull * total, hipMemcpyHostToDevice, h->stream));
@@ -669,7 +673,7 @@ int pe_set_committees(pe_engine* h, uint64_t epoch, uint32_t n_committees, const
     t->offsets.assign(offsets, offsets + n_committees + 1);
     t->is_partition = partition;
     t->stamp = ++h->table_stamp;
-    return PE_OK;
+    return build_committee_sums(h, t, false);  // on the sums' stream: the call does not wait for them
 }
 
 // The committee tables the handle holds: epochs first (out_epochs NULL: count only), then one table at a time.
@@ -759,6 +763,11 @@ static int compute_committees_impl(pe_engine* h, uint64_t epoch, const uint8_t s
     // let it finish; a completed or never recorded event returns at once
     if (t->ev_ready) HIP_TRY(h, hipEventSynchronize(t->ev_ready));
     t->ready_pending = false;
+    // ... and so for the sums of the table this slot held: invalid from here on, rebuilt behind the new table, under the
+    // ordering that protects the table itself (the flush above; the stream the new table is written on waits for the old
+    // build's event -- the host does not)
+    t->sums_valid = t->sums_wanted = false;
+    if (!asynchronous && t->ev_sums) HIP_TRY(h, hipStreamWaitEvent(h->stream, t->ev_sums, 0));
     const uint32_t nb = (n_active + 255) / 256;
     if (asynchronous) {
         // Nothing of this call touches the pipelines' arenas or the engine's stream: the table carries its own small
@@ -787,6 +796,8 @@ static int compute_committees_impl(pe_engine* h, uint64_t epoch, const uint8_t s
             HIP_TRY(h, t->d_inv_pos.ensure(4ull * h->n_val));
         }
         hipStream_t ps = h->prep_stream;
+        // the sums' build of the table this slot held reads the arrays the shuffle is about to rewrite, on its own stream
+        if (t->ev_sums) HIP_TRY(h, hipStreamWaitEvent(ps, t->ev_sums, 0));
         uint8_t* ds = t->d_stage.as<uint8_t>();
         HIP_TRY(h, hipMemcpyAsync(ds, hs, bytes, hipMemcpyHostToDevice, ps));
         uint32_t* d_source = h->d_shuffle_scratch.as<uint32_t>();
@@ -813,6 +824,9 @@ static int compute_committees_impl(pe_engine* h, uint64_t epoch, const uint8_t s
         t->is_partition = true;
         t->n_val_at_load = h->n_val;
         t->stamp = ++h->table_stamp;
+        // the sums are sized now and built by the first aggregate that has this table as a candidate and finds no shuffle
+        // in flight (committee_sums_build_wanted): nothing of them lands inside a step that shuffles
+        PE_TRY(build_committee_sums(h, t, true));
         lap.mark("comm.async_launch");
         return PE_OK;
     }
@@ -864,6 +878,7 @@ static int compute_committees_impl(pe_engine* h, uint64_t epoch, const uint8_t s
     t->is_partition = true;  // a permutation of distinct indices, sliced
     t->n_val_at_load = h->n_val;
     t->stamp = ++h->table_stamp;
+    PE_TRY(build_committee_sums(h, t, false));  // the table is complete: the sums go to their own stream, nobody waits here
     lap.mark("comm.4_outputs");
     return PE_OK;
 }

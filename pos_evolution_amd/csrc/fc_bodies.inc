@@ -462,6 +462,14 @@ __device__ __forceinline__ void bits_union_body(const uint32_t g /* group of thi
             host_info[2 * g] = cnt;
             host_info[2 * g + 1] = member_sum - cnt;
         }
+        if (a.cmpl) {  // by complement: more than half of a whole committee attests and the committee's sum is at hand
+            const AttGroup& G = a.grp[g];
+            uint32_t v = NONE32;
+            if (G.status_agg == 0 && G.table < 2 && a.sums_ok[G.table & 1] && G.size == d.n_bits && 2 * cnt > G.size)
+                v = G.pos | (G.table << 31);
+            a.cmpl[g] = v;
+            if (a.host_cmpl) a.host_cmpl[g] = v;
+        }
     }
 }
 

@@ -495,13 +495,15 @@ __device__ __forceinline__ bool g1s_add_quad(fq& out_a, fq& out_b, int q, const 
 // fused one did.
 // Slot -> (output slot of its block, block size): shared by the two kernels.
 __device__ __forceinline__ void g1_slot_block(const G1Group* __restrict__ groups, uint32_t n_groups, uint32_t n_slots,
-                                              uint32_t slot, uint32_t& my_out, uint32_t& my_size, G1Group& d, uint32_t& t)
+                                              uint32_t slot, uint32_t& my_out, uint32_t& my_size, G1Group& d, uint32_t& t,
+                                              uint32_t* g_out = nullptr)
 {
     my_out = NONE32;
     my_size = 0;
     t = 0;
     if (slot >= n_slots) return;
     const uint32_t g = find_group(groups, n_groups, slot);
+    if (g_out) *g_out = g;
     d = groups[g];
     t = slot - d.slot_base;
     const bool wide = d.log2_block > 8;                  // group spans whole workgroups
@@ -768,7 +770,8 @@ __device__ __forceinline__ void g1_accumulate_body(const uint32_t* __restrict__ 
                                                    uint32_t n_groups, uint32_t n_slots, uint32_t* __restrict__ lane_partials,
                                                    uint32_t* __restrict__ wg_partials, const AttPlan* __restrict__ plan_dev,
                                                    const uint32_t* __restrict__ members1,
-                                                   unsigned long long* __restrict__ clock_rec)
+                                                   unsigned long long* __restrict__ clock_rec,
+                                                   const uint32_t* __restrict__ cmpl)
 {
     const int tid = threadIdx.x;
     if (plan_dev) {
@@ -793,13 +796,18 @@ __device__ __forceinline__ void g1_accumulate_body(const uint32_t* __restrict__ 
     bool exc = false;
     uint32_t my_out, my_size, t;
     G1Group d{};  // padding lanes (slot >= n_slots) read zeros, not an unwritten struct
-    g1_slot_block(groups, n_groups, n_slots, slot, my_out, my_size, d, t);
+    uint32_t g = 0;
+    g1_slot_block(groups, n_groups, n_slots, slot, my_out, my_size, d, t, &g);
     uint32_t first = 0, count = 0;
+    // a group that goes by complement (the verdict of k_bits_union, one word per group; k_g1_finish reads the same word):
+    // the lane sums the members whose bit is NOT set, and the finish subtracts that from the committee's sum
+    uint32_t invert = 0;
     if (slot < n_slots && t < d.n_tasks) {
         const uint32_t gk = d.k & 0x7FFFFFFFu;
         if (d.k >> 31) members = members1;
         first = t * gk;
         count = min(gk, d.n_members - first);
+        if (cmpl) invert = cmpl[g] != NONE32 ? 1u : 0u;
     }
     // Two loads deep: while point j is added, the row of point j + 1 is in flight (its index arrived an iteration ago) and
     // so are the index and the bit word of point j + 2 -- the wave never waits for an address it needs at once.  (One
@@ -810,7 +818,7 @@ __device__ __forceinline__ void g1_accumulate_body(const uint32_t* __restrict__ 
         const uint32_t i = first + j;
         idx = members ? members[d.member_start + i] : d.member_start + i;
         if (!gated) return true;
-        return (bit_arena[d.bits_word + (i >> 5)] >> (i & 31)) & 1u;
+        return (((bit_arena[d.bits_word + (i >> 5)] >> (i & 31)) & 1u) ^ invert) != 0;
     };
     auto fetch = [&](uint32_t j, fq& ox, fq& oy) -> bool {  // complete, for the rare path
         uint32_t idx;
@@ -860,7 +868,8 @@ __device__ __forceinline__ void g1_accumulate_body(const uint32_t* __restrict__ 
         b[(2 * FQ_N + k) * G1_WG] = inf ? 0u : (uint32_t)acc.zz.l[k];
         b[(3 * FQ_N + k) * G1_WG] = inf ? 0u : (uint32_t)acc.zzz.l[k];
     }
-    if (my_size == 1) {  // a group of one task: done here, in the words k_g1_finish reads (rare: committees of <= k members)
+    if (my_size == 1) {  // a group of one task: done here, in the words k_g1_finish reads (rare: committees of <= k members;
+                         // of a group that goes by complement this is the absentees' sum, like every other lane's)
         uint32_t* dst = wg_partials + (size_t)G1X_WORDS * my_out;
 #pragma nounroll
         for (int c = 0; c < 4; ++c) {
@@ -885,10 +894,10 @@ k_g1_accumulate(const uint32_t* __restrict__ pts30, const uint32_t* __restrict__
                 const uint32_t* __restrict__ bit_arena, const G1Group* __restrict__ groups, uint32_t n_groups,
                 uint32_t n_slots, uint32_t* __restrict__ lane_partials, uint32_t* __restrict__ wg_partials,
                 const AttPlan* __restrict__ plan_dev, const uint32_t* __restrict__ members1,
-                unsigned long long* __restrict__ clock_rec)
+                unsigned long long* __restrict__ clock_rec, const uint32_t* __restrict__ cmpl)
 {
     s30::g1_accumulate_body(pts30, members, bit_arena, groups, n_groups, n_slots, lane_partials, wg_partials, plan_dev,
-                            members1, clock_rec);
+                            members1, clock_rec, cmpl);
 }
 
 void launch_g1_table_s30(hipStream_t s, const uint32_t* points_mont24, uint32_t* points_s30, uint64_t n)
@@ -899,7 +908,7 @@ void launch_g1_table_s30(hipStream_t s, const uint32_t* points_mont24, uint32_t*
 void launch_g1_accumulate(hipStream_t s, const uint32_t* points_s30, const uint32_t* members,
                               const uint32_t* bit_arena, const G1Group* groups, uint32_t n_groups, uint32_t n_slots,
                               uint32_t* lane_partials, uint32_t* wg_partials48, const AttPlan* plan_dev,
-                              const uint32_t* members1, int exclusive, unsigned long long* clock_rec)
+                              const uint32_t* members1, int exclusive, unsigned long long* clock_rec, const uint32_t* cmpl)
 {
     if (n_groups == 0 || n_slots == 0) return;
     const unsigned blocks = (n_slots + G1_WG - 1) / G1_WG;
@@ -918,7 +927,7 @@ void launch_g1_accumulate(hipStream_t s, const uint32_t* points_s30, const uint3
                                       (int)G1_ACC_EXCLUSIVE_LDS);
     }
     hipLaunchKernelGGL(k_g1_accumulate, dim3(blocks), dim3(G1_WG), lds_bytes, s, points_s30, members, bit_arena,
-                       groups, n_groups, n_slots, lane_partials, wg_partials48, plan_dev, members1, clock_rec);
+                       groups, n_groups, n_slots, lane_partials, wg_partials48, plan_dev, members1, clock_rec, cmpl);
 }
 
 // one_per_cu (the tree of a streaming step, on its own stream): ask for 84 KB of LDS instead of the 54 KB the kernel uses,
@@ -969,7 +978,8 @@ void launch_g1_tree(hipStream_t s, const uint32_t* lane_partials, const G1Group*
 __global__ void __launch_bounds__(64)
 k_g1_finish(const uint32_t* __restrict__ partials, const G1Group* __restrict__ groups, uint32_t n_groups,
             uint32_t n_parts_fixed, uint32_t part_stride, uint8_t* __restrict__ out_be96,
-            uint32_t* __restrict__ out_jac, const AttPlan* __restrict__ plan_dev)
+            uint32_t* __restrict__ out_jac, const AttPlan* __restrict__ plan_dev, const uint32_t* __restrict__ cmpl,
+            const uint32_t* __restrict__ sums0, const uint32_t* __restrict__ sums1)
 {
     // the launch's n_groups BOUNDS the device-resident count: the output block (96 B per group) and, across ranks, the
     // gathered partials' stride are sized by it (an aggregate that formed more groups than pe_dist_set_max_groups
@@ -994,11 +1004,25 @@ k_g1_finish(const uint32_t* __restrict__ partials, const G1Group* __restrict__ g
         n_parts = n_parts_fixed;
         stride = part_stride;
     }
+    // A group that went by complement (cmpl[g] = committee id | candidate table << 31, the word k_g1_accumulate read): the
+    // partials are the absentees' sum N, and the group's sum is S_c - N.  One more turn of the same loop: Y is negated (0 stays
+    // 0: infinity), then the committee's sum is added by the same complete add -- N at infinity, S_c = N (infinity out) and
+    // S_c = -N (a doubling) are its cases.
+    const uint32_t verdict = cmpl ? cmpl[g] : NONE32;
+    const uint32_t* csum = nullptr;
+    if (verdict != NONE32) csum = ((verdict >> 31) ? sums1 : sums0) + (size_t)G1X_WORDS * (verdict & 0x7FFFFFFFu);
     g1x acc;
     g1x_set_inf(acc);
-    for (uint32_t k = 0; k < n_parts; ++k) {
+    for (uint32_t k = 0; k < n_parts + (csum ? 1u : 0u); ++k) {
         g1x q;
-        global_load_x(q, partials + (size_t)G1X_WORDS * (first + (uint64_t)k * stride));
+        const uint32_t* src = partials + (size_t)G1X_WORDS * (first + (uint64_t)k * stride);
+        if (k == n_parts) {
+            fp ny;
+            fp_neg(ny, acc.y);
+            acc.y = ny;
+            src = csum;
+        }
+        global_load_x(q, src);
         g1x_add(acc, q);
     }
     if (out_jac) global_store_x(out_jac + (size_t)G1X_WORDS * g, acc);
@@ -1019,11 +1043,39 @@ k_g1_finish(const uint32_t* __restrict__ partials, const G1Group* __restrict__ g
 
 void launch_g1_finish(hipStream_t s, const uint32_t* partials48, const G1Group* groups, uint32_t n_groups,
                       uint32_t n_parts_fixed, uint32_t part_stride, uint8_t* out_be96, uint32_t* out_xyzz48,
-                      const AttPlan* plan_dev)
+                      const AttPlan* plan_dev, const uint32_t* cmpl, const uint32_t* sums0, const uint32_t* sums1)
 {
     if (n_groups == 0) return;
     hipLaunchKernelGGL(k_g1_finish, dim3((n_groups + 63) / 64), dim3(64), 0, s, partials48, groups, n_groups,
-                       n_parts_fixed, part_stride, out_be96, out_xyzz48, plan_dev);
+                       n_parts_fixed, part_stride, out_be96, out_xyzz48, plan_dev, cmpl, sums0, sums1);
+}
+
+// ---------------------------------------------------------------- committee sums
+// The descriptors of a table's committees as ungated groups with uniform blocks (committee c at slot c << log2_block, its sum at
+// partial c), for the per-table sums the complement route subtracts from: the accumulation and the tree then run unchanged.
+__global__ void __launch_bounds__(256)
+k_g1_committee_groups(const uint32_t* __restrict__ offsets, uint32_t n_committees, uint32_t k, uint32_t log2_block,
+                      G1Group* __restrict__ groups)
+{
+    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n_committees) return;
+    G1Group d;
+    d.member_start = offsets[c];
+    d.n_members = offsets[c + 1] - offsets[c];
+    d.bits_word = NONE32;
+    d.slot_base = c << log2_block;
+    d.n_tasks = (d.n_members + k - 1) / k;
+    d.k = k;
+    d.log2_block = log2_block;
+    d.out_base = c;
+    groups[c] = d;
+}
+void launch_g1_committee_groups(hipStream_t s, const uint32_t* offsets, uint32_t n_committees, uint32_t k, uint32_t log2_block,
+                                G1Group* groups)
+{
+    if (n_committees == 0) return;
+    hipLaunchKernelGGL(k_g1_committee_groups, dim3((n_committees + 255) / 256), dim3(256), 0, s, offsets, n_committees, k,
+                       log2_block, groups);
 }
 
 }  // namespace posevo

@@ -60,7 +60,14 @@ struct AttPlan;
 void launch_g1_accumulate(hipStream_t s, const uint32_t* points_s30, const uint32_t* members,
                           const uint32_t* bit_arena, const G1Group* groups, uint32_t n_groups, uint32_t n_slots,
                           uint32_t* lane_partials, uint32_t* wg_partials48, const AttPlan* plan_dev = nullptr,
-                          const uint32_t* members1 = nullptr, int exclusive = 0, unsigned long long* clock_rec = nullptr);
+                          const uint32_t* members1 = nullptr, int exclusive = 0, unsigned long long* clock_rec = nullptr,
+                          const uint32_t* cmpl = nullptr);
+// cmpl (nullable): one word per group, written by k_bits_union (UnionArgs::cmpl): NONE32 = the group is summed directly, else
+// committee id | candidate table << 31 = the group goes by complement: the accumulation sums the members whose bit is NOT set,
+// and k_g1_finish subtracts that from the committee's sum (sums0 / sums1: the candidate tables' per-committee XYZZ sums, 48
+// words each, built with the table -- launch_g1_committee_groups + the accumulation + the tree).
+void launch_g1_committee_groups(hipStream_t s, const uint32_t* offsets, uint32_t n_committees, uint32_t k, uint32_t log2_block,
+                                G1Group* groups);
 // exclusive: the launch asks for this much LDS it never touches (more than half a CU's): at most one of its workgroups per CU
 constexpr size_t G1_ACC_EXCLUSIVE_LDS = 82 * 1024;
 // The compacting LDS tree over each workgroup's 256 lane partials: one 48-u32 XYZZ partial (192 bytes) per
@@ -72,7 +79,8 @@ void launch_g1_tree(hipStream_t s, const uint32_t* lane_partials, const G1Group*
 // g when first == null), then either write the XYZZ sum (48 u32) or normalise to 96-byte affine.
 void launch_g1_finish(hipStream_t s, const uint32_t* partials48, const G1Group* groups, uint32_t n_groups,
                       uint32_t n_parts_fixed, uint32_t part_stride, uint8_t* out_be96, uint32_t* out_xyzz48,
-                      const AttPlan* plan_dev = nullptr);
+                      const AttPlan* plan_dev = nullptr, const uint32_t* cmpl = nullptr, const uint32_t* sums0 = nullptr,
+                      const uint32_t* sums1 = nullptr);
 
 // ---- fork choice ----
 struct TreeDev {               // block tree in DFS pre-order (device arrays of n entries)
@@ -298,6 +306,10 @@ struct UnionArgs {
     uint32_t* host_arena; uint32_t* host_info;  // nullable: the same two outputs written a second time straight into
                                // host-coherent pinned memory, so that no device-to-host copy command has to follow the kernel
     const AttPlan* plan_dev;   // nullable: the group count lives on the device, n_groups bounds it
+    // nullable: the complement verdict of every group, decided here once (the popcount exists here first) and read by
+    // k_g1_accumulate and k_g1_finish: cmpl[g] = grp[g].pos | grp[g].table << 31 when the group is a whole committee of a
+    // candidate table whose sums are valid (sums_ok) and 2 * popcount(union) > committee size; NONE32 otherwise
+    uint32_t* cmpl; uint32_t* host_cmpl; const AttGroup* grp; uint32_t sums_ok[2];
 };
 // Subtree sums (prefix scan over pre-order), viability, best child, the descent to the head.
 struct TreeArgs {

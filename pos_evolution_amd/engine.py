@@ -1387,6 +1387,13 @@ class Engine:
         self._check(self._lib.pe_profile_arena_growths(self._h, C.byref(n)))
         return int(n.value)
 
+    def profile_committee_sums(self):
+        """pe_profile_committee_sums: (committee tables that hold valid pubkey sums, groups of the last completed aggregate
+        over device rows that were summed by complement)."""
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.pe_profile_committee_sums(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def profile_accumulate_mhz(self):
         """pe_profile_accumulate_mhz: the shader clock (MHz) of each k_g1_accumulate launch since profile_reset(), in launch
         order (launches made while profiling was on; the last 4096)."""
