@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define PE_ABI_VERSION 14
+#define PE_ABI_VERSION 15
 
 typedef struct pe_engine pe_engine;
 
@@ -851,6 +851,31 @@ int pe_aggregate_signed(pe_engine* h, const pe_attestation* atts, uint32_t n,
 /* The subgroup check on its own: n points in the 192-byte uncompressed form (host memory); status[i] = PE_SIG_OK or
  * PE_SIG_NOT_IN_SUBGROUP (infinity passes). */
 int pe_g2_subgroup_check(pe_engine* h, const uint8_t* points192, uint64_t n, int32_t* status);
+
+/* ---- the pairing check (is_valid_indexed_attestation's last step, pe:736, 976, 1456) ------------------------------
+ * Batched optimal-ate pairing products on the device.  Points in the formats above: 96-byte uncompressed G1 (x | y),
+ * 192-byte uncompressed G2 in ZCash order (x.c1 | x.c0 | y.c1 | y.c0), infinity = bit 6 of byte 0.  All arrays in host
+ * memory.  Every point is checked against its curve equation (and for canonical coordinates) on the device.
+ * verdict[g]: 1  the product of e(P_j, Q_j) over j in [offsets[g], offsets[g+1]) is 1
+ *             0  it is not
+ *             2  a point of the group is not on its curve (PE_BLS_BAD_POINT)
+ * an empty group gives 1 (the empty product); infinity on either side contributes 1.
+ * Subgroup membership is the caller's: pe_g1_key_validate / pe_g2_subgroup_check.
+ * Synchronous (completes open pipelines first); one GPU: PE_ERR_STATE on a handle with pe_dist_init* active.
+ * offsets not monotone or past n_pairs: PE_ERR_INVALID_ARG.  Not computed here: hash_to_curve (the caller supplies the
+ * message point H(m) in G2) and random-linear-combination batching (one final exponentiation per group). */
+#define PE_BLS_VALID 1
+#define PE_BLS_INVALID 0
+#define PE_BLS_BAD_POINT 2
+int pe_pairing_check(pe_engine* h, const uint8_t* g1_points96, const uint8_t* g2_points192, uint64_t n_pairs,
+                     const uint32_t* offsets, uint32_t n_groups, int32_t* verdict);
+/* FastAggregateVerify per group: the pubkeys registry[index[j]], j in [offsets[g], offsets[g+1]), are summed on the device
+ * (the route of pe_g1_sum), and the pairs (sum, message_points192[g]), (-G1, signatures192[g]) are checked.
+ * verdict[g] as above; an empty group gives 0 (FastAggregateVerify refuses n = 0), an identity signature gives 0.
+ * The verdict may be passed on as PE_ATT_FLAG_SIGNATURE_VALID where the caller injects it today.  No pubkeys loaded:
+ * PE_ERR_STATE; an index outside the registry: PE_ERR_INVALID_ARG. */
+int pe_fast_aggregate_verify(pe_engine* h, const uint32_t* index, const uint32_t* offsets, uint32_t n_groups,
+                             const uint8_t* message_points192, const uint8_t* signatures192, int32_t* verdict);
 
 /* ---- multi-GPU exchange (validator-range shards) ----------- */
 /* Each rank owns a contiguous validator range and the whole (small) block table.

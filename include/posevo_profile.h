@@ -62,6 +62,13 @@ int pe_profile_committee_sums(const pe_engine* h, uint32_t* out_tables_with_sums
  * it one to one: ~2.05 GHz for the first milliseconds of heavy load after an idle moment, ~2.4 GHz after ~35 ms of it
  * (tools/clockramp.hip, profiles/r06_clockramp.txt) -- which is most of the distance between a 20-step and a 200-step run. */
 int pe_profile_accumulate_mhz(pe_engine* h, double* out_mhz, uint32_t cap, uint32_t* out_n);
+/* For the parity tests of pe_pairing_check (same arguments): the value each group's verdict compares with 1, i.e. the Miller
+ * loop's product raised to (p^12 - 1) / r * 3 -- the reduced pairing product cubed.  576 bytes per group: the 12 Fp
+ * coefficients as plain (not Montgomery) residues, 48 bytes big-endian each, in the order c_0.c0, c_0.c1, c_1.c0, ... c_5.c1,
+ * where c_k = c_k.c0 + c_k.c1 u is the Fp2 coefficient of w^k in Fp12 = Fp2[w] / (w^6 - (1 + u)); in the tower
+ * Fp6 = Fp2[v] / (v^3 - (1 + u)), Fp12 = Fp6[w] / (w^2 - v), c_(2i+j) is the coefficient of v^i w^j. */
+int pe_profile_pairing_gt(pe_engine* h, const uint8_t* g1_points96, const uint8_t* g2_points192, uint64_t n_pairs,
+                          const uint32_t* offsets, uint32_t n_groups, uint8_t* out576);
 
 #ifdef __cplusplus
 }

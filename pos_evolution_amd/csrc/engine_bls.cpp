@@ -1,0 +1,117 @@
+// engine_bls.cpp -- the pairing-product check and FastAggregateVerify on the device.
+//   pe_pairing_check          per group: prod e(P_j, Q_j) == 1
+//   pe_fast_aggregate_verify  per group: e(sum of the group's registry pubkeys, H(m)) e(-g1, signature) == 1; the sum goes the
+//                             route of pe_g1_sum, H(m) is the caller's (hash_to_curve is out of scope)
+//   pe_profile_pairing_gt     the value the verdict compares with 1, for the parity tests
+// Both verdict calls are synchronous and complete open pipelines first (enter); one GPU: PE_ERR_STATE under pe_dist_init*.
+#include "engine_internal.h"
+
+using namespace posevo;
+
+namespace {
+
+// -g1: the generator of G1 negated, 96-byte uncompressed form (x, p - y of the published generator)
+const uint8_t NEG_G1_BE96[96] = {
+    0x17, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x94, 0x26, 0x95, 0x63, 0x8c, 0x4f, 0xa9, 0xac, 0x0f,
+    0xc3, 0x68, 0x8c, 0x4f, 0x97, 0x74, 0xb9, 0x05, 0xa1, 0x4e, 0x3a, 0x3f, 0x17, 0x1b, 0xac, 0x58,
+    0x6c, 0x55, 0xe8, 0x3f, 0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a, 0xdb, 0x22, 0xc6, 0xbb,
+    0x11, 0x4d, 0x1d, 0x68, 0x55, 0xd5, 0x45, 0xa8, 0xaa, 0x7d, 0x76, 0xc8, 0xcf, 0x2e, 0x21, 0xf2,
+    0x67, 0x81, 0x6a, 0xef, 0x1d, 0xb5, 0x07, 0xc9, 0x66, 0x55, 0xb9, 0xd5, 0xca, 0xac, 0x42, 0x36,
+    0x4e, 0x6f, 0x38, 0xba, 0x0e, 0xcb, 0x75, 0x1b, 0xad, 0x54, 0xdc, 0xd6, 0xb9, 0x39, 0xc2, 0xca
+};
+
+size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
+
+int pairing_run(pe_engine* h, const char* who, const uint8_t* g1, const uint8_t* g2, uint64_t n_pairs, const uint32_t* offsets,
+                uint32_t n_groups, int32_t* verdict, uint8_t* out576)
+{
+    if (h->dist_ready())
+        return fail(h, PE_ERR_STATE, std::string(who) + ": the handle exchanges with other ranks (pe_dist_init); "
+                                                        "the sharded handles are not supported");
+    if (n_groups == 0) return PE_OK;
+    if (n_pairs >= 0xFFFFFFFFull) return fail(h, PE_ERR_CAPACITY, std::string(who) + ": too many pairs");
+    for (uint32_t g = 0; g < n_groups; ++g)
+        if (offsets[g + 1] < offsets[g]) return fail(h, PE_ERR_INVALID_ARG, std::string(who) + ": offsets not monotone");
+    if (offsets[n_groups] > n_pairs) return fail(h, PE_ERR_INVALID_ARG, std::string(who) + ": offsets exceed the number of pairs");
+    const size_t rows = std::max<uint64_t>(1, n_pairs);  // the kernels' idle lanes read row 0
+    const size_t o_g1 = 0, o_g2 = o_g1 + up256(96 * rows), o_off = o_g2 + up256(192 * rows),
+                 o_ws = o_off + up256(4 * ((size_t)n_groups + 1)), o_flag = o_ws + up256(4 * (size_t)BLS_PAIR_WORDS * rows),
+                 o_gt = o_flag + up256(4 * rows), o_bad = o_gt + up256(4 * (size_t)BLS_GT_WORDS * n_groups),
+                 o_verdict = o_bad + up256(4 * (size_t)n_groups), o_out = o_verdict + up256(4 * (size_t)n_groups),
+                 total = o_out + (out576 ? up256(576 * (size_t)n_groups) : 0);
+    HIP_TRY(h, h->d_bls.ensure(total));
+    uint8_t* d = h->d_bls.as<uint8_t>();
+    if (n_pairs == 0) HIP_TRY(h, hipMemsetAsync(d + o_flag, 0, 4, h->stream));
+    if (n_pairs) {
+        HIP_TRY(h, hipMemcpyAsync(d + o_g1, g1, 96 * n_pairs, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(d + o_g2, g2, 192 * n_pairs, hipMemcpyHostToDevice, h->stream));
+    }
+    HIP_TRY(h, hipMemcpyAsync(d + o_off, offsets, 4 * ((size_t)n_groups + 1), hipMemcpyHostToDevice, h->stream));
+    uint32_t* ws = reinterpret_cast<uint32_t*>(d + o_ws);
+    int32_t* flag = reinterpret_cast<int32_t*>(d + o_flag);
+    uint32_t* gt = reinterpret_cast<uint32_t*>(d + o_gt);
+    int32_t* bad = reinterpret_cast<int32_t*>(d + o_bad);
+    int32_t* dv = reinterpret_cast<int32_t*>(d + o_verdict);
+    launch_bls_prepare(h->stream, d + o_g1, d + o_g2, n_pairs, ws, flag);
+    launch_bls_miller(h->stream, ws, flag, reinterpret_cast<const uint32_t*>(d + o_off), n_groups, gt, bad);
+    launch_bls_final_exp(h->stream, gt, bad, n_groups, dv, out576 ? d + o_out : nullptr);
+    HIP_TRY(h, hipGetLastError());
+    if (verdict) HIP_TRY(h, hipMemcpyAsync(verdict, dv, 4 * (size_t)n_groups, hipMemcpyDeviceToHost, h->stream));
+    if (out576) HIP_TRY(h, hipMemcpyAsync(out576, d + o_out, 576 * (size_t)n_groups, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return PE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pe_pairing_check(pe_engine* h, const uint8_t* g1_points96, const uint8_t* g2_points192, uint64_t n_pairs,
+                     const uint32_t* offsets, uint32_t n_groups, int32_t* verdict)
+{
+    if (!h || !offsets || (n_groups && !verdict) || (n_pairs && (!g1_points96 || !g2_points192))) return PE_ERR_INVALID_ARG;
+    PE_TRY(enter(h));  // open pipelines complete
+    return pairing_run(h, "pe_pairing_check", g1_points96, g2_points192, n_pairs, offsets, n_groups, verdict, nullptr);
+}
+
+int pe_profile_pairing_gt(pe_engine* h, const uint8_t* g1_points96, const uint8_t* g2_points192, uint64_t n_pairs,
+                          const uint32_t* offsets, uint32_t n_groups, uint8_t* out576)
+{
+    if (!h || !offsets || (n_groups && !out576) || (n_pairs && (!g1_points96 || !g2_points192))) return PE_ERR_INVALID_ARG;
+    PE_TRY(enter(h));
+    return pairing_run(h, "pe_profile_pairing_gt", g1_points96, g2_points192, n_pairs, offsets, n_groups, nullptr, out576);
+}
+
+int pe_fast_aggregate_verify(pe_engine* h, const uint32_t* index, const uint32_t* offsets, uint32_t n_groups,
+                             const uint8_t* message_points192, const uint8_t* signatures192, int32_t* verdict)
+{
+    if (!h || !offsets || (n_groups && (!message_points192 || !signatures192 || !verdict))) return PE_ERR_INVALID_ARG;
+    if (n_groups && offsets[n_groups] && !index) return PE_ERR_INVALID_ARG;
+    PE_TRY(enter(h));
+    if (h->dist_ready())
+        return fail(h, PE_ERR_STATE, "pe_fast_aggregate_verify: the handle exchanges with other ranks (pe_dist_init); "
+                                     "the sharded handles are not supported");
+    if (n_groups == 0) return PE_OK;
+    if (!h->have_points) return fail(h, PE_ERR_STATE, "pe_fast_aggregate_verify: no pubkeys loaded");
+    // the aggregate pubkeys, summed on the device; the pairs (sum, H(m)), (-g1, signature) of every group
+    std::vector<uint8_t> g1((size_t)192 * n_groups), g2((size_t)384 * n_groups), sums((size_t)96 * n_groups);
+    std::vector<uint32_t> pair_off((size_t)n_groups + 1);
+    PE_TRY(pe_g1_sum(h, nullptr, 0, index, offsets, n_groups, sums.data()));
+    for (uint32_t g = 0; g < n_groups; ++g) {
+        memcpy(&g1[(size_t)192 * g], &sums[(size_t)96 * g], 96);
+        memcpy(&g1[(size_t)192 * g + 96], NEG_G1_BE96, 96);
+        memcpy(&g2[(size_t)384 * g], message_points192 + (size_t)192 * g, 192);
+        memcpy(&g2[(size_t)384 * g + 192], signatures192 + (size_t)192 * g, 192);
+        pair_off[g] = 2 * g;
+    }
+    pair_off[n_groups] = 2 * n_groups;
+    PE_TRY(pairing_run(h, "pe_fast_aggregate_verify", g1.data(), g2.data(), 2ull * n_groups, pair_off.data(), n_groups, verdict,
+                       nullptr));
+    // FastAggregateVerify refuses n = 0, and an identity signature never verifies (the product is 1 there only with an identity
+    // aggregate key, which KeyValidate refuses); a bad point keeps its verdict 2
+    for (uint32_t g = 0; g < n_groups; ++g)
+        if (verdict[g] == 1 && (offsets[g + 1] == offsets[g] || (signatures192[(size_t)192 * g] & 0x40))) verdict[g] = 0;
+    return PE_OK;
+}
+
+}  // extern "C"

@@ -258,6 +258,7 @@ struct pe_engine {
     DevBuf d_ssz_validator_roots;  // hash_tree_root(Validator) of every validator, u8[n_val][32]: the leaves of `validators`
     DevBuf d_ssz_level[2];         // the nodes between two passes of k_ssz_merkle, word form
     DevBuf d_ssz_chunks;           // pe_ssz_merkleize: the caller's chunks
+    DevBuf d_bls;                  // pe_pairing_check: inputs | workspace rows | flags | Fp12 values | verdicts of one call (engine_bls.cpp)
 
     // ---- tree snapshot (pre-order) ----
     bool tree_dirty = true;

@@ -617,4 +617,20 @@ struct SszValidatorArgs {
 };
 void launch_ssz_validator_roots(hipStream_t s, const SszValidatorArgs& a);
 
+// ---- pairing-product check (bls_kernels.hip; host side: engine_bls.cpp) ---------------------------------
+// A group is a 16-lane row (six lane pairs = the six Fp2 coefficients of an Fp12 value, fp12.h), a workgroup is one wave.
+constexpr uint32_t BLS_GROUPS_PER_WAVE = 4;   // = groups per workgroup
+constexpr int BLS_PAIR_WORDS = 144;           // a pair's workspace row: Q.x, Q.y (Fp2), P.x, P.y (Fp), T = X, Y, Z (Fp2), Montgomery
+constexpr int BLS_GT_WORDS = 144;             // a group's Fp12 value between the two kernels: c_k component c at 12 (2 k + c)
+// wire bytes (96-byte G1, 192-byte G2) -> workspace rows; pair_flag: 0 contributes, 1 infinity on a side, 2 off its curve
+void launch_bls_prepare(hipStream_t s, const uint8_t* g1_be96, const uint8_t* g2_be192, uint64_t n_pairs, uint32_t* ws,
+                        int32_t* pair_flag);
+// the Miller loop of every group over pairs [offsets[g], offsets[g + 1]): gt[g] = the conjugated accumulator, group_bad[g] =
+// a pair of the group is flagged 2.  ws / pair_flag hold at least one row even when there is no pair.
+void launch_bls_miller(hipStream_t s, uint32_t* ws, const int32_t* pair_flag, const uint32_t* offsets, uint32_t n_groups,
+                       uint32_t* gt, int32_t* group_bad);
+// verdict[g] = group_bad[g] ? 2 : gt[g]^((p^12 - 1) / r * 3) == 1; out576 (nullable): that power, 12 x 48 bytes big-endian
+void launch_bls_final_exp(hipStream_t s, const uint32_t* gt, const int32_t* group_bad, uint32_t n_groups, int32_t* verdict,
+                          uint8_t* out576);
+
 }  // namespace posevo

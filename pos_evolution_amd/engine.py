@@ -711,6 +711,49 @@ class Engine:
         self._check(self._lib.pe_g2_subgroup_check(self._h, _ptr(pts, C.c_uint8), len(pts), _ptr(st, C.c_int32)))
         return st[:len(pts)]
 
+    @staticmethod
+    def _pair_args(g1_points96, g2_points192, offsets):
+        g1 = np.ascontiguousarray(g1_points96, dtype=np.uint8).reshape(-1, 96)
+        g2 = np.ascontiguousarray(g2_points192, dtype=np.uint8).reshape(-1, 192)
+        off = np.ascontiguousarray(offsets, dtype=np.uint32)
+        if len(g1) != len(g2) or off.size < 1:
+            raise ValueError("one G2 point per G1 point, and n_groups + 1 offsets")
+        return g1, g2, off
+
+    def pairing_check(self, g1_points96, g2_points192, offsets) -> np.ndarray:
+        """pe_pairing_check: int32[n_groups]; 1 = the product of e(P_j, Q_j) over the group's pairs is 1, 0 = it is not,
+        2 = a point of the group is off its curve.  An empty group gives 1; infinity on either side contributes 1."""
+        g1, g2, off = self._pair_args(g1_points96, g2_points192, offsets)
+        verdict = np.zeros(max(off.size - 1, 1), dtype=np.int32)
+        self._check(self._lib.pe_pairing_check(self._h, _ptr(g1, C.c_uint8), _ptr(g2, C.c_uint8), len(g1), _ptr(off, C.c_uint32),
+                                               off.size - 1, _ptr(verdict, C.c_int32)))
+        return verdict[:off.size - 1]
+
+    def fast_aggregate_verify(self, index, offsets, message_points192, signatures192) -> np.ndarray:
+        """pe_fast_aggregate_verify: int32[n_groups]; per group the registry pubkeys index[offsets[g]:offsets[g+1]] are summed
+        on the device and e(sum, message_points192[g]) == e(g1, signatures192[g]) is checked.  1 valid, 0 not (also: empty
+        group, identity signature), 2 = a point off its curve.  The message point H(m) is the caller's."""
+        idx = np.ascontiguousarray(index, dtype=np.uint32)
+        off = np.ascontiguousarray(offsets, dtype=np.uint32)
+        msg = np.ascontiguousarray(message_points192, dtype=np.uint8).reshape(-1, 192)
+        sig = np.ascontiguousarray(signatures192, dtype=np.uint8).reshape(-1, 192)
+        n_groups = off.size - 1
+        if n_groups < 0 or len(msg) != n_groups or len(sig) != n_groups or (n_groups and idx.size < int(off[-1])):
+            raise ValueError("n_groups + 1 offsets, one message point and one signature per group, offsets[-1] indices")
+        verdict = np.zeros(max(n_groups, 1), dtype=np.int32)
+        self._check(self._lib.pe_fast_aggregate_verify(self._h, _ptr(idx, C.c_uint32) if idx.size else None, _ptr(off, C.c_uint32),
+                                                       n_groups, _ptr(msg, C.c_uint8), _ptr(sig, C.c_uint8),
+                                                       _ptr(verdict, C.c_int32)))
+        return verdict[:n_groups]
+
+    def _profile_pairing_gt(self, g1_points96, g2_points192, offsets) -> np.ndarray:
+        """pe_profile_pairing_gt (parity tests only): uint8[n_groups, 576], the value each verdict compares with 1."""
+        g1, g2, off = self._pair_args(g1_points96, g2_points192, offsets)
+        out = np.zeros((max(off.size - 1, 1), 576), dtype=np.uint8)
+        self._check(self._lib.pe_profile_pairing_gt(self._h, _ptr(g1, C.c_uint8), _ptr(g2, C.c_uint8), len(g1),
+                                                    _ptr(off, C.c_uint32), off.size - 1, _ptr(out, C.c_uint8)))
+        return out[:off.size - 1]
+
     def process_attestation_batch(self, state_ctx: pe_state_ctx, rows=None, packed=None, cap: int = 0):
         """-> (status int32[n], proposer_reward_numerator uint64[n]).  ``packed=(ROWS_RESIDENT, RESIDENT), cap=c`` as for
         on_attestation_batch."""

@@ -343,6 +343,21 @@ def get_indexed_attestation(store: Store, attestation):
     return [int(i) for i in indices], attestation.data, getattr(attestation, "signature", None)
 
 
+def fast_aggregate_verify(store: Store, indices: Sequence[int], message_point, signature) -> bool:
+    """bls.FastAggregateVerify(pubkeys of ``indices``, message, signature) -- the check is_valid_indexed_attestation ends with
+    (pe:1456) -- computed on the GPU: the registry pubkeys are summed and e(sum, H(m)) == e(g1, signature) is decided by the
+    pairing-product kernels.  ``message_point`` is H(m) as a 192-byte uncompressed G2 point (hash_to_curve is the caller's),
+    ``signature`` the 192-byte uncompressed aggregate signature.  Returns the computed boolean; it may be passed as
+    ``signature_valid`` wherever the verdict is injected today (attestations, IndexedAttestation).  An empty index list, an
+    identity signature and a point off its curve give False.  Subgroup membership is checked by Engine.g2_subgroup_check /
+    key validation, not here."""
+    idx = np.asarray(list(indices), dtype=np.uint32)
+    verdict = store.engine.fast_aggregate_verify(idx, np.array([0, idx.size], dtype=np.uint32),
+                                                 np.frombuffer(bytes(message_point), dtype=np.uint8),
+                                                 np.frombuffer(bytes(signature), dtype=np.uint8))
+    return int(verdict[0]) == 1
+
+
 def get_head(store: Store) -> bytes:
     """pe:1102-1116.  Raises (AssertionError) when the justified checkpoint has moved and the balances of its state
     have not been handed over (Store.ensure_justified_state)."""
