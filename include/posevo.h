@@ -863,7 +863,7 @@ int pe_g2_subgroup_check(pe_engine* h, const uint8_t* points192, uint64_t n, int
  * Subgroup membership is the caller's: pe_g1_key_validate / pe_g2_subgroup_check.
  * Synchronous (completes open pipelines first); one GPU: PE_ERR_STATE on a handle with pe_dist_init* active.
  * offsets not monotone or past n_pairs: PE_ERR_INVALID_ARG.  Not computed here: hash_to_curve (the caller supplies the
- * message point H(m) in G2) and random-linear-combination batching (one final exponentiation per group). */
+ * message point H(m) in G2).  One final exponentiation per group; pe_batch_verify below pays one per call. */
 #define PE_BLS_VALID 1
 #define PE_BLS_INVALID 0
 #define PE_BLS_BAD_POINT 2
@@ -876,6 +876,27 @@ int pe_pairing_check(pe_engine* h, const uint8_t* g1_points96, const uint8_t* g2
  * PE_ERR_STATE; an index outside the registry: PE_ERR_INVALID_ARG. */
 int pe_fast_aggregate_verify(pe_engine* h, const uint32_t* index, const uint32_t* offsets, uint32_t n_groups,
                              const uint8_t* message_points192, const uint8_t* signatures192, int32_t* verdict);
+/* Many aggregates at once, by random linear combination:
+ *     prod_g e(r_g pk_g, H(m_g)) * e(-G1, sum_g r_g sig_g) == 1
+ * Only the message pairs pay a Miller loop each, and when every group is valid the whole call pays ONE final exponentiation;
+ * otherwise the engine finds the invalid groups itself (per chunk of groups, then one by one).  Formats, host-memory arrays,
+ * synchronous completion and PE_ERR_STATE under pe_dist_init* are those of the calls above.
+ * pe_batch_verify takes one aggregate pubkey per group (96-byte G1, e.g. out_aggpk96 of pe_aggregate_signed, decompressed);
+ * pe_batch_fast_aggregate_verify sums registry[index[j]], j in [offsets[g], offsets[g+1]), as pe_fast_aggregate_verify does.
+ * verdict[g] is what pe_fast_aggregate_verify gives the group, for every input whose signatures lie in G2:
+ *     1  valid     0  invalid (also: an empty group, an identity aggregate key, an identity signature)     2  a point off its curve
+ * and a signature on the curve but outside G2 -- not a BLSSignature -- gives 0: it is decided by the subgroup check before
+ * batching, because the combination is sound over G2 only.  Message points are taken to be hash outputs (in G2) and pubkeys to
+ * be KeyValidated, as in the calls above.
+ * scalars: n_groups non-zero 64-bit values, or NULL: the engine draws them from the operating system's generator (getrandom).
+ * NULL is the production mode.  Caller-supplied scalars MUST BE UNPREDICTABLE to whoever made the signatures: knowing r_1, r_2,
+ * a forger submits sig_1 + r_2 D and sig_2 - r_1 D, whose combination is that of the honest pair, and both groups pass.  With
+ * secret scalars a wrong 1 has probability about 2^-64 per call.  A zero scalar: PE_ERR_INVALID_ARG. */
+int pe_batch_verify(pe_engine* h, const uint8_t* pubkeys96, const uint8_t* message_points192,
+                    const uint8_t* signatures192, uint32_t n_groups, const uint64_t* scalars, int32_t* verdict);
+int pe_batch_fast_aggregate_verify(pe_engine* h, const uint32_t* index, const uint32_t* offsets, uint32_t n_groups,
+                                   const uint8_t* message_points192, const uint8_t* signatures192,
+                                   const uint64_t* scalars, int32_t* verdict);
 
 /* ---- multi-GPU exchange (validator-range shards) ----------- */
 /* Each rank owns a contiguous validator range and the whole (small) block table.

@@ -69,6 +69,18 @@ int pe_profile_accumulate_mhz(pe_engine* h, double* out_mhz, uint32_t cap, uint3
  * Fp6 = Fp2[v] / (v^3 - (1 + u)), Fp12 = Fp6[w] / (w^2 - v), c_(2i+j) is the coefficient of v^i w^j. */
 int pe_profile_pairing_gt(pe_engine* h, const uint8_t* g1_points96, const uint8_t* g2_points192, uint64_t n_pairs,
                           const uint32_t* offsets, uint32_t n_groups, uint8_t* out576);
+/* pe_batch_verify / pe_batch_fast_aggregate_verify.  A chunk is c live groups and the one signature pair they share: c + 1 pairs
+ * on one Miller accumulator.  c is the handle's knob, 1 .. PE_BATCH_CHUNK_MAX; the tests walk it. */
+#define PE_BATCH_CHUNK_MAX 64
+int pe_profile_batch_set_chunk(pe_engine* h, uint32_t chunk);
+/* What the handle's last batch call did: out[0] live groups (what the settle pass left), [1] chunks, [2] launches of the
+ * product tree, [3] values put through the final exponentiation at the top level (1, or 0 without a live group), [4] chunk
+ * values exponentiated in the fallback, [5] groups rechecked one by one, [6] c, [7] F (the product tree's fan-in).
+ * An honest batch shows [3] == 1 and [4] == [5] == 0. */
+int pe_profile_batch_stats(const pe_engine* h, uint32_t out[8]);
+/* The 576 bytes (layout of pe_profile_pairing_gt) the last batch call's top-level verdict compared with 1: the product of the
+ * chunk values raised to (p^12 - 1) / r * 3.  Without a live group: the bytes of 1. */
+int pe_profile_batch_gt(const pe_engine* h, uint8_t* out576);
 
 #ifdef __cplusplus
 }

@@ -179,6 +179,8 @@ SIGNATURES = {
     "pe_g2_subgroup_check": (C.c_int, [_H, _u8p, C.c_uint64, _i32p]),
     "pe_pairing_check": (C.c_int, [_H, _u8p, _u8p, C.c_uint64, _u32p, C.c_uint32, _i32p]),
     "pe_fast_aggregate_verify": (C.c_int, [_H, _u32p, _u32p, C.c_uint32, _u8p, _u8p, _i32p]),
+    "pe_batch_verify": (C.c_int, [_H, _u8p, _u8p, _u8p, C.c_uint32, _u64p, _i32p]),
+    "pe_batch_fast_aggregate_verify": (C.c_int, [_H, _u32p, _u32p, C.c_uint32, _u8p, _u8p, _u64p, _i32p]),
     "pe_pipeline_set_lag": (C.c_int, [_H, C.c_uint32]),
     "pe_pipeline_get_lag": (C.c_uint32, [_H]),
     "pe_pipeline_generation": (C.c_uint64, [_H]),
@@ -280,6 +282,9 @@ SIGNATURES = {
     "pe_profile_committee_sums": (C.c_int, [_H, _P(C.c_uint32), _P(C.c_uint32)]),
     "pe_profile_accumulate_mhz": (C.c_int, [_H, C.c_void_p, C.c_uint32, _P(C.c_uint32)]),
     "pe_profile_pairing_gt": (C.c_int, [_H, _u8p, _u8p, C.c_uint64, _u32p, C.c_uint32, _u8p]),
+    "pe_profile_batch_set_chunk": (C.c_int, [_H, C.c_uint32]),
+    "pe_profile_batch_stats": (C.c_int, [_H, _u32p]),
+    "pe_profile_batch_gt": (C.c_int, [_H, _u8p]),
 }
 
 PE_ROWS_RESIDENT = 1  # include/posevo.h: "every group of the last pe_aggregate over rows in device memory"

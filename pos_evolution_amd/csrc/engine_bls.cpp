@@ -3,15 +3,16 @@
 //   pe_fast_aggregate_verify  per group: e(sum of the group's registry pubkeys, H(m)) e(-g1, signature) == 1; the sum goes the
 //                             route of pe_g1_sum, H(m) is the caller's (hash_to_curve is out of scope)
 //   pe_profile_pairing_gt     the value the verdict compares with 1, for the parity tests
+// (pe_batch_verify, which decides many aggregates with one final exponentiation and falls back on pairing_run: engine_batch.cpp)
 // Both verdict calls are synchronous and complete open pipelines first (enter); one GPU: PE_ERR_STATE under pe_dist_init*.
 #include "engine_internal.h"
 
 using namespace posevo;
 
-namespace {
+namespace posevo {
 
 // -g1: the generator of G1 negated, 96-byte uncompressed form (x, p - y of the published generator)
-const uint8_t NEG_G1_BE96[96] = {
+extern const uint8_t NEG_G1_BE96[96] = {
     0x17, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x94, 0x26, 0x95, 0x63, 0x8c, 0x4f, 0xa9, 0xac, 0x0f,
     0xc3, 0x68, 0x8c, 0x4f, 0x97, 0x74, 0xb9, 0x05, 0xa1, 0x4e, 0x3a, 0x3f, 0x17, 0x1b, 0xac, 0x58,
     0x6c, 0x55, 0xe8, 0x3f, 0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a, 0xdb, 0x22, 0xc6, 0xbb,
@@ -20,7 +21,7 @@ const uint8_t NEG_G1_BE96[96] = {
     0x4e, 0x6f, 0x38, 0xba, 0x0e, 0xcb, 0x75, 0x1b, 0xad, 0x54, 0xdc, 0xd6, 0xb9, 0x39, 0xc2, 0xca
 };
 
-size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
+static size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
 
 int pairing_run(pe_engine* h, const char* who, const uint8_t* g1, const uint8_t* g2, uint64_t n_pairs, const uint32_t* offsets,
                 uint32_t n_groups, int32_t* verdict, uint8_t* out576)
@@ -62,7 +63,7 @@ int pairing_run(pe_engine* h, const char* who, const uint8_t* g1, const uint8_t*
     return PE_OK;
 }
 
-}  // namespace
+}  // namespace posevo
 
 extern "C" {
 

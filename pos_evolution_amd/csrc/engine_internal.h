@@ -259,6 +259,11 @@ struct pe_engine {
     DevBuf d_ssz_level[2];         // the nodes between two passes of k_ssz_merkle, word form
     DevBuf d_ssz_chunks;           // pe_ssz_merkleize: the caller's chunks
     DevBuf d_bls;                  // pe_pairing_check: inputs | workspace rows | flags | Fp12 values | verdicts of one call (engine_bls.cpp)
+    // ---- pe_batch_verify (engine_batch.cpp) ----
+    DevBuf d_batch;                // one call's inputs, Montgomery rows, scaled points, chunk rows, chunk values and product levels
+    uint32_t batch_chunk = 2;      // c: live groups per chunk (pe_profile_batch_set_chunk)
+    uint32_t batch_stats[8] = {};  // pe_profile_batch_stats, of the last call
+    uint8_t batch_gt[576] = {};    // pe_profile_batch_gt, of the last call
 
     // ---- tree snapshot (pre-order) ----
     bool tree_dirty = true;
@@ -558,6 +563,10 @@ int complete_arena(pe_engine* h, int ai);
 void complete_oldest_if_ready(pe_engine* h);
 int flush_pending(pe_engine* h);
 int enter(pe_engine* h);
+// ---- the per-group pairing check (engine_bls.cpp), which pe_batch_verify falls back on
+extern const uint8_t NEG_G1_BE96[96];
+int pairing_run(pe_engine* h, const char* who, const uint8_t* g1, const uint8_t* g2, uint64_t n_pairs, const uint32_t* offsets,
+                uint32_t n_groups, int32_t* verdict, uint8_t* out576);
 // keep_held: the call does not touch what the held-back fork-choice launches read or write and enqueues nothing that must
 // follow them (host-side scalars; the calls that hold or pair themselves): everything else issues them first
 int need_init(pe_engine* h, bool flush = true, bool keep_held = false);

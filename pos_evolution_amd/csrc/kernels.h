@@ -633,4 +633,23 @@ void launch_bls_miller(hipStream_t s, uint32_t* ws, const int32_t* pair_flag, co
 void launch_bls_final_exp(hipStream_t s, const uint32_t* gt, const int32_t* group_bad, uint32_t n_groups, int32_t* verdict,
                           uint8_t* out576);
 
+// ---- batch verification by random linear combination (bls_batch_kernels.hip; host side: engine_batch.cpp) ----
+constexpr uint32_t BLS_BATCH_FAN = 8;  // F: Fp12 values one row of k_bls_gt_product multiplies per launch
+// a group's state after the settle pass; k_g2_subgroup_check turns LIVE into NOT_G2 (its own status 3)
+enum { BLS_BATCH_LIVE = 0, BLS_BATCH_IDENTITY = 1, BLS_BATCH_BAD = 2, BLS_BATCH_NOT_G2 = 3 };
+// wire bytes -> Montgomery rows (pk: x, y; G2: x0 x1 y0 y1, the layout launch_g2_subgroup_check reads) and status[g]
+void launch_bls_batch_settle(hipStream_t s, const uint8_t* pk96, const uint8_t* msg192, const uint8_t* sig192, uint32_t n_groups,
+                             uint32_t* pk_mont24, uint32_t* msg_mont48, uint32_t* sig_mont48, int32_t* status);
+// live group i = group live[i]: row (i / chunk) (chunk + 1) + i % chunk of ws = (scalars[g] pk_g, H(m_g)); pair_flag set
+void launch_bls_scale_g1(hipStream_t s, const uint32_t* live, uint32_t n_live, uint32_t chunk, const uint64_t* scalars,
+                         const uint32_t* pk_mont24, const uint32_t* msg_mont48, uint32_t* ws, int32_t* pair_flag);
+// scaled96[i] = scalars[g] sig_g as an XYZZ point (G2X_WORDS words)
+void launch_bls_scale_g2(hipStream_t s, const uint32_t* live, uint32_t n_live, const uint64_t* scalars, const uint32_t* sig_mont48,
+                         uint32_t* scaled96);
+// chunk j: row j (chunk + 1) + (its live groups) of ws = (-g1, the sum of its scaled96); pair_flag set
+void launch_bls_chunk_sig(hipStream_t s, const uint32_t* scaled96, uint32_t n_live, uint32_t chunk, uint32_t n_chunks,
+                          const uint8_t* neg_g1_be96, uint32_t* ws, int32_t* pair_flag);
+// out[o] = the product of in[o F .. o F + F) (BLS_GT_WORDS each), n_out = ceil(n_in / F)
+void launch_bls_gt_product(hipStream_t s, const uint32_t* in, uint32_t n_in, uint32_t* out, uint32_t n_out);
+
 }  // namespace posevo

@@ -746,6 +746,65 @@ class Engine:
                                                        _ptr(verdict, C.c_int32)))
         return verdict[:n_groups]
 
+    @staticmethod
+    def _batch_scalars(scalars, n_groups):
+        if scalars is None:
+            return None, None
+        r = np.ascontiguousarray(scalars, dtype=np.uint64)
+        if r.size != n_groups:
+            raise ValueError("one scalar per group")
+        return r, (_ptr(r, C.c_uint64) if r.size else None)
+
+    def batch_verify(self, pubkeys96, message_points192, signatures192, scalars=None) -> np.ndarray:
+        """pe_batch_verify: int32[n_groups], the verdicts of fast_aggregate_verify for groups given by their aggregate pubkey,
+        reached by random linear combination: one final exponentiation for the whole call when every group is valid.
+        ``scalars=None`` (production): the engine draws secret 64-bit scalars.  Scalars the signers can predict let a pair of
+        forged signatures pass; a signature outside G2 gives 0."""
+        pk = np.ascontiguousarray(pubkeys96, dtype=np.uint8).reshape(-1, 96)
+        msg = np.ascontiguousarray(message_points192, dtype=np.uint8).reshape(-1, 192)
+        sig = np.ascontiguousarray(signatures192, dtype=np.uint8).reshape(-1, 192)
+        n_groups = len(pk)
+        if len(msg) != n_groups or len(sig) != n_groups:
+            raise ValueError("one pubkey, one message point and one signature per group")
+        r, r_ptr = self._batch_scalars(scalars, n_groups)
+        verdict = np.zeros(max(n_groups, 1), dtype=np.int32)
+        self._check(self._lib.pe_batch_verify(self._h, _ptr(pk, C.c_uint8), _ptr(msg, C.c_uint8), _ptr(sig, C.c_uint8), n_groups,
+                                              r_ptr, _ptr(verdict, C.c_int32)))
+        return verdict[:n_groups]
+
+    def batch_fast_aggregate_verify(self, index, offsets, message_points192, signatures192, scalars=None) -> np.ndarray:
+        """pe_batch_fast_aggregate_verify: fast_aggregate_verify's arguments and verdicts, decided as batch_verify decides."""
+        idx = np.ascontiguousarray(index, dtype=np.uint32)
+        off = np.ascontiguousarray(offsets, dtype=np.uint32)
+        msg = np.ascontiguousarray(message_points192, dtype=np.uint8).reshape(-1, 192)
+        sig = np.ascontiguousarray(signatures192, dtype=np.uint8).reshape(-1, 192)
+        n_groups = off.size - 1
+        if n_groups < 0 or len(msg) != n_groups or len(sig) != n_groups or (n_groups and idx.size < int(off[-1])):
+            raise ValueError("n_groups + 1 offsets, one message point and one signature per group, offsets[-1] indices")
+        r, r_ptr = self._batch_scalars(scalars, n_groups)
+        verdict = np.zeros(max(n_groups, 1), dtype=np.int32)
+        self._check(self._lib.pe_batch_fast_aggregate_verify(self._h, _ptr(idx, C.c_uint32) if idx.size else None,
+                                                             _ptr(off, C.c_uint32), n_groups, _ptr(msg, C.c_uint8),
+                                                             _ptr(sig, C.c_uint8), r_ptr, _ptr(verdict, C.c_int32)))
+        return verdict[:n_groups]
+
+    def _profile_batch_set_chunk(self, chunk: int) -> None:
+        """pe_profile_batch_set_chunk: c, the live groups of one chunk of the batch calls."""
+        self._check(self._lib.pe_profile_batch_set_chunk(self._h, int(chunk)))
+
+    def _profile_batch_stats(self) -> dict:
+        """pe_profile_batch_stats: what the last batch call did."""
+        out = np.zeros(8, dtype=np.uint32)
+        self._check(self._lib.pe_profile_batch_stats(self._h, _ptr(out, C.c_uint32)))
+        names = ("live", "chunks", "product_launches", "top_exps", "fallback_exps", "rechecked", "c", "F")
+        return dict(zip(names, (int(v) for v in out)))
+
+    def _profile_batch_gt(self) -> bytes:
+        """pe_profile_batch_gt: the 576 bytes the last batch call's top-level verdict compared with 1."""
+        out = np.zeros(576, dtype=np.uint8)
+        self._check(self._lib.pe_profile_batch_gt(self._h, _ptr(out, C.c_uint8)))
+        return out.tobytes()
+
     def _profile_pairing_gt(self, g1_points96, g2_points192, offsets) -> np.ndarray:
         """pe_profile_pairing_gt (parity tests only): uint8[n_groups, 576], the value each verdict compares with 1."""
         g1, g2, off = self._pair_args(g1_points96, g2_points192, offsets)

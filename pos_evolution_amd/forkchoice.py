@@ -358,6 +358,20 @@ def fast_aggregate_verify(store: Store, indices: Sequence[int], message_point, s
     return int(verdict[0]) == 1
 
 
+def batch_fast_aggregate_verify(store: Store, index_lists: Sequence[Sequence[int]], message_points, signatures) -> list:
+    """bls.FastAggregateVerify for many aggregates at once -- one list of indices, one H(m) and one signature (192-byte
+    uncompressed G2 points) per aggregate -- by random linear combination with scalars the engine draws itself
+    (Engine.batch_fast_aggregate_verify): one final exponentiation for the whole call when every aggregate is valid.  Returns one
+    boolean per aggregate, each what fast_aggregate_verify returns for it; a signature outside G2 gives False."""
+    lists = [np.asarray(list(ix), dtype=np.uint32) for ix in index_lists]
+    off = np.cumsum([0] + [ix.size for ix in lists]).astype(np.uint32)
+    idx = np.concatenate(lists) if lists else np.zeros(0, dtype=np.uint32)
+    verdict = store.engine.batch_fast_aggregate_verify(
+        idx, off, np.frombuffer(b"".join(bytes(m) for m in message_points), dtype=np.uint8),
+        np.frombuffer(b"".join(bytes(s) for s in signatures), dtype=np.uint8))
+    return [int(v) == 1 for v in verdict]
+
+
 def get_head(store: Store) -> bytes:
     """pe:1102-1116.  Raises (AssertionError) when the justified checkpoint has moved and the balances of its state
     have not been handed over (Store.ensure_justified_state)."""
