@@ -897,6 +897,34 @@ int pe_batch_verify(pe_engine* h, const uint8_t* pubkeys96, const uint8_t* messa
 int pe_batch_fast_aggregate_verify(pe_engine* h, const uint32_t* index, const uint32_t* offsets, uint32_t n_groups,
                                    const uint8_t* message_points192, const uint8_t* signatures192,
                                    const uint64_t* scalars, int32_t* verdict);
+/* An epoch's UNAGGREGATED signatures, each decided: an aggregate can be valid while two of its members are forged (sig_a + D and
+ * sig_b - D sum to the honest aggregate), so pe_aggregate_signatures' output says nothing about its members.  All members of a
+ * group signed the same message (one committee's votes for one AttestationData), and with secret weights r_j
+ *     e(sum_j r_j pk_j, H(m_g)) * e(-G1, sum_j r_j sig_j) == 1
+ * decides them all with ONE two-pair check per group; the two weighted sums are the device's work (k_g1_weighted_accumulate,
+ * k_g2_weighted_accumulate).  Only a group that fails pays one pairing check per member, all such groups in one further run.
+ *   signatures96   n compressed BLSSignatures, host or device memory, as pe_aggregate_signatures takes them
+ *   index          host; member j's signature is signatures96[index[j]]; NULL: member j's is signatures96[j]
+ *   signer         host; member j's validator index: its pubkey is the registry's (taken as KeyValidated)
+ *   offsets        host; group g = members [offsets[g], offsets[g+1])
+ *   message_points192   H(m_g), one 192-byte G2 point per group (hash_to_curve is the caller's)
+ *   scalars        host; one non-zero 64-bit r_j per member, or NULL: drawn from getrandom.  NULL is the production mode.
+ *                  Caller-supplied scalars MUST BE UNPREDICTABLE to the signers, exactly as for pe_batch_verify: with r_a = r_b
+ *                  known, sig_a + D and sig_b - D both pass.  With secret scalars a wrong 1 has probability <= 2^-64 per group.
+ *   member_verdict per member: 1 valid, 0 not
+ *   sig_status     nullable, per member: 0 ok, 1 malformed, 2 off the curve, 3 on the curve outside G2 (the subgroup test is
+ *                  always on: the combination is sound over G2 only), PE_SIG_STATUS_IDENTITY the point at infinity.  A member
+ *                  whose status is not 0 has verdict 0 and is left out of both sums: it cannot spoil its group.
+ *   group_verdict  1 iff every member's verdict is 1 (an empty group: 1); 2: H(m_g) is not on its curve (its members: 0);
+ *                  a group whose message point is the identity has 0, and so has every member
+ *   out_signatures96   nullable: per group the compressed aggregate of the members with verdict 1 (none: infinity) -- for a
+ *                  group without a bad member byte for byte pe_aggregate_signatures(..., PE_SIG_CHECK_SUBGROUP)'s
+ * Synchronous; completes open pipelines first.  PE_ERR_STATE without pubkeys or under pe_dist_init*; PE_ERR_INVALID_ARG for a
+ * zero scalar, a signer outside the registry, an index outside n, non-monotone offsets: nothing is written then. */
+#define PE_SIG_STATUS_IDENTITY 4
+int pe_verify_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t n, const uint32_t* index, const uint32_t* signer,
+                         const uint32_t* offsets, uint32_t n_groups, const uint8_t* message_points192, const uint64_t* scalars,
+                         int32_t* member_verdict, int32_t* sig_status, int32_t* group_verdict, uint8_t* out_signatures96);
 
 /* ---- multi-GPU exchange (validator-range shards) ----------- */
 /* Each rank owns a contiguous validator range and the whole (small) block table.

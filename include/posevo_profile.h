@@ -82,6 +82,18 @@ int pe_profile_batch_stats(const pe_engine* h, uint32_t out[8]);
  * chunk values raised to (p^12 - 1) / r * 3.  Without a live group: the bytes of 1. */
 int pe_profile_batch_gt(const pe_engine* h, uint8_t* out576);
 
+/* pe_verify_signatures.  A slot of the weighted sums is a stripe of k members of one group (one Horner pass over the 64 bit
+ * planes per stripe: 64 / k doublings per point); k is the handle's knob, 1 .. PE_VERIFY_STRIPE_MAX; the tests walk it to reach
+ * the layout's edges with a few hundred points. */
+#define PE_VERIFY_STRIPE_MAX 16
+int pe_profile_verify_set_stripe(pe_engine* h, uint32_t k);
+/* What the handle's last pe_verify_signatures did: out[0] members the settle pass decided (status != 0), [1] groups whose
+ * combined check failed, [2] members rechecked one by one, [3] pairing runs (1, or 2 with the locate pass), [4] k. */
+int pe_profile_verify_stats(const pe_engine* h, uint32_t out[5]);
+/* The last call's weighted sums per group, canonical affine wire bytes: sum_j r_j pk_j (96 each) and sum_j r_j sig_j (192 each)
+ * over the members the settle pass left.  n_groups must be the last call's. */
+int pe_profile_verify_sums(const pe_engine* h, uint32_t n_groups, uint8_t* out_pk96, uint8_t* out_sig192);
+
 #ifdef __cplusplus
 }
 #endif

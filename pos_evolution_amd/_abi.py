@@ -21,6 +21,7 @@ PE_ERR_STATE = -14
 PE_ERR_TIMEOUT = -15
 PE_DIST_SINGLE_COMM = 1
 PE_SIG_G2_COMPRESSED, PE_SIG_G2_UNCOMPRESSED, PE_SIG_CHECK_SUBGROUP = 1, 2, 0x100
+PE_SIG_STATUS_IDENTITY = 4  # pe_verify_signatures: the signature is the point at infinity
 NONE32 = 0xFFFFFFFF
 
 PE_VAL_ACTIVE, PE_VAL_SLASHED, PE_VAL_EQUIVOCATING, PE_VAL_ACTIVE_PREV = 0x01, 0x02, 0x04, 0x08
@@ -181,6 +182,8 @@ SIGNATURES = {
     "pe_fast_aggregate_verify": (C.c_int, [_H, _u32p, _u32p, C.c_uint32, _u8p, _u8p, _i32p]),
     "pe_batch_verify": (C.c_int, [_H, _u8p, _u8p, _u8p, C.c_uint32, _u64p, _i32p]),
     "pe_batch_fast_aggregate_verify": (C.c_int, [_H, _u32p, _u32p, C.c_uint32, _u8p, _u8p, _u64p, _i32p]),
+    "pe_verify_signatures": (C.c_int, [_H, C.c_void_p, C.c_uint64, _u32p, _u32p, _u32p, C.c_uint32, _u8p, _u64p, _i32p, _i32p, _i32p,
+                                       _u8p]),
     "pe_pipeline_set_lag": (C.c_int, [_H, C.c_uint32]),
     "pe_pipeline_get_lag": (C.c_uint32, [_H]),
     "pe_pipeline_generation": (C.c_uint64, [_H]),
@@ -285,6 +288,9 @@ SIGNATURES = {
     "pe_profile_batch_set_chunk": (C.c_int, [_H, C.c_uint32]),
     "pe_profile_batch_stats": (C.c_int, [_H, _u32p]),
     "pe_profile_batch_gt": (C.c_int, [_H, _u8p]),
+    "pe_profile_verify_set_stripe": (C.c_int, [_H, C.c_uint32]),
+    "pe_profile_verify_stats": (C.c_int, [_H, _u32p]),
+    "pe_profile_verify_sums": (C.c_int, [_H, C.c_uint32, _u8p, _u8p]),
 }
 
 PE_ROWS_RESIDENT = 1  # include/posevo.h: "every group of the last pe_aggregate over rows in device memory"

@@ -17,9 +17,7 @@
 
 using namespace posevo;
 
-namespace {
-
-size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
+namespace posevo {
 
 int draw_scalars(pe_engine* h, std::vector<uint64_t>& out)
 {
@@ -27,15 +25,21 @@ int draw_scalars(pe_engine* h, std::vector<uint64_t>& out)
     size_t left = out.size() * sizeof(uint64_t);
     while (left) {
         const ssize_t got = getrandom(p, std::min<size_t>(left, 256), 0);  // up to 256 bytes are never interrupted
-        if (got <= 0) return fail(h, PE_ERR_STATE, "pe_batch_verify: getrandom failed");
+        if (got <= 0) return fail(h, PE_ERR_STATE, "getrandom failed");
         p += got;
         left -= (size_t)got;
     }
     for (uint64_t& r : out)
         while (r == 0)
-            if (getrandom(&r, sizeof(r), 0) != (ssize_t)sizeof(r)) return fail(h, PE_ERR_STATE, "pe_batch_verify: getrandom failed");
+            if (getrandom(&r, sizeof(r), 0) != (ssize_t)sizeof(r)) return fail(h, PE_ERR_STATE, "getrandom failed");
     return PE_OK;
 }
+
+}  // namespace posevo
+
+namespace {
+
+size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
 
 int batch_run(pe_engine* h, const char* who, const uint8_t* pk96, const uint8_t* msg192, const uint8_t* sig192, uint32_t n,
               const uint64_t* scalars, int32_t* verdict)

@@ -264,6 +264,11 @@ struct pe_engine {
     uint32_t batch_chunk = 2;      // c: live groups per chunk (pe_profile_batch_set_chunk)
     uint32_t batch_stats[8] = {};  // pe_profile_batch_stats, of the last call
     uint8_t batch_gt[576] = {};    // pe_profile_batch_gt, of the last call
+    // ---- pe_verify_signatures (engine_sigverify.cpp) ----
+    DevBuf d_verify;                // one call's member lists, scalars, plans, partials, sums and locate rows
+    uint32_t verify_stripe = 16;    // k: members per slot of the weighted sums (pe_profile_verify_set_stripe)
+    uint32_t verify_stats[5] = {};  // pe_profile_verify_stats, of the last call
+    std::vector<uint8_t> verify_sums_pk, verify_sums_sig;  // pe_profile_verify_sums, of the last call (96 / 192 bytes a group)
 
     // ---- tree snapshot (pre-order) ----
     bool tree_dirty = true;
@@ -565,6 +570,7 @@ int flush_pending(pe_engine* h);
 int enter(pe_engine* h);
 // ---- the per-group pairing check (engine_bls.cpp), which pe_batch_verify falls back on
 extern const uint8_t NEG_G1_BE96[96];
+int draw_scalars(pe_engine* h, std::vector<uint64_t>& out);  // non-zero 64-bit values from getrandom (engine_batch.cpp)
 int pairing_run(pe_engine* h, const char* who, const uint8_t* g1, const uint8_t* g2, uint64_t n_pairs, const uint32_t* offsets,
                 uint32_t n_groups, int32_t* verdict, uint8_t* out576);
 // keep_held: the call does not touch what the held-back fork-choice launches read or write and enqueues nothing that must
@@ -780,14 +786,15 @@ struct G1Plan {
 // fills them in afterwards).
 // wg_slots = task slots per workgroup (G1: one lane per slot; G2: a lane pair per slot), target_slots = slots that
 // fill the chip at two waves per SIMD.
+// fixed_k: members per slot as given (the weighted sums, whose stripe is a knob), 0 = chosen to fill the chip.
 template <typename SizeFn>
 void plan_g1(uint32_t n_groups, SizeFn size_of, G1Group* out, G1Plan* plan, uint32_t wg_slots = G1_WG,
-             uint32_t target_slots = G1_TARGET_LANES)
+             uint32_t target_slots = G1_TARGET_LANES, uint32_t fixed_k = 0)
 {
     uint64_t total = 0;
     for (uint32_t g = 0; g < n_groups; ++g) total += size_of(g);
     const uint32_t min_k = G1_MIN_K;
-    const uint32_t k = (uint32_t)std::max<uint64_t>(min_k, (total + target_slots - 1) / target_slots);
+    const uint32_t k = fixed_k ? fixed_k : (uint32_t)std::max<uint64_t>(min_k, (total + target_slots - 1) / target_slots);
     uint32_t cursor = 0, outp = 0;
     for (uint32_t g = 0; g < n_groups; ++g) {
         G1Group& d = out[g];

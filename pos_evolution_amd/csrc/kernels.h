@@ -652,4 +652,20 @@ void launch_bls_chunk_sig(hipStream_t s, const uint32_t* scaled96, uint32_t n_li
 // out[o] = the product of in[o F .. o F + F) (BLS_GT_WORDS each), n_out = ceil(n_in / F)
 void launch_bls_gt_product(hipStream_t s, const uint32_t* in, uint32_t n_in, uint32_t* out, uint32_t n_out);
 
+// ---- per-member signature verification: weighted sums per committee (sigverify_kernels.hip; host side: engine_sigverify.cpp) ----
+constexpr uint32_t SV_STRIPE_MAX = 16;  // members per slot at most: a plane's mask of set members is 16 bits
+// wg_partials96 = per (group, workgroup) sum of scalars[m] * row (index ? index[m] : m) of points_mont48 over the group's members
+// m: k_g2_accumulate's plan and partials (launch_g2_finish takes them), G1Group::k <= SV_STRIPE_MAX
+void launch_g2_weighted_accumulate(hipStream_t s, const uint32_t* points_mont48, const uint32_t* index, const uint64_t* scalars,
+                                   const G1Group* groups, uint32_t n_groups, uint32_t n_slots, uint32_t* wg_partials96);
+// the same over registry rows (G1_ROW_WORDS words each) signer[m]: a plan of G1_WG slots per workgroup, partials of G1X_WORDS
+// words as launch_g1_finish takes them
+void launch_g1_weighted_accumulate(hipStream_t s, const uint32_t* points_mont, const uint32_t* signer, const uint64_t* scalars,
+                                   const G1Group* groups, uint32_t n_groups, uint32_t n_slots, uint32_t* wg_partials48);
+// status[i] = code where it is 0 and row i of points_mont48 is the (0, 0) row
+void launch_sv_mark_identity(hipStream_t s, const uint32_t* points_mont48, uint64_t n, int32_t* status, int32_t code);
+// rows of the registry / of the decoded signatures back to wire bytes (96 / 192 each), for the locate pass
+void launch_sv_rows_g1(hipStream_t s, const uint32_t* points_mont, const uint32_t* rows, uint32_t n, uint8_t* out_be96);
+void launch_sv_rows_g2(hipStream_t s, const uint32_t* points_mont48, const uint32_t* rows, uint32_t n, uint8_t* out_be192);
+
 }  // namespace posevo

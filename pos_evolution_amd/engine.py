@@ -752,7 +752,7 @@ class Engine:
             return None, None
         r = np.ascontiguousarray(scalars, dtype=np.uint64)
         if r.size != n_groups:
-            raise ValueError("one scalar per group")
+            raise ValueError("one scalar per group (verify_signatures: per member)")
         return r, (_ptr(r, C.c_uint64) if r.size else None)
 
     def batch_verify(self, pubkeys96, message_points192, signatures192, scalars=None) -> np.ndarray:
@@ -787,6 +787,59 @@ class Engine:
                                                              _ptr(off, C.c_uint32), n_groups, _ptr(msg, C.c_uint8),
                                                              _ptr(sig, C.c_uint8), r_ptr, _ptr(verdict, C.c_int32)))
         return verdict[:n_groups]
+
+    def verify_signatures(self, signatures, signer, offsets, message_points192, index=None, scalars=None, aggregates=True):
+        """pe_verify_signatures: every unaggregated signature of an epoch decided, one pairing check per group.  Group g is the
+        members [offsets[g], offsets[g+1]) -- one committee's votes for one AttestationData, so one message point
+        message_points192[g] --, member j is signed by validator signer[j] with signatures[index[j]] (index=None: signatures[j]).
+        signatures: (n, 96) uint8 array or a DeviceArena of n * 96 bytes.  ``scalars=None`` (production): the engine draws one
+        secret 64-bit weight per member; weights the signers can predict let a cancelling pair of forged signatures pass.
+        -> (member_verdict int32 (members,): 1 valid, 0 not;  sig_status int32 (members,): 0 ok, 1 malformed, 2 off the curve,
+        3 outside G2, 4 the identity;  group_verdict int32 (n_groups,): 1 iff every member is valid, 2 = H(m) off its curve;
+        aggregates (n_groups, 96) uint8: per group the compressed sum of the valid members' signatures, or None)."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint32)
+        n_groups = off.size - 1
+        who = np.ascontiguousarray(signer, dtype=np.uint32)
+        msg = np.ascontiguousarray(message_points192, dtype=np.uint8).reshape(-1, 192)
+        members = int(off[-1]) if n_groups > 0 else 0
+        if n_groups < 0 or len(msg) != n_groups or who.size != members:
+            raise ValueError("n_groups + 1 offsets, one message point per group, one signer per member")
+        if isinstance(signatures, DeviceArena):
+            sig_ptr, n = signatures.ptr, signatures.size // 96
+        else:
+            sig = np.ascontiguousarray(signatures, dtype=np.uint8)
+            sig_ptr, n = sig.ctypes.data, sig.size // 96
+        idx = None if index is None else np.ascontiguousarray(index, dtype=np.uint32)
+        if idx is not None and idx.size != members:
+            raise ValueError("one index per member")
+        r, r_ptr = self._batch_scalars(scalars, members)
+        verdict = np.zeros(max(members, 1), dtype=np.int32)
+        status = np.zeros(max(members, 1), dtype=np.int32)
+        group = np.zeros(max(n_groups, 1), dtype=np.int32)
+        out = np.zeros((max(n_groups, 1), 96), dtype=np.uint8) if aggregates else None
+        self._check(self._lib.pe_verify_signatures(
+            self._h, C.c_void_p(sig_ptr), n, _ptr(idx, C.c_uint32) if idx is not None and idx.size else None,
+            _ptr(who, C.c_uint32) if who.size else None, _ptr(off, C.c_uint32), n_groups, _ptr(msg, C.c_uint8) if n_groups else None,
+            r_ptr, _ptr(verdict, C.c_int32), _ptr(status, C.c_int32), _ptr(group, C.c_int32),
+            _ptr(out, C.c_uint8) if aggregates else None))
+        return verdict[:members], status[:members], group[:n_groups], (out[:n_groups] if aggregates else None)
+
+    def _profile_verify_set_stripe(self, k: int) -> None:
+        """pe_profile_verify_set_stripe: k, the members of one slot of verify_signatures' weighted sums."""
+        self._check(self._lib.pe_profile_verify_set_stripe(self._h, int(k)))
+
+    def _profile_verify_stats(self) -> dict:
+        """pe_profile_verify_stats: what the last verify_signatures did."""
+        out = np.zeros(5, dtype=np.uint32)
+        self._check(self._lib.pe_profile_verify_stats(self._h, _ptr(out, C.c_uint32)))
+        return dict(zip(("settled", "failed_groups", "rechecked", "pairing_runs", "k"), (int(v) for v in out)))
+
+    def _profile_verify_sums(self, n_groups: int):
+        """pe_profile_verify_sums: the last verify_signatures' weighted sums per group, (n_groups, 96) and (n_groups, 192)."""
+        pk = np.zeros((max(n_groups, 1), 96), dtype=np.uint8)
+        sig = np.zeros((max(n_groups, 1), 192), dtype=np.uint8)
+        self._check(self._lib.pe_profile_verify_sums(self._h, int(n_groups), _ptr(pk, C.c_uint8), _ptr(sig, C.c_uint8)))
+        return pk[:n_groups], sig[:n_groups]
 
     def _profile_batch_set_chunk(self, chunk: int) -> None:
         """pe_profile_batch_set_chunk: c, the live groups of one chunk of the batch calls."""

@@ -372,6 +372,23 @@ def batch_fast_aggregate_verify(store: Store, index_lists: Sequence[Sequence[int
     return [int(v) == 1 for v in verdict]
 
 
+def verify_attestation_signatures(store: Store, signers: Sequence[Sequence[int]], message_points, signatures) -> list:
+    """One boolean per UNAGGREGATED attestation: ``signers[g]`` are the validators whose single-signer attestations carry the
+    same AttestationData (one committee's votes), ``message_points[g]`` is H(m) of that data as a 192-byte uncompressed G2 point
+    (hash_to_curve is the caller's) and ``signatures[g]`` their 96-byte compressed BLSSignatures, in the order of ``signers[g]``.
+    Engine.verify_signatures decides each group with one pairing check over sums weighted by scalars the engine draws itself,
+    and finds the invalid members of a group that fails.  Returns a list of lists of booleans, shaped like ``signers``; each may
+    be passed as ``signature_valid`` wherever the verdict is injected today.  A valid aggregate says nothing about its members
+    (sig_a + D and sig_b - D sum to the honest aggregate): this call is what does."""
+    lists = [np.asarray(list(ix), dtype=np.uint32) for ix in signers]
+    off = np.cumsum([0] + [ix.size for ix in lists]).astype(np.uint32)
+    who = np.concatenate(lists) if lists else np.zeros(0, dtype=np.uint32)
+    sig = np.frombuffer(b"".join(bytes(s) for group in signatures for s in group), dtype=np.uint8)
+    msg = np.frombuffer(b"".join(bytes(m) for m in message_points), dtype=np.uint8)
+    verdict, _, _, _ = store.engine.verify_signatures(sig, who, off, msg, aggregates=False)
+    return [[int(v) == 1 for v in verdict[off[g]:off[g + 1]]] for g in range(len(lists))]
+
+
 def get_head(store: Store) -> bytes:
     """pe:1102-1116.  Raises (AssertionError) when the justified checkpoint has moved and the balances of its state
     have not been handed over (Store.ensure_justified_state)."""
