@@ -13,83 +13,17 @@
 //   k_bls_chunk_sig     a lane pair per chunk: the sum of the chunk's r sig, affine, as the chunk's last row (P = -g1)
 //   k_bls_gt_product    a 16-lane row per output: the product of up to BLS_BATCH_FAN Fp12 values (one level of the tree)
 //
+// Shared with bls_kernels.hip: the wire decoders (wire_points.h), the workspace row's layout (kernels.h), f12_one_coeff (fp12.h),
+// the dword movers (fp_mem.h: these rows are written and read word by word).
 // The point formulas are the complete ones of g1.h / g2.h (infinity, P = Q, P = -Q): the inputs are curve points, not
 // necessarily subgroup points, and r P may meet P again or infinity on a point of small order.
 #include "fp12.h"
+#include "fp_mem.h"
 #include "fp_sqrt.h"
 #include "kernels.h"
+#include "wire_points.h"
 
 namespace posevo {
-
-enum { BLS_PAIR_LIVE = 0, BLS_PAIR_SKIP = 1 };  // pair_flag of bls_kernels.hip: contributes | contributes 1
-constexpr int BLS_WS_P = 4, BLS_WS_T = 6;       // the workspace row in fp values: Q.x, Q.y (two each), P.x, P.y, T = X, Y, Z
-
-__device__ __forceinline__ void bb_ld(fp& r, const uint32_t* __restrict__ p)
-{
-#pragma unroll
-    for (int j = 0; j < 12; ++j) r.l[j] = p[j];
-}
-__device__ __forceinline__ void bb_st(uint32_t* __restrict__ p, const fp& a)
-{
-#pragma unroll
-    for (int j = 0; j < 12; ++j) p[j] = a.l[j];
-}
-__device__ __forceinline__ void bb_four(fp& r)
-{
-    fp t;
-    fp_set_zero(t);
-    t.l[0] = 4;
-    fp_to_mont(r, t);
-}
-// 96 wire bytes -> (x, y) in Montgomery form, zero for the identity; returns "not a point of y^2 = x^3 + 4"
-__device__ __forceinline__ bool bb_load_g1(fp& mx, fp& my, bool& inf, const uint8_t* __restrict__ a)
-{
-    fp_set_zero(mx);
-    fp_set_zero(my);
-    inf = (a[0] & 0x40) != 0;
-    if (inf) return false;
-    fp x, y, t, u, four;
-    fp_load_be48(x, a);
-    fp_load_be48(y, a + 48);
-    y.l[11] = __builtin_bswap32(reinterpret_cast<const uint32_t*>(a + 48)[0]);  // only the leading byte has flags
-    bool bad = (a[0] & 0x80) != 0 || !fp_is_canonical(x) || !fp_is_canonical(y);
-    fp_to_mont(mx, x);
-    fp_to_mont(my, y);
-    bb_four(four);
-    fp_sqr(t, mx);
-    fp_mul(t, t, mx);
-    fp_add(t, t, four);
-    fp_sqr(u, my);
-    bad |= !fp_eq(t, u);
-    return bad;
-}
-// 192 wire bytes (c1 first) -> this lane's halves of (x, y); returns "not a point of y^2 = x^3 + 4 (1 + u)" (pair-wide)
-__device__ __forceinline__ bool bb_load_g2(fp& mx, fp& my, bool& inf, const uint8_t* __restrict__ b, bool role)
-{
-    fp_set_zero(mx);
-    fp_set_zero(my);
-    inf = (b[0] & 0x40) != 0;
-    bool bad = false;
-    if (!inf) {  // both lanes of the pair take this branch
-        fp x, y, t, u, four;
-        const uint8_t* xs = b + (role ? 0 : 48);
-        const uint8_t* ys = b + 96 + (role ? 0 : 48);
-        fp_load_be48(x, xs);
-        if (!role) x.l[11] = __builtin_bswap32(reinterpret_cast<const uint32_t*>(xs)[0]);
-        fp_load_be48(y, ys);
-        y.l[11] = __builtin_bswap32(reinterpret_cast<const uint32_t*>(ys)[0]);
-        bad = (b[0] & 0x80) != 0 || !fp_is_canonical(x) || !fp_is_canonical(y);
-        fp_to_mont(mx, x);
-        fp_to_mont(my, y);
-        bb_four(four);
-        f2_sqr(t, mx, role);
-        f2_mul(t, t, mx, role);
-        fp_add(t, t, four);
-        f2_sqr(u, my, role);
-        bad |= !fp_eq(t, u);
-    }
-    return !pair_and(!bad);
-}
 
 // ---------------------------------------------------------------- settle
 // status[g]: BLS_BATCH_LIVE stays a candidate, BLS_BATCH_IDENTITY an identity key, message point or signature (verdict 0),
@@ -105,14 +39,14 @@ __global__ void __launch_bounds__(256) k_bls_batch_settle(const uint8_t* __restr
     const bool role = (gid & 1) != 0;
     fp px, py, mx, my, sx, sy;
     bool p_inf, m_inf, s_inf;
-    bool bad = bb_load_g1(px, py, p_inf, pk96 + (size_t)96 * g);
-    bad |= bb_load_g2(mx, my, m_inf, msg192 + (size_t)192 * g, role);
-    bad |= bb_load_g2(sx, sy, s_inf, sig192 + (size_t)192 * g, role);
-    bb_st(pk_mont24 + (size_t)24 * g + 12 * (int)role, role ? py : px);
-    bb_st(msg_mont48 + (size_t)48 * g + 12 * (int)role, mx);
-    bb_st(msg_mont48 + (size_t)48 * g + 12 * (2 + (int)role), my);
-    bb_st(sig_mont48 + (size_t)48 * g + 12 * (int)role, sx);
-    bb_st(sig_mont48 + (size_t)48 * g + 12 * (2 + (int)role), sy);
+    bool bad = wire_load_g1(px, py, p_inf, pk96 + (size_t)96 * g);
+    bad |= wire_load_g2(mx, my, m_inf, msg192 + (size_t)192 * g, role);
+    bad |= wire_load_g2(sx, sy, s_inf, sig192 + (size_t)192 * g, role);
+    fp_words::st(pk_mont24 + (size_t)24 * g + 12 * (int)role, role ? py : px);
+    fp_words::st(msg_mont48 + (size_t)48 * g + 12 * (int)role, mx);
+    fp_words::st(msg_mont48 + (size_t)48 * g + 12 * (2 + (int)role), my);
+    fp_words::st(sig_mont48 + (size_t)48 * g + 12 * (int)role, sx);
+    fp_words::st(sig_mont48 + (size_t)48 * g + 12 * (2 + (int)role), sy);
     if (!role) status[g] = bad ? BLS_BATCH_BAD : (p_inf || m_inf || s_inf) ? BLS_BATCH_IDENTITY : BLS_BATCH_LIVE;
 }
 
@@ -129,8 +63,8 @@ __global__ void __launch_bounds__(64) k_bls_scale_g1(const uint32_t* __restrict_
     const uint32_t g = live[i];
     const uint64_t r = scalars[g];
     fp px, py;
-    bb_ld(px, pk_mont24 + (size_t)24 * g);
-    bb_ld(py, pk_mont24 + (size_t)24 * g + 12);
+    fp_words::ld(px, pk_mont24 + (size_t)24 * g);
+    fp_words::ld(py, pk_mont24 + (size_t)24 * g + 12);
     g1x acc;
     g1x_set_inf(acc);
 #pragma unroll 1
@@ -156,8 +90,8 @@ __global__ void __launch_bounds__(64) k_bls_scale_g1(const uint32_t* __restrict_
         row[j] = w;                  // Q
         row[12 * BLS_WS_T + j] = w;  // T = (Q.x, Q.y, 1)
     }
-    bb_st(row + 12 * BLS_WS_P, x);
-    bb_st(row + 12 * (BLS_WS_P + 1), y);
+    fp_words::st(row + 12 * BLS_WS_P, x);
+    fp_words::st(row + 12 * (BLS_WS_P + 1), y);
 #pragma unroll
     for (int j = 0; j < 12; ++j) {
         row[12 * (BLS_WS_T + 4) + j] = fp_r1_limb(j);
@@ -171,23 +105,6 @@ __global__ void __launch_bounds__(64) k_bls_scale_g1(const uint32_t* __restrict_
 // two lanes of a pair share the scalar and take the branch together (the exchanges inside stay defined); across the wave the
 // body runs once per bit when any pair has the bit set and not at all otherwise -- never more than the select form, which runs
 // it for every bit and keeps a second XYZZ point (96 registers) alive across it.
-__device__ __forceinline__ void bb_g2x_store(uint32_t* __restrict__ dst, const g2x& p, bool role)
-{
-    const int o = role ? 12 : 0;
-    bb_st(dst + o, p.x);
-    bb_st(dst + 24 + o, p.y);
-    bb_st(dst + 48 + o, p.zz);
-    bb_st(dst + 72 + o, p.zzz);
-}
-__device__ __forceinline__ void bb_g2x_load(g2x& p, const uint32_t* __restrict__ src, bool role)
-{
-    const int o = role ? 12 : 0;
-    bb_ld(p.x, src + o);
-    bb_ld(p.y, src + 24 + o);
-    bb_ld(p.zz, src + 48 + o);
-    bb_ld(p.zzz, src + 72 + o);
-}
-
 // (one wave per SIMD: at two the doubling with the branch's live values around it spilled 56 bytes per lane)
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1)))
 k_bls_scale_g2(const uint32_t* __restrict__ live, uint32_t n_live, const uint64_t* __restrict__ scalars,
@@ -200,8 +117,8 @@ k_bls_scale_g2(const uint32_t* __restrict__ live, uint32_t n_live, const uint64_
     const uint32_t g = live[i];
     const uint64_t r = scalars[g];
     fp qx, qy;
-    bb_ld(qx, sig_mont48 + (size_t)48 * g + (role ? 12 : 0));
-    bb_ld(qy, sig_mont48 + (size_t)48 * g + 24 + (role ? 12 : 0));
+    fp_words::ld(qx, sig_mont48 + (size_t)48 * g + (role ? 12 : 0));
+    fp_words::ld(qy, sig_mont48 + (size_t)48 * g + 24 + (role ? 12 : 0));
     g2x acc;
     g2x_set_inf(acc);
 #pragma unroll 1
@@ -209,7 +126,7 @@ k_bls_scale_g2(const uint32_t* __restrict__ live, uint32_t n_live, const uint64_
         acc = g2x_double(acc, role);
         if ((r >> bit) & 1) g2x_add_affine(acc, qx, qy, false, role);
     }
-    bb_g2x_store(scaled96 + (size_t)G2X_WORDS * i, acc, role);
+    g2x_st<fp_words>(scaled96 + (size_t)G2X_WORDS * i, acc, role);
 }
 
 // The chunk's signature pair: Q = T = the sum of its scaled signatures, P = -g1 (wire bytes, converted here).  A sum at
@@ -229,7 +146,7 @@ k_bls_chunk_sig(const uint32_t* __restrict__ scaled96, uint32_t n_live, uint32_t
 #pragma unroll 1
     for (uint32_t t = 0; t < cnt; ++t) {
         g2x p;
-        bb_g2x_load(p, scaled96 + (size_t)G2X_WORDS * (first + t), role);
+        g2x_ld<fp_words>(p, scaled96 + (size_t)G2X_WORDS * (first + t), role);
         g2x_add(acc, p, role);
     }
     const bool inf = g2x_is_inf(acc);
@@ -244,13 +161,13 @@ k_bls_chunk_sig(const uint32_t* __restrict__ scaled96, uint32_t n_live, uint32_t
     fp_load_be48(pc, neg_g1_be96 + (role ? 48 : 0));  // the leading bytes of -g1 carry no flag bits
     fp_to_mont(pm, pc);
     const uint32_t row_idx = j * (chunk + 1) + cnt;
-    uint32_t* row = ws + (size_t)BLS_PAIR_WORDS * row_idx;
-    bb_st(row + 12 * (0 + (int)role), x);
-    bb_st(row + 12 * (2 + (int)role), y);
-    bb_st(row + 12 * (BLS_WS_P + (int)role), pm);
-    bb_st(row + 12 * (BLS_WS_T + 0 + (int)role), x);
-    bb_st(row + 12 * (BLS_WS_T + 2 + (int)role), y);
-    bb_st(row + 12 * (BLS_WS_T + 4 + (int)role), one);
+    uint32_t* row = ws + (size_t)BLS_PAIR_WORDS * row_idx;  // (k_bls_prepare's six stores: see the comment there)
+    fp_words::st(row + 12 * (0 + (int)role), x);
+    fp_words::st(row + 12 * (2 + (int)role), y);
+    fp_words::st(row + 12 * (BLS_WS_P + (int)role), pm);
+    fp_words::st(row + 12 * (BLS_WS_T + 0 + (int)role), x);
+    fp_words::st(row + 12 * (BLS_WS_T + 2 + (int)role), y);
+    fp_words::st(row + 12 * (BLS_WS_T + 4 + (int)role), one);
     if (!role) pair_flag[row_idx] = inf ? BLS_PAIR_SKIP : BLS_PAIR_LIVE;
 }
 
@@ -268,9 +185,8 @@ __global__ void __launch_bounds__(64) k_bls_gt_product(const uint32_t* __restric
     for (uint32_t t = 0; t < BLS_BATCH_FAN; ++t) {
         const uint64_t idx = (uint64_t)o * BLS_BATCH_FAN + t;
         fp a;
-        fp_set_zero(a);
-        if (c.k == 0 && !c.role) fp_set_one(a);
-        if (valid && c.act && idx < n_in) bb_ld(a, in + (size_t)BLS_GT_WORDS * idx + 12 * (2 * c.k + (int)c.role));
+        f12_one_coeff(a, c);
+        if (valid && c.act && idx < n_in) fp_words::ld(a, in + (size_t)BLS_GT_WORDS * idx + 12 * (2 * c.k + (int)c.role));
         if (c.act) slot_st(lds, t == 0 ? 0 : 1, c.lane, a);
         if (t == 0) continue;
         fp r;
@@ -283,7 +199,7 @@ __global__ void __launch_bounds__(64) k_bls_gt_product(const uint32_t* __restric
     if (!valid || !c.act) return;
     fp r;
     slot_ld(r, lds, 0, c.lane);
-    bb_st(out + (size_t)BLS_GT_WORDS * o + 12 * (2 * c.k + (int)c.role), r);
+    fp_words::st(out + (size_t)BLS_GT_WORDS * o + 12 * (2 * c.k + (int)c.role), r);
 }
 
 // ---------------------------------------------------------------- launchers

@@ -3,7 +3,8 @@
 // The step is_valid_indexed_attestation ends with (pe:736, 976, 1456): FastAggregateVerify's e(pk_agg, H(m)) == e(g1, sig),
 // as the product e(pk_agg, H(m)) e(-g1, sig) == 1.
 //
-//   k_bls_prepare    a lane pair per (P, Q): wire bytes -> Montgomery form, both curve equations checked, T = Q
+//   k_bls_prepare    a lane pair per (P, Q): wire bytes -> Montgomery form, both curve equations checked, T = Q (the decode is
+//                    wire_points.h's, kept written out here; the workspace row: BLS_WS_* / BLS_PAIR_* of kernels.h)
 //   k_bls_miller     a 16-lane row per group (fp12.h: lane pair k = coefficient k): the optimal-ate Miller loop over
 //                    |z| = 0xd201000000010000, 63 doublings and 5 additions, ONE accumulator f per group: every pair of the
 //                    group contributes its lines to it, so a group pays the 63 Fp12 squarings once; conjugated at the end (z < 0)
@@ -20,8 +21,10 @@
 // In the Miller loop lane pair k of a row works the point steps of the group's pairs k, k + 6, ... (T in device memory between
 // steps, Q and P read where needed), then all six lane pairs multiply f by each line in turn.
 #include "fp12.h"
+#include "fp_mem.h"
 #include "fp_sqrt.h"
 #include "kernels.h"
+#include "wire_points.h"
 
 namespace posevo {
 
@@ -29,29 +32,7 @@ namespace posevo {
 
 enum { BLS_OP_MUL = 0, BLS_OP_SQR, BLS_OP_ADD, BLS_OP_SUB, BLS_OP_NEG, BLS_OP_MULFP, BLS_OP_LD };
 enum { BLS_FE_MUL = 0, BLS_FE_CSQR, BLS_FE_CONJ, BLS_FE_FROB, BLS_FE_INVSCALE };
-enum { BLS_PAIR_LIVE = 0, BLS_PAIR_SKIP = 1, BLS_PAIR_BAD = 2 };
-// a pair's row of the workspace, in fp values: Q.x (c0, c1), Q.y (c0, c1), P.x, P.y, then T = (X, Y, Z), two components each
-constexpr int BLS_WS_P = 4, BLS_WS_T = 6;
-static_assert(BLS_PAIR_WORDS == 12 * 12, "workspace row");
 static_assert(BLS_SLOT_L2 == BLS_SLOT_L0 + 1 && BLS_SLOT_L3 == BLS_SLOT_L0 + 2, "the line's slots are consecutive");
-
-__device__ __forceinline__ void fp_ld_global(fp& r, const uint32_t* __restrict__ p)
-{
-#pragma unroll
-    for (int j = 0; j < 12; ++j) r.l[j] = p[j];
-}
-__device__ __forceinline__ void fp_st_global(uint32_t* __restrict__ p, const fp& a)
-{
-#pragma unroll
-    for (int j = 0; j < 12; ++j) p[j] = a.l[j];
-}
-__device__ __forceinline__ void fp_set_small_mont(fp& r, uint32_t v)
-{
-    fp t;
-    fp_set_zero(t);
-    t.l[0] = v;
-    fp_to_mont(r, t);
-}
 
 // ---------------------------------------------------------------- prepare
 __global__ void __launch_bounds__(256) k_bls_prepare(const uint8_t* __restrict__ g1_be96, const uint8_t* __restrict__ g2_be192,
@@ -61,6 +42,7 @@ __global__ void __launch_bounds__(256) k_bls_prepare(const uint8_t* __restrict__
     const uint64_t pair = gid >> 1;
     if (pair >= n_pairs) return;  // n_pairs counts whole lane pairs: both lanes leave together
     const bool role = (gid & 1) != 0;
+    // (wire_load_g1 / wire_load_g2 of wire_points.h, open-coded around ONE Montgomery 4: through them 155 -> 154 or 156 VGPRs)
     const uint8_t* a = g1_be96 + 96 * pair;
     const uint8_t* b = g2_be192 + 192 * pair;
     const bool p_inf = (a[0] & 0x40) != 0, q_inf = (b[0] & 0x40) != 0;
@@ -103,12 +85,13 @@ __global__ void __launch_bounds__(256) k_bls_prepare(const uint8_t* __restrict__
     uint32_t* row = ws + (uint64_t)BLS_PAIR_WORDS * pair;
     fp one;
     f2_set_one(one, role);
-    fp_st_global(row + 12 * (0 + (int)role), qx);
-    fp_st_global(row + 12 * (2 + (int)role), qy);
-    fp_st_global(row + 12 * (BLS_WS_P + (int)role), role ? py : px);
-    fp_st_global(row + 12 * (BLS_WS_T + 0 + (int)role), qx);
-    fp_st_global(row + 12 * (BLS_WS_T + 2 + (int)role), qy);
-    fp_st_global(row + 12 * (BLS_WS_T + 4 + (int)role), one);
+    // (the same six stores as k_bls_chunk_sig's: as one shared function they changed the registers of both kernels)
+    fp_words::st(row + 12 * (0 + (int)role), qx);
+    fp_words::st(row + 12 * (2 + (int)role), qy);
+    fp_words::st(row + 12 * (BLS_WS_P + (int)role), role ? py : px);
+    fp_words::st(row + 12 * (BLS_WS_T + 0 + (int)role), qx);
+    fp_words::st(row + 12 * (BLS_WS_T + 2 + (int)role), qy);
+    fp_words::st(row + 12 * (BLS_WS_T + 4 + (int)role), one);
     if (!role) pair_flag[pair] = bad ? BLS_PAIR_BAD : (p_inf || q_inf) ? BLS_PAIR_SKIP : BLS_PAIR_LIVE;
 }
 
@@ -129,7 +112,7 @@ __device__ __forceinline__ void bls_miller_step(const bls_lane& c, const uint32_
             fp t;
 #pragma unroll
             for (int s = 0; s < 3; ++s) {
-                fp_ld_global(t, row + 12 * (BLS_WS_T + 2 * s + (int)c.role));
+                fp_words::ld(t, row + 12 * (BLS_WS_T + 2 * s + (int)c.role));
                 slot_st(c.lds, s, c.lane, t);
             }
         }
@@ -139,7 +122,7 @@ __device__ __forceinline__ void bls_miller_step(const bls_lane& c, const uint32_
             const int op = (int)(w & 255), d = (int)(w >> 8 & 255), sa = (int)(w >> 16 & 255), sb = (int)(w >> 24);
             fp x, y, r;
             if (op == BLS_OP_LD) {
-                fp_ld_global(r, row + 12 * (sa < 2 ? 2 * sa + (int)c.role : BLS_WS_P + sa - 2));
+                fp_words::ld(r, row + 12 * (sa < 2 ? 2 * sa + (int)c.role : BLS_WS_P + sa - 2));
             } else {
                 slot_ld(x, c.lds, sa, c.lane);
                 slot_ld(y, c.lds, op == BLS_OP_SQR || op == BLS_OP_NEG ? sa : sb, c.lane);
@@ -159,7 +142,7 @@ __device__ __forceinline__ void bls_miller_step(const bls_lane& c, const uint32_
 #pragma unroll
             for (int s = 0; s < 3; ++s) {
                 slot_ld(t, c.lds, s, c.lane);
-                fp_st_global(row + 12 * (BLS_WS_T + 2 * s + (int)c.role), t);
+                fp_words::st(row + 12 * (BLS_WS_T + 2 * s + (int)c.role), t);
             }
         } else if (c.act) {  // no pair, infinity on a side or a bad point: the line is 1
             fp one, zero;
@@ -198,8 +181,7 @@ __global__ void __launch_bounds__(64) k_bls_miller(uint32_t* __restrict__ ws, co
     max_n = (uint32_t)__builtin_amdgcn_readfirstlane((int)max_n);
     {
         fp one;
-        fp_set_zero(one);
-        if (c.k == 0 && !c.role) fp_set_one(one);
+        f12_one_coeff(one, c);
         if (c.act) slot_st(lds, BLS_SLOT_F, c.lane, one);
     }
     // a bad point anywhere in the group (lane pair k looks at pairs k, k + 6, ...)
@@ -220,7 +202,7 @@ __global__ void __launch_bounds__(64) k_bls_miller(uint32_t* __restrict__ ws, co
     f12_conj(r, c, BLS_SLOT_F);
     for (int m = 1; m < 16; m <<= 1) bad |= __shfl_xor(bad, m, 64);
     if (gvalid && c.act) {
-        fp_st_global(gt + (uint64_t)BLS_GT_WORDS * g + 12 * (2 * c.k + (int)c.role), r);
+        fp_words::st(gt + (uint64_t)BLS_GT_WORDS * g + 12 * (2 * c.k + (int)c.role), r);
         if ((c.lane & 15) == 0) group_bad[g] = bad;
     }
 }
@@ -236,9 +218,8 @@ __global__ void __launch_bounds__(64) k_bls_final_exp(const uint32_t* __restrict
     const bool gvalid = g < n_groups;
     {
         fp a;
-        fp_set_zero(a);
-        if (c.k == 0 && !c.role) fp_set_one(a);  // rows past the last group work on 1
-        if (gvalid && c.act) fp_ld_global(a, gt + (uint64_t)BLS_GT_WORDS * g + 12 * (2 * c.k + (int)c.role));
+        f12_one_coeff(a, c);  // rows past the last group work on 1
+        if (gvalid && c.act) fp_words::ld(a, gt + (uint64_t)BLS_GT_WORDS * g + 12 * (2 * c.k + (int)c.role));
         if (c.act) slot_st(lds, 0, c.lane, a);
     }
     const int cj = BLS_CYCLO_J[c.k], part = BLS_CYCLO_PART[c.k];
@@ -262,8 +243,7 @@ __global__ void __launch_bounds__(64) k_bls_final_exp(const uint32_t* __restrict
     __syncthreads();
     fp r, want;
     slot_ld(r, lds, 0, c.lane);
-    fp_set_zero(want);
-    if (c.k == 0 && !c.role) fp_set_one(want);
+    f12_one_coeff(want, c);
     int is_one = !c.act || fp_eq(r, want);
     for (int m = 1; m < 16; m <<= 1) is_one &= __shfl_xor(is_one, m, 64);
     if (!gvalid || !c.act) return;

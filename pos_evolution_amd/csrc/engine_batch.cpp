@@ -39,8 +39,6 @@ int draw_scalars(pe_engine* h, std::vector<uint64_t>& out)
 
 namespace {
 
-size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
-
 int batch_run(pe_engine* h, const char* who, const uint8_t* pk96, const uint8_t* msg192, const uint8_t* sig192, uint32_t n,
               const uint64_t* scalars, int32_t* verdict)
 {
@@ -146,19 +144,11 @@ int batch_run(pe_engine* h, const char* who, const uint8_t* pk96, const uint8_t*
     const uint32_t k = (uint32_t)again.size();
     st[5] = k;
     if (k == 0) return PE_OK;
-    std::vector<uint8_t> g1((size_t)192 * k), g2((size_t)384 * k);
-    std::vector<uint32_t> pair_off((size_t)k + 1);
     std::vector<int32_t> one_by_one(k);
-    for (uint32_t t = 0; t < k; ++t) {
-        const size_t g = again[t];
-        memcpy(&g1[(size_t)192 * t], pk96 + 96 * g, 96);
-        memcpy(&g1[(size_t)192 * t + 96], NEG_G1_BE96, 96);
-        memcpy(&g2[(size_t)384 * t], msg192 + 192 * g, 192);
-        memcpy(&g2[(size_t)384 * t + 192], sig192 + 192 * g, 192);
-        pair_off[t] = 2 * t;
-    }
-    pair_off[k] = 2 * k;
-    PE_TRY(pairing_run(h, who, g1.data(), g2.data(), 2ull * k, pair_off.data(), k, one_by_one.data(), nullptr));
+    PE_TRY(verify_pairs_run(
+        h, who, k, [&](uint32_t t) { return pk96 + (size_t)96 * again[t]; },
+        [&](uint32_t t) { return msg192 + (size_t)192 * again[t]; }, [&](uint32_t t) { return sig192 + (size_t)192 * again[t]; },
+        one_by_one.data()));
     for (uint32_t t = 0; t < k; ++t) verdict[again[t]] = one_by_one[t];
     return PE_OK;
 }
@@ -172,9 +162,7 @@ int pe_batch_verify(pe_engine* h, const uint8_t* pubkeys96, const uint8_t* messa
 {
     if (!h || (n_groups && (!pubkeys96 || !message_points192 || !signatures192 || !verdict))) return PE_ERR_INVALID_ARG;
     PE_TRY(enter(h));  // open pipelines complete
-    if (h->dist_ready())
-        return fail(h, PE_ERR_STATE, "pe_batch_verify: the handle exchanges with other ranks (pe_dist_init); "
-                                     "the sharded handles are not supported");
+    if (h->dist_ready()) return refuse_dist(h, "pe_batch_verify");
     return batch_run(h, "pe_batch_verify", pubkeys96, message_points192, signatures192, n_groups, scalars, verdict);
 }
 
@@ -185,9 +173,7 @@ int pe_batch_fast_aggregate_verify(pe_engine* h, const uint32_t* index, const ui
     if (!h || !offsets || (n_groups && (!message_points192 || !signatures192 || !verdict))) return PE_ERR_INVALID_ARG;
     if (n_groups && offsets[n_groups] && !index) return PE_ERR_INVALID_ARG;
     PE_TRY(enter(h));
-    if (h->dist_ready())
-        return fail(h, PE_ERR_STATE, "pe_batch_fast_aggregate_verify: the handle exchanges with other ranks (pe_dist_init); "
-                                     "the sharded handles are not supported");
+    if (h->dist_ready()) return refuse_dist(h, "pe_batch_fast_aggregate_verify");
     if (n_groups == 0) return batch_run(h, "pe_batch_fast_aggregate_verify", nullptr, nullptr, nullptr, 0, scalars, verdict);
     if (!h->have_points) return fail(h, PE_ERR_STATE, "pe_batch_fast_aggregate_verify: no pubkeys loaded");
     // the aggregate pubkeys, summed on the device as pe_fast_aggregate_verify sums them; an empty group's is the identity

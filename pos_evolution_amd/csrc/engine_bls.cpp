@@ -21,14 +21,10 @@ extern const uint8_t NEG_G1_BE96[96] = {
     0x4e, 0x6f, 0x38, 0xba, 0x0e, 0xcb, 0x75, 0x1b, 0xad, 0x54, 0xdc, 0xd6, 0xb9, 0x39, 0xc2, 0xca
 };
 
-static size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
-
 int pairing_run(pe_engine* h, const char* who, const uint8_t* g1, const uint8_t* g2, uint64_t n_pairs, const uint32_t* offsets,
                 uint32_t n_groups, int32_t* verdict, uint8_t* out576)
 {
-    if (h->dist_ready())
-        return fail(h, PE_ERR_STATE, std::string(who) + ": the handle exchanges with other ranks (pe_dist_init); "
-                                                        "the sharded handles are not supported");
+    if (h->dist_ready()) return refuse_dist(h, who);
     if (n_groups == 0) return PE_OK;
     if (n_pairs >= 0xFFFFFFFFull) return fail(h, PE_ERR_CAPACITY, std::string(who) + ": too many pairs");
     for (uint32_t g = 0; g < n_groups; ++g)
@@ -63,6 +59,22 @@ int pairing_run(pe_engine* h, const char* who, const uint8_t* g1, const uint8_t*
     return PE_OK;
 }
 
+int verify_pairs_run(pe_engine* h, const char* who, uint32_t n, const WireAt& pk_at, const WireAt& msg_at, const WireAt& sig_at,
+                     int32_t* verdict)
+{
+    std::vector<uint8_t> g1((size_t)192 * n), g2((size_t)384 * n);
+    std::vector<uint32_t> pair_off((size_t)n + 1);
+    for (uint32_t t = 0; t < n; ++t) {
+        memcpy(&g1[(size_t)192 * t], pk_at(t), 96);
+        memcpy(&g1[(size_t)192 * t + 96], NEG_G1_BE96, 96);
+        memcpy(&g2[(size_t)384 * t], msg_at(t), 192);
+        memcpy(&g2[(size_t)384 * t + 192], sig_at(t), 192);
+        pair_off[t] = 2 * t;
+    }
+    pair_off[n] = 2 * n;
+    return pairing_run(h, who, g1.data(), g2.data(), 2ull * n, pair_off.data(), n, verdict, nullptr);
+}
+
 }  // namespace posevo
 
 extern "C" {
@@ -89,25 +101,16 @@ int pe_fast_aggregate_verify(pe_engine* h, const uint32_t* index, const uint32_t
     if (!h || !offsets || (n_groups && (!message_points192 || !signatures192 || !verdict))) return PE_ERR_INVALID_ARG;
     if (n_groups && offsets[n_groups] && !index) return PE_ERR_INVALID_ARG;
     PE_TRY(enter(h));
-    if (h->dist_ready())
-        return fail(h, PE_ERR_STATE, "pe_fast_aggregate_verify: the handle exchanges with other ranks (pe_dist_init); "
-                                     "the sharded handles are not supported");
+    if (h->dist_ready()) return refuse_dist(h, "pe_fast_aggregate_verify");
     if (n_groups == 0) return PE_OK;
     if (!h->have_points) return fail(h, PE_ERR_STATE, "pe_fast_aggregate_verify: no pubkeys loaded");
     // the aggregate pubkeys, summed on the device; the pairs (sum, H(m)), (-g1, signature) of every group
-    std::vector<uint8_t> g1((size_t)192 * n_groups), g2((size_t)384 * n_groups), sums((size_t)96 * n_groups);
-    std::vector<uint32_t> pair_off((size_t)n_groups + 1);
+    std::vector<uint8_t> sums((size_t)96 * n_groups);
     PE_TRY(pe_g1_sum(h, nullptr, 0, index, offsets, n_groups, sums.data()));
-    for (uint32_t g = 0; g < n_groups; ++g) {
-        memcpy(&g1[(size_t)192 * g], &sums[(size_t)96 * g], 96);
-        memcpy(&g1[(size_t)192 * g + 96], NEG_G1_BE96, 96);
-        memcpy(&g2[(size_t)384 * g], message_points192 + (size_t)192 * g, 192);
-        memcpy(&g2[(size_t)384 * g + 192], signatures192 + (size_t)192 * g, 192);
-        pair_off[g] = 2 * g;
-    }
-    pair_off[n_groups] = 2 * n_groups;
-    PE_TRY(pairing_run(h, "pe_fast_aggregate_verify", g1.data(), g2.data(), 2ull * n_groups, pair_off.data(), n_groups, verdict,
-                       nullptr));
+    PE_TRY(verify_pairs_run(
+        h, "pe_fast_aggregate_verify", n_groups, [&](uint32_t g) { return &sums[(size_t)96 * g]; },
+        [&](uint32_t g) { return message_points192 + (size_t)192 * g; }, [&](uint32_t g) { return signatures192 + (size_t)192 * g; },
+        verdict));
     // FastAggregateVerify refuses n = 0, and an identity signature never verifies (the product is 1 there only with an identity
     // aggregate key, which KeyValidate refuses); a bad point keeps its verdict 2
     for (uint32_t g = 0; g < n_groups; ++g)

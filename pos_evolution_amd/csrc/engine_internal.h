@@ -573,6 +573,18 @@ extern const uint8_t NEG_G1_BE96[96];
 int draw_scalars(pe_engine* h, std::vector<uint64_t>& out);  // non-zero 64-bit values from getrandom (engine_batch.cpp)
 int pairing_run(pe_engine* h, const char* who, const uint8_t* g1, const uint8_t* g2, uint64_t n_pairs, const uint32_t* offsets,
                 uint32_t n_groups, int32_t* verdict, uint8_t* out576);
+// n groups of two pairs, (pk_t, H(m_t)) and (-g1, sig_t), through pairing_run: verdict[t] = e(pk_t, H(m_t)) == e(g1, sig_t), or
+// PE_BLS_BAD_POINT.  pk_at(t): 96 wire bytes; msg_at(t), sig_at(t): 192 each.  What the caller makes of a verdict is its own.
+using WireAt = std::function<const uint8_t*(uint32_t)>;
+int verify_pairs_run(pe_engine* h, const char* who, uint32_t n, const WireAt& pk_at, const WireAt& msg_at, const WireAt& sig_at,
+                     int32_t* verdict);
+inline size_t up256(size_t v) { return (v + 255) & ~size_t(255); }  // sub-buffers of one allocation start 256-byte aligned
+// the calls that serve one GPU only
+inline int refuse_dist(pe_engine* h, const char* who)
+{
+    return fail(h, PE_ERR_STATE, std::string(who) + ": the handle exchanges with other ranks (pe_dist_init); "
+                                                    "the sharded handles are not supported");
+}
 // keep_held: the call does not touch what the held-back fork-choice launches read or write and enqueues nothing that must
 // follow them (host-side scalars; the calls that hold or pair themselves): everything else issues them first
 int need_init(pe_engine* h, bool flush = true, bool keep_held = false);

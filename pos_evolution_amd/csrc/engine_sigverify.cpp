@@ -14,12 +14,6 @@
 
 using namespace posevo;
 
-namespace {
-
-size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
-
-}  // namespace
-
 extern "C" {
 
 int pe_verify_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t n, const uint32_t* index, const uint32_t* signer,
@@ -32,9 +26,7 @@ int pe_verify_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t n, 
     if (total && (!signer || !member_verdict)) return PE_ERR_INVALID_ARG;
     PE_TRY(enter(h));  // open pipelines complete
     const char* who = "pe_verify_signatures";
-    if (h->dist_ready())
-        return fail(h, PE_ERR_STATE, "pe_verify_signatures: the handle exchanges with other ranks (pe_dist_init); "
-                                     "the sharded handles are not supported");
+    if (h->dist_ready()) return refuse_dist(h, who);
     if (!h->have_points) return fail(h, PE_ERR_STATE, "pe_verify_signatures: no pubkeys loaded");
     if (n >= 0xFFFFFFFFull / 48) return fail(h, PE_ERR_CAPACITY, "pe_verify_signatures: too many signatures");
     for (uint32_t g = 0; g < n_groups; ++g)
@@ -121,18 +113,11 @@ int pe_verify_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t n, 
     HIP_TRY(h, hipStreamSynchronize(s));
 
     // ---- decide: the pairs (sum r pk, H(m_g)), (-g1, sum r sig), one group of two per committee
-    std::vector<uint8_t> p1((size_t)192 * n_groups), p2((size_t)384 * n_groups);
-    std::vector<uint32_t> pair_off((size_t)n_groups + 1);
     std::vector<int32_t> combined(n_groups);
-    for (uint32_t g = 0; g < n_groups; ++g) {
-        memcpy(&p1[(size_t)192 * g], &h->verify_sums_pk[(size_t)96 * g], 96);
-        memcpy(&p1[(size_t)192 * g + 96], NEG_G1_BE96, 96);
-        memcpy(&p2[(size_t)384 * g], message_points192 + (size_t)192 * g, 192);
-        memcpy(&p2[(size_t)384 * g + 192], &h->verify_sums_sig[(size_t)192 * g], 192);
-        pair_off[g] = 2 * g;
-    }
-    pair_off[n_groups] = 2 * n_groups;
-    PE_TRY(pairing_run(h, who, p1.data(), p2.data(), 2ull * n_groups, pair_off.data(), n_groups, combined.data(), nullptr));
+    const WireAt msg_of = [&](uint32_t g) { return message_points192 + (size_t)192 * g; };
+    PE_TRY(verify_pairs_run(
+        h, who, n_groups, [&](uint32_t g) { return &h->verify_sums_pk[(size_t)96 * g]; }, msg_of,
+        [&](uint32_t g) { return &h->verify_sums_sig[(size_t)192 * g]; }, combined.data()));
     stats[3] = 1;
     std::vector<uint32_t> again;  // the members the locate pass decides
     std::vector<int32_t> gverdict(n_groups);
@@ -179,19 +164,10 @@ int pe_verify_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t n, 
         HIP_TRY(h, hipMemcpyAsync(pk.data(), d + o_be96, 96ull * n_again, hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipMemcpyAsync(sg.data(), d + o_be192, 192ull * n_again, hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipStreamSynchronize(s));
-        p1.assign((size_t)192 * n_again, 0);
-        p2.assign((size_t)384 * n_again, 0);
-        pair_off.assign((size_t)n_again + 1, 0);
         std::vector<int32_t> one_by_one(n_again);
-        for (uint32_t t = 0; t < n_again; ++t) {
-            memcpy(&p1[(size_t)192 * t], &pk[(size_t)96 * t], 96);
-            memcpy(&p1[(size_t)192 * t + 96], NEG_G1_BE96, 96);
-            memcpy(&p2[(size_t)384 * t], message_points192 + (size_t)192 * group_of[t], 192);
-            memcpy(&p2[(size_t)384 * t + 192], &sg[(size_t)192 * t], 192);
-            pair_off[t] = 2 * t;
-        }
-        pair_off[n_again] = 2 * n_again;
-        PE_TRY(pairing_run(h, who, p1.data(), p2.data(), 2ull * n_again, pair_off.data(), n_again, one_by_one.data(), nullptr));
+        PE_TRY(verify_pairs_run(
+            h, who, n_again, [&](uint32_t t) { return &pk[(size_t)96 * t]; }, [&](uint32_t t) { return msg_of(group_of[t]); },
+            [&](uint32_t t) { return &sg[(size_t)192 * t]; }, one_by_one.data()));
         stats[3] = 2;
         for (uint32_t t = 0; t < n_again; ++t) mverdict[again[t]] = one_by_one[t] == PE_BLS_VALID;
     }

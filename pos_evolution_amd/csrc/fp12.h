@@ -52,6 +52,12 @@ __device__ __forceinline__ void slot_st(uint32_t* lds, int s, int lane, const fp
 }
 // this lane's component of coefficient i of the Fp12 value in slot s
 __device__ __forceinline__ void f12_coeff(fp& r, const bls_lane& c, int s, int i) { slot_ld(r, c.lds, s, c.row + 2 * i + (int)c.role); }
+// this lane's component of the Fp12 one: the Montgomery one in the c0 lane of lane pair 0, zero everywhere else
+__device__ __forceinline__ void f12_one_coeff(fp& r, const bls_lane& c)
+{
+    fp_set_zero(r);
+    if (c.k == 0 && !c.role) fp_set_one(r);
+}
 
 // r = xi * a = (a0 - a1) + (a0 + a1) u
 __device__ __forceinline__ void f2_mul_xi(fp& r, const fp& a, bool role)

@@ -6,7 +6,8 @@
 //
 //   k_g2_convert     192-B big-endian affine (x.c1 | x.c0 | y.c1 | y.c0) -> Montgomery limbs [x0 x1 y0 y1]
 //   k_g2_accumulate  per-pair XYZZ accumulation of k gathered points (mixed adds, 18 products per lane each), then a
-//                    compacting pairwise tree over the workgroup's 128 partials staged in LDS
+//                    compacting pairwise tree over the workgroup's 128 partials staged in LDS (point_sum_tree.h: the group
+//                    search and the tree, shared with the weighted sums of sigverify_kernels.hip; fp_mem.h: the movers)
 //   k_g2_finish      per group: add the workgroup partials, normalise to canonical affine, store big-endian
 //
 // Bound: integer VALU, 36 Montgomery products per gathered 192-byte point.
@@ -22,6 +23,7 @@
 #include "g2.h"
 #include "fp_sqrt.h"
 #include "kernels.h"
+#include "point_sum_tree.h"
 
 namespace posevo {
 
@@ -224,70 +226,6 @@ void launch_g2_decompress_batch(hipStream_t s, G2DecompressBatch& b)
 // ---------------------------------------------------------------- accumulate
 constexpr int G2_WG = 256;  // lanes; G2_WG_SLOTS (kernels.h) = 128 point slots
 
-__device__ __forceinline__ void ld12(fp& v, const uint32_t* __restrict__ src)
-{
-    const uint4* s = reinterpret_cast<const uint4*>(src);
-    const uint4 a = s[0], b = s[1], c = s[2];
-    v.l[0] = a.x; v.l[1] = a.y; v.l[2] = a.z; v.l[3] = a.w;
-    v.l[4] = b.x; v.l[5] = b.y; v.l[6] = b.z; v.l[7] = b.w;
-    v.l[8] = c.x; v.l[9] = c.y; v.l[10] = c.z; v.l[11] = c.w;
-}
-__device__ __forceinline__ void st12(uint32_t* __restrict__ dst, const fp& v)
-{
-    uint4* d = reinterpret_cast<uint4*>(dst);
-    d[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-    d[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-    d[2] = make_uint4(v.l[8], v.l[9], v.l[10], v.l[11]);
-}
-// XYZZ partial in global memory: [x0 x1 y0 y1 zz0 zz1 zzz0 zzz1] x 12 words; a lane moves its own halves
-__device__ __forceinline__ void g2_global_store(uint32_t* __restrict__ dst, const g2x& p, bool role)
-{
-    const int o = role ? 12 : 0;
-    st12(dst + o, p.x);
-    st12(dst + 24 + o, p.y);
-    st12(dst + 48 + o, p.zz);
-    st12(dst + 72 + o, p.zzz);
-}
-__device__ __forceinline__ void g2_global_load(g2x& p, const uint32_t* __restrict__ src, bool role)
-{
-    const int o = role ? 12 : 0;
-    ld12(p.x, src + o);
-    ld12(p.y, src + 24 + o);
-    ld12(p.zz, src + 48 + o);
-    ld12(p.zzz, src + 72 + o);
-}
-// LDS staging, limb-major over lane positions: word k of position L at lds[k * G2_WG + L]; slot s = positions 2s, 2s+1
-__device__ __forceinline__ void g2_lds_store(uint32_t* lds, int pos, const g2x& p)
-{
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {
-        lds[k * G2_WG + pos] = p.x.l[k];
-        lds[(12 + k) * G2_WG + pos] = p.y.l[k];
-        lds[(24 + k) * G2_WG + pos] = p.zz.l[k];
-        lds[(36 + k) * G2_WG + pos] = p.zzz.l[k];
-    }
-}
-__device__ __forceinline__ void g2_lds_load(g2x& p, const uint32_t* lds, int pos)
-{
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {
-        p.x.l[k] = lds[k * G2_WG + pos];
-        p.y.l[k] = lds[(12 + k) * G2_WG + pos];
-        p.zz.l[k] = lds[(24 + k) * G2_WG + pos];
-        p.zzz.l[k] = lds[(36 + k) * G2_WG + pos];
-    }
-}
-
-__device__ __forceinline__ uint32_t g2_find_group(const G1Group* __restrict__ groups, uint32_t n_groups, uint32_t slot)
-{
-    uint32_t lo = 0, hi = n_groups;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (groups[mid].slot_base <= slot) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(G2_WG) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_g2_accumulate(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ members,
                 const G1Group* __restrict__ groups, uint32_t n_groups, uint32_t n_slots,
@@ -306,8 +244,9 @@ k_g2_accumulate(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ m
     g2x_set_inf(acc);
     uint32_t my_out = NONE32, my_size = 0;
 
+    // (slot_task_of's arithmetic, open-coded: through the helper this kernel's scratch grew from 28 to 32 bytes)
     if (slot < n_slots) {
-        const uint32_t g = g2_find_group(groups, n_groups, slot);
+        const uint32_t g = plan_find_group(groups, n_groups, slot);
         const G1Group d = groups[g];
         const uint32_t t = slot - d.slot_base;
         const bool wide = d.log2_block > 8;
@@ -326,8 +265,8 @@ k_g2_accumulate(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ m
                 const uint32_t i = first + j;
                 const uint32_t idx = members ? members[d.member_start + i] : d.member_start + i;
                 const uint32_t* p = pts + 48ull * idx + (role ? 12 : 0);
-                ld12(ox, p);
-                ld12(oy, p + 24);
+                fp_vec16::ld(ox, p);
+                fp_vec16::ld(oy, p + 24);
             };
             if (count > 0) fetch(0, qx, qy);
             for (uint32_t j = 0; j < count; ++j) {
@@ -338,51 +277,7 @@ k_g2_accumulate(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ m
             }
         }
     }
-    // ---- workgroup tree over the 128 slot partials: level with n pairs, slot w < n adds slots 2w and 2w+1 ----
-    if (my_size == 1) {
-        g2_global_store(wg_partials + (size_t)G2X_WORDS * my_out, acc, role);
-        my_size = 0;
-    }
-    g2_lds_store(lds, tid, acc);
-    if (!role) {
-        lds_out[ws] = my_out;
-        lds_sz[ws] = my_size;
-    }
-    __syncthreads();
-    for (int n = G2_WG_SLOTS / 2; n >= 1; n >>= 1) {
-        const bool active = ws < n;
-        g2x p1;
-        uint32_t out = NONE32, sz = 0;
-        bool store_lds = false;
-        if (active) {
-            sz = lds_sz[2 * ws];
-            out = lds_out[2 * ws];
-            if (sz >= 2) {
-                g2x p2;
-                g2_lds_load(p1, lds, 4 * ws + (role ? 1 : 0));
-                g2_lds_load(p2, lds, 4 * ws + 2 + (role ? 1 : 0));
-                g2x_add(p1, p2, role);
-                sz >>= 1;
-                if (sz == 1) {
-                    g2_global_store(wg_partials + (size_t)G2X_WORDS * out, p1, role);
-                    sz = 0;
-                } else {
-                    store_lds = true;
-                }
-            } else {
-                sz = 0;
-            }
-        }
-        __syncthreads();
-        if (active) {
-            if (store_lds) g2_lds_store(lds, tid, p1);
-            if (!role) {
-                lds_out[ws] = out;
-                lds_sz[ws] = sz;
-            }
-        }
-        __syncthreads();
-    }
+    point_sum_tree<sum_g2, G2_WG>(lds, lds_out, lds_sz, acc, my_out, my_size, wg_partials);
 }
 
 void launch_g2_accumulate(hipStream_t s, const uint32_t* points_mont48, const uint32_t* members,
@@ -410,7 +305,7 @@ k_g2_finish(const uint32_t* __restrict__ partials, const G1Group* __restrict__ g
     g2x_set_inf(acc);
     for (uint32_t k = 0; k < n_parts; ++k) {
         g2x q;
-        g2_global_load(q, partials + (size_t)G2X_WORDS * (d.out_base + k), role);
+        g2x_ld<fp_vec16>(q, partials + (size_t)G2X_WORDS * (d.out_base + k), role);
         g2x_add(acc, q, role);
     }
     // wire order: x.c1 | x.c0 | y.c1 | y.c0 -- role 1 (c1) writes the leading 48 bytes of each coordinate
@@ -485,8 +380,8 @@ k_g2_subgroup_check(const uint32_t* __restrict__ pts, uint64_t n, int32_t* __res
     if (status[i] != 0) return;  // both lanes of the pair read the same word
     fp px, py;
     const uint32_t* p = pts + 48ull * i + (role ? 12 : 0);
-    ld12(px, p);
-    ld12(py, p + 24);
+    fp_vec16::ld(px, p);
+    fp_vec16::ld(py, p + 24);
     if (pair_and(fp_is_zero(px) && fp_is_zero(py))) return;  // infinity: in every subgroup
     // Q = [|z|] P, left to right over |z| = 0xd201000000010000 (bit 63 is the leading one)
     const uint32_t Z_HI = 0xd2010000u, Z_LO = 0x00010000u;
@@ -571,8 +466,8 @@ __device__ __forceinline__ void g2_aggregate_rows_body(const uint32_t lane, cons
         if (status[row] != 0) { ++bad; continue; }
         fp qx, qy;
         const uint32_t* p = pts + 48ull * row + (role ? 12 : 0);
-        ld12(qx, p);
-        ld12(qy, p + 24);
+        fp_vec16::ld(qx, p);
+        fp_vec16::ld(qy, p + 24);
         const bool q_inf = pair_and(fp_is_zero(qx) && fp_is_zero(qy));
         g2x_add_affine(acc, qx, qy, q_inf, role);
     }

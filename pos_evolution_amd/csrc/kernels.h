@@ -622,6 +622,11 @@ void launch_ssz_validator_roots(hipStream_t s, const SszValidatorArgs& a);
 constexpr uint32_t BLS_GROUPS_PER_WAVE = 4;   // = groups per workgroup
 constexpr int BLS_PAIR_WORDS = 144;           // a pair's workspace row: Q.x, Q.y (Fp2), P.x, P.y (Fp), T = X, Y, Z (Fp2), Montgomery
 constexpr int BLS_GT_WORDS = 144;             // a group's Fp12 value between the two kernels: c_k component c at 12 (2 k + c)
+// the row in fp values (12 words each): Q.x (c0, c1), Q.y (c0, c1), P.x, P.y, then T = (X, Y, Z), two components each
+constexpr int BLS_WS_P = 4, BLS_WS_T = 6;
+static_assert(BLS_PAIR_WORDS == 12 * (BLS_WS_T + 6), "workspace row");
+// pair_flag: the pair contributes | contributes 1 (infinity on a side) | holds a point off its curve
+enum { BLS_PAIR_LIVE = 0, BLS_PAIR_SKIP = 1, BLS_PAIR_BAD = 2 };
 // wire bytes (96-byte G1, 192-byte G2) -> workspace rows; pair_flag: 0 contributes, 1 infinity on a side, 2 off its curve
 void launch_bls_prepare(hipStream_t s, const uint8_t* g1_be96, const uint8_t* g2_be192, uint64_t n_pairs, uint32_t* ws,
                         int32_t* pair_flag);

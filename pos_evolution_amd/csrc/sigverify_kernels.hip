@@ -6,6 +6,7 @@
 //                             128 slots per workgroup, the compacting LDS tree, k_g2_finish behind it)
 //   k_g1_weighted_accumulate  sum_j r_j pk_j per group over registry rows: a lane per stripe, 256 slots per workgroup, the same
 //                             tree over single lanes, k_g1_finish behind it
+//                             (the slot's task and the tree: point_sum_tree.h, one source for these two and k_g2_accumulate)
 //   k_sv_mark_identity        a decoded signature at infinity gets its own status (it is no signature)
 //   k_sv_rows_g1 / _g2        listed Montgomery rows back to wire bytes: the pairs of the locate pass
 //
@@ -19,6 +20,7 @@
 // The point forms are the complete ones of g1.h / g2.h: acc = 2 acc followed by + P meets acc = +-P on structured keys.
 #include "g2.h"
 #include "kernels.h"
+#include "point_sum_tree.h"
 
 namespace posevo {
 
@@ -27,95 +29,10 @@ namespace {
 constexpr int SV_WG = 256;
 constexpr int SV_PLANES = 64;
 
-__device__ __forceinline__ void sv_ld12(fp& v, const uint32_t* __restrict__ src)
-{
-    const uint4* s = reinterpret_cast<const uint4*>(src);
-    const uint4 a = s[0], b = s[1], c = s[2];
-    v.l[0] = a.x; v.l[1] = a.y; v.l[2] = a.z; v.l[3] = a.w;
-    v.l[4] = b.x; v.l[5] = b.y; v.l[6] = b.z; v.l[7] = b.w;
-    v.l[8] = c.x; v.l[9] = c.y; v.l[10] = c.z; v.l[11] = c.w;
-}
-__device__ __forceinline__ void sv_st12(uint32_t* __restrict__ dst, const fp& v)
-{
-    uint4* d = reinterpret_cast<uint4*>(dst);
-    d[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-    d[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-    d[2] = make_uint4(v.l[8], v.l[9], v.l[10], v.l[11]);
-}
-// LDS staging of the tree, limb-major over lane positions: word w of position L at lds[w * SV_WG + L]
-__device__ __forceinline__ void sv_lds_store(uint32_t* lds, int pos, const fp& x, const fp& y, const fp& zz, const fp& zzz)
-{
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {
-        lds[k * SV_WG + pos] = x.l[k];
-        lds[(12 + k) * SV_WG + pos] = y.l[k];
-        lds[(24 + k) * SV_WG + pos] = zz.l[k];
-        lds[(36 + k) * SV_WG + pos] = zzz.l[k];
-    }
-}
-__device__ __forceinline__ void sv_lds_load(fp& x, fp& y, fp& zz, fp& zzz, const uint32_t* lds, int pos)
-{
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {
-        x.l[k] = lds[k * SV_WG + pos];
-        y.l[k] = lds[(12 + k) * SV_WG + pos];
-        zz.l[k] = lds[(24 + k) * SV_WG + pos];
-        zzz.l[k] = lds[(36 + k) * SV_WG + pos];
-    }
-}
-__device__ __forceinline__ void sv_g2_global_store(uint32_t* __restrict__ dst, const g2x& p, bool role)
-{
-    const int o = role ? 12 : 0;
-    sv_st12(dst + o, p.x);
-    sv_st12(dst + 24 + o, p.y);
-    sv_st12(dst + 48 + o, p.zz);
-    sv_st12(dst + 72 + o, p.zzz);
-}
-__device__ __forceinline__ void sv_g1_global_store(uint32_t* __restrict__ dst, const g1x& p)
-{
-    sv_st12(dst, p.x);
-    sv_st12(dst + 12, p.y);
-    sv_st12(dst + 24, p.zz);
-    sv_st12(dst + 36, p.zzz);
-}
-__device__ __forceinline__ uint32_t sv_find_group(const G1Group* __restrict__ groups, uint32_t n_groups, uint32_t slot)
-{
-    uint32_t lo = 0, hi = n_groups;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (groups[mid].slot_base <= slot) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// What a slot is to do: its stripe [first, first + count) of the group's members (count 0: a padding slot) and where its
-// block's partial goes (the plan of plan_g1, read exactly as k_g2_accumulate reads it).
-struct sv_task {
-    uint32_t member0, count, out, size;
-};
-__device__ __forceinline__ sv_task sv_task_of(const G1Group* __restrict__ groups, uint32_t n_groups, uint32_t n_slots, uint32_t slot,
-                                              uint32_t wg_slots)
-{
-    sv_task t = {0, 0, NONE32, 0};
-    if (slot >= n_slots) return t;
-    const G1Group d = groups[sv_find_group(groups, n_groups, slot)];
-    const uint32_t s = slot - d.slot_base;
-    const bool wide = d.log2_block > 8;
-    const uint32_t block_slots = d.n_tasks == 0 ? 0u : wide ? ((d.n_tasks + wg_slots - 1) / wg_slots) * wg_slots : (1u << d.log2_block);
-    if (s < block_slots) {
-        t.size = wide ? wg_slots : (1u << d.log2_block);
-        t.out = d.out_base + (wide ? s / wg_slots : 0u);
-    }
-    if (s < d.n_tasks) {
-        t.member0 = d.member_start + s * d.k;
-        t.count = min(d.k, d.n_members - s * d.k);
-    }
-    return t;
-}
 // The stripe's scalars, transposed: bit j of masks[b * n_slots_wg + ws] = bit b of the scalar of the stripe's member j.
 // `planes` = [lo, hi): the planes this lane writes (the two lanes of a G2 pair take half each).
 __device__ __forceinline__ void sv_plane_masks(uint16_t* masks, int wg_slots, int ws, const uint64_t* __restrict__ scalars,
-                                               const sv_task& t, int lo, int hi)
+                                               const slot_task& t, int lo, int hi)
 {
     for (int b = lo; b < hi; ++b) masks[b * wg_slots + ws] = 0;
     for (uint32_t j = 0; j < t.count; ++j) {
@@ -142,7 +59,7 @@ k_g2_weighted_accumulate(const uint32_t* __restrict__ pts, const uint32_t* __res
     const int tid = threadIdx.x;
     const bool role = tid & 1;
     const int ws = tid >> 1;
-    const sv_task t = sv_task_of(groups, n_groups, n_slots, blockIdx.x * G2_WG_SLOTS + ws, G2_WG_SLOTS);
+    const slot_task t = slot_task_of(groups, n_groups, n_slots, blockIdx.x * G2_WG_SLOTS + ws, G2_WG_SLOTS);
     sv_plane_masks(masks, G2_WG_SLOTS, ws, scalars, t, role ? 32 : 0, role ? 64 : 32);
     __syncthreads();
 
@@ -159,60 +76,15 @@ k_g2_weighted_accumulate(const uint32_t* __restrict__ pts, const uint32_t* __res
             const uint32_t row = index ? index[member] : member;
             const uint32_t* p = pts + 48ull * row + (role ? 12 : 0);
             fp qx, qy;
-            sv_ld12(qx, p);
-            sv_ld12(qy, p + 24);
+            fp_vec16::ld(qx, p);
+            fp_vec16::ld(qy, p + 24);
             const bool q_inf = pair_and(fp_is_zero(qx) && fp_is_zero(qy));
             g2x_add_affine(acc, qx, qy, q_inf, role);
         }
     }
     __syncthreads();  // the masks are done with: the same LDS now stages the tree
 
-    // ---- workgroup tree over the 128 slot partials (k_g2_accumulate's): level with n pairs, slot w < n adds slots 2w and 2w+1
-    uint32_t my_out = t.out, my_size = t.size;
-    if (my_size == 1) {
-        sv_g2_global_store(wg_partials + (size_t)G2X_WORDS * my_out, acc, role);
-        my_size = 0;
-    }
-    sv_lds_store(lds, tid, acc.x, acc.y, acc.zz, acc.zzz);
-    if (!role) {
-        lds_out[ws] = my_out;
-        lds_sz[ws] = my_size;
-    }
-    __syncthreads();
-    for (int n = G2_WG_SLOTS / 2; n >= 1; n >>= 1) {
-        const bool active = ws < n;
-        g2x p1;
-        uint32_t out = NONE32, sz = 0;
-        bool store_lds = false;
-        if (active) {
-            sz = lds_sz[2 * ws];
-            out = lds_out[2 * ws];
-            if (sz >= 2) {
-                g2x p2;
-                sv_lds_load(p1.x, p1.y, p1.zz, p1.zzz, lds, 4 * ws + (role ? 1 : 0));
-                sv_lds_load(p2.x, p2.y, p2.zz, p2.zzz, lds, 4 * ws + 2 + (role ? 1 : 0));
-                g2x_add(p1, p2, role);
-                sz >>= 1;
-                if (sz == 1) {
-                    sv_g2_global_store(wg_partials + (size_t)G2X_WORDS * out, p1, role);
-                    sz = 0;
-                } else {
-                    store_lds = true;
-                }
-            } else {
-                sz = 0;
-            }
-        }
-        __syncthreads();
-        if (active) {
-            if (store_lds) sv_lds_store(lds, tid, p1.x, p1.y, p1.zz, p1.zzz);
-            if (!role) {
-                lds_out[ws] = out;
-                lds_sz[ws] = sz;
-            }
-        }
-        __syncthreads();
-    }
+    point_sum_tree<sum_g2, SV_WG>(lds, lds_out, lds_sz, acc, t.out, t.size, wg_partials);
 }
 
 // ---------------------------------------------------------------- sum_j r_j pk_j
@@ -228,7 +100,7 @@ k_g1_weighted_accumulate(const uint32_t* __restrict__ pts, const uint32_t* __res
     uint16_t* masks = reinterpret_cast<uint16_t*>(lds);
 
     const int ws = threadIdx.x;
-    const sv_task t = sv_task_of(groups, n_groups, n_slots, blockIdx.x * SV_WG + ws, SV_WG);
+    const slot_task t = slot_task_of(groups, n_groups, n_slots, blockIdx.x * SV_WG + ws, SV_WG);
     sv_plane_masks(masks, SV_WG, ws, scalars, t, 0, SV_PLANES);
     __syncthreads();
 
@@ -244,54 +116,14 @@ k_g1_weighted_accumulate(const uint32_t* __restrict__ pts, const uint32_t* __res
             m &= m - 1;
             const uint32_t* p = pts + (uint64_t)G1_ROW_WORDS * signer[member];
             fp qx, qy;
-            sv_ld12(qx, p);
-            sv_ld12(qy, p + 12);
+            fp_vec16::ld(qx, p);
+            fp_vec16::ld(qy, p + 12);
             g1x_add_affine(acc, qx, qy, fp_is_zero(qx) && fp_is_zero(qy));
         }
     }
     __syncthreads();
 
-    uint32_t my_out = t.out, my_size = t.size;
-    if (my_size == 1) {
-        sv_g1_global_store(wg_partials + (size_t)G1X_WORDS * my_out, acc);
-        my_size = 0;
-    }
-    sv_lds_store(lds, ws, acc.x, acc.y, acc.zz, acc.zzz);
-    lds_out[ws] = my_out;
-    lds_sz[ws] = my_size;
-    __syncthreads();
-    for (int n = SV_WG / 2; n >= 1; n >>= 1) {
-        const bool active = ws < n;
-        g1x p1;
-        uint32_t out = NONE32, sz = 0;
-        bool store_lds = false;
-        if (active) {
-            sz = lds_sz[2 * ws];
-            out = lds_out[2 * ws];
-            if (sz >= 2) {
-                g1x p2;
-                sv_lds_load(p1.x, p1.y, p1.zz, p1.zzz, lds, 2 * ws);
-                sv_lds_load(p2.x, p2.y, p2.zz, p2.zzz, lds, 2 * ws + 1);
-                g1x_add(p1, p2);
-                sz >>= 1;
-                if (sz == 1) {
-                    sv_g1_global_store(wg_partials + (size_t)G1X_WORDS * out, p1);
-                    sz = 0;
-                } else {
-                    store_lds = true;
-                }
-            } else {
-                sz = 0;
-            }
-        }
-        __syncthreads();
-        if (active) {
-            if (store_lds) sv_lds_store(lds, ws, p1.x, p1.y, p1.zz, p1.zzz);
-            lds_out[ws] = out;
-            lds_sz[ws] = sz;
-        }
-        __syncthreads();
-    }
+    point_sum_tree<sum_g1, SV_WG>(lds, lds_out, lds_sz, acc, t.out, t.size, wg_partials);
 }
 
 // ---------------------------------------------------------------- the identity, and rows back to wire bytes
@@ -319,8 +151,8 @@ k_sv_rows_g1(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ rows
     if (t >= n) return;
     const uint32_t* p = pts + (uint64_t)G1_ROW_WORDS * rows[t];
     fp x, y, px, py;
-    sv_ld12(x, p);
-    sv_ld12(y, p + 12);
+    fp_vec16::ld(x, p);
+    fp_vec16::ld(y, p + 12);
     const bool inf = fp_is_zero(x) && fp_is_zero(y);
     fp_from_mont(px, x);
     fp_from_mont(py, y);
@@ -340,7 +172,7 @@ k_sv_rows_g2(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ rows
     uint32_t any = 0;
     for (int j = 0; j < 48; ++j) any |= p[j];
     fp v, pv;
-    sv_ld12(v, p + 12 * e);
+    fp_vec16::ld(v, p + 12 * e);
     fp_from_mont(pv, v);
     uint8_t* o = out_be192 + 192ull * t;
     fp_store_be48(o + 48 * ((e & 2) | ((e & 1) ^ 1)), pv);
