@@ -926,6 +926,36 @@ int pe_verify_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t n, 
                          const uint32_t* offsets, uint32_t n_groups, const uint8_t* message_points192, const uint64_t* scalars,
                          int32_t* member_verdict, int32_t* sig_status, int32_t* group_verdict, uint8_t* out_signatures96);
 
+/* The RESIDENT aggregate decided where it lies: every group of the handle's last pe_aggregate_signed over rows in device memory
+ * (with out_aggpk96 requested) gets the verdict of e(aggregate key, H(m)) e(-G1, aggregate signature) == 1, computed from the
+ * key and the signature that aggregate left in device memory -- no wait for out_aggpk96 / out_signatures96, no second
+ * decompression, no upload of points the device already holds.
+ *   message_points192   n_points message points H(m), 192-byte G2 wire form; host memory, or device memory (read in place when
+ *                       16-byte aligned, copied otherwise).  hash_to_curve is the caller's.
+ *   point_of_row        host memory, one entry per INPUT row of that aggregate: the group a row went into takes the point of
+ *                       its first row (pe_attestation order of appearance).  NULL: group g takes message_points192[g].
+ *   flags               PE_VERIFY_APPLY: on the device, sig_valid of every group decided by rows 2-4 below becomes
+ *                       sig_valid AND (verdict == 1) -- pe_on_attestation_batch / pe_process_attestation_batch with
+ *                       PE_ROWS_RESIDENT then answer PE_ATT_BAD_SIGNATURE for the groups that did not verify.  Idempotent.
+ *   verdict             cap entries in group order; entries past the groups formed read 0.
+ * verdict[g], first matching row:
+ *   1. the group has no committee (its row status says why)                                  PE_BLS_UNDECIDED, sig_valid untouched
+ *   2. its message point is not canonical or not on its curve                                PE_BLS_BAD_POINT
+ *   3. its members overlap | a member's signature did not decode or failed the leg's subgroup check | its union is empty
+ *      (identity aggregate key) | identity aggregate signature | identity message point | aggregate signature outside G2
+ *                                                                                            PE_BLS_INVALID
+ *   4. the pairing product is 1: PE_BLS_VALID, otherwise PE_BLS_INVALID
+ * The G2 test of row 3 is the call's own pass over the aggregate signatures; it is skipped when the aggregate ran with
+ * PE_SIG_CHECK_SUBGROUP (sums of members of G2 lie in G2).
+ * Synchronous: completes open pipelines first.  PE_ERR_STATE unless the handle's last aggregate is such a pe_aggregate_signed,
+ * the store's clock and committee tables are what it resolved against (the rule of PE_ROWS_RESIDENT), and no pe_dist_init* is
+ * active; PE_ERR_INVALID_ARG for a point_of_row entry >= n_points, or n_points below the group count without point_of_row;
+ * PE_ERR_CAPACITY for cap below the group count.  An error writes nothing and applies nothing. */
+#define PE_BLS_UNDECIDED 3
+#define PE_VERIFY_APPLY  0x1u
+int pe_verify_resident(pe_engine* h, const uint8_t* message_points192, uint32_t n_points, const uint32_t* point_of_row,
+                       uint32_t flags, uint32_t cap, int32_t* verdict);
+
 /* ---- multi-GPU exchange (validator-range shards) ----------- */
 /* Each rank owns a contiguous validator range and the whole (small) block table.
  * get_head splits at the one exchange point:

@@ -94,6 +94,15 @@ int pe_profile_verify_stats(const pe_engine* h, uint32_t out[5]);
  * over the members the settle pass left.  n_groups must be the last call's. */
 int pe_profile_verify_sums(const pe_engine* h, uint32_t n_groups, uint8_t* out_pk96, uint8_t* out_sig192);
 
+/* pe_verify_resident.  What the handle's last call did: out[r] for r < 9 = groups decided by row r of the rule table, in its
+ * precedence order: [0] no committee (PE_BLS_UNDECIDED), [1] message point not canonical or off its curve, [2] overlapping
+ * members, [3] a member's signature did not decode or failed its subgroup check, [4] empty union (identity aggregate key),
+ * [5] identity aggregate signature, [6] identity message point, [7] aggregate signature outside G2, [8] the pairing value;
+ * out[9] = 1 when the call ran its own subgroup pass over the aggregate signatures (0: the leg ran with PE_SIG_CHECK_SUBGROUP),
+ * out[10] = groups.  A call that failed leaves the previous call's numbers. */
+#define PE_VERIFY_RESIDENT_STATS 11
+int pe_profile_verify_resident_stats(const pe_engine* h, uint32_t out[PE_VERIFY_RESIDENT_STATS]);
+
 #ifdef __cplusplus
 }
 #endif

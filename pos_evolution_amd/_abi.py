@@ -22,6 +22,9 @@ PE_ERR_TIMEOUT = -15
 PE_DIST_SINGLE_COMM = 1
 PE_SIG_G2_COMPRESSED, PE_SIG_G2_UNCOMPRESSED, PE_SIG_CHECK_SUBGROUP = 1, 2, 0x100
 PE_SIG_STATUS_IDENTITY = 4  # pe_verify_signatures: the signature is the point at infinity
+PE_BLS_INVALID, PE_BLS_VALID, PE_BLS_BAD_POINT, PE_BLS_UNDECIDED = 0, 1, 2, 3
+PE_VERIFY_APPLY = 0x1  # pe_verify_resident: AND the verdict into the group's sig_valid on the device
+PE_VERIFY_RESIDENT_STATS = 11
 NONE32 = 0xFFFFFFFF
 
 PE_VAL_ACTIVE, PE_VAL_SLASHED, PE_VAL_EQUIVOCATING, PE_VAL_ACTIVE_PREV = 0x01, 0x02, 0x04, 0x08
@@ -184,6 +187,7 @@ SIGNATURES = {
     "pe_batch_fast_aggregate_verify": (C.c_int, [_H, _u32p, _u32p, C.c_uint32, _u8p, _u8p, _u64p, _i32p]),
     "pe_verify_signatures": (C.c_int, [_H, C.c_void_p, C.c_uint64, _u32p, _u32p, _u32p, C.c_uint32, _u8p, _u64p, _i32p, _i32p, _i32p,
                                        _u8p]),
+    "pe_verify_resident": (C.c_int, [_H, C.c_void_p, C.c_uint32, _u32p, C.c_uint32, C.c_uint32, _i32p]),
     "pe_pipeline_set_lag": (C.c_int, [_H, C.c_uint32]),
     "pe_pipeline_get_lag": (C.c_uint32, [_H]),
     "pe_pipeline_generation": (C.c_uint64, [_H]),
@@ -291,6 +295,7 @@ SIGNATURES = {
     "pe_profile_verify_set_stripe": (C.c_int, [_H, C.c_uint32]),
     "pe_profile_verify_stats": (C.c_int, [_H, _u32p]),
     "pe_profile_verify_sums": (C.c_int, [_H, C.c_uint32, _u8p, _u8p]),
+    "pe_profile_verify_resident_stats": (C.c_int, [_H, _u32p]),
 }
 
 PE_ROWS_RESIDENT = 1  # include/posevo.h: "every group of the last pe_aggregate over rows in device memory"

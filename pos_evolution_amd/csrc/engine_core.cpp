@@ -534,6 +534,7 @@ void pe_engine_destroy(pe_engine* h)
         a.d_sig_in.release();
         a.d_sig_pts.release();
         a.d_sig_status.release();
+        a.d_res_points.release();
         a.d_stage.release();
         a.d_outblk.release();
         a.h_stage.release();
@@ -674,7 +675,7 @@ int pe_pipeline_set_lag(pe_engine* h, uint32_t depth)
     {
         using A = pe_engine::PipeArena;
         DevBuf A::*dev[] = {&A::d_stage, &A::d_outblk, &A::d_res_bits, &A::d_res_info, &A::d_partials, &A::d_lane_partials,
-                            &A::d_sig_in, &A::d_sig_pts, &A::d_sig_status};
+                            &A::d_sig_in, &A::d_sig_pts, &A::d_sig_status, &A::d_res_points};
         for (auto m : dev) {
             size_t cap = 0;
             for (auto& o : h->arena) cap = std::max(cap, (o.*m).cap);

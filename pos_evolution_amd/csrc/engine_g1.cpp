@@ -261,6 +261,8 @@ int sig_batch_flush(pe_engine* h)
         r.out96[r.count] = sg.o_sig;
         r.out_bad[r.count] = sg.o_bad;
         r.n_groups[r.count] = sg.ng_bound;
+        r.keep_mont48[r.count] = sg.keep_mont48;
+        r.keep_bad[r.count] = sg.keep_bad;
         ++r.count;
     }
     {
@@ -714,16 +716,21 @@ int pe_aggregate_signed(pe_engine* h, const pe_attestation* atts, uint32_t n, co
     if ((fmt != PE_SIG_G2_COMPRESSED && fmt != PE_SIG_G2_UNCOMPRESSED) || (sig_format_flags & ~(0xFFu | PE_SIG_CHECK_SUBGROUP)))
         return fail(h, PE_ERR_INVALID_ARG, "pe_aggregate_signed: unknown signature format / flags");
     (void)hipSetDevice(h->device);
+    h->rv.valid = false;  // whatever this call forms is the handle's last aggregate from here on
     if (n == 0) return pe_aggregate(h, atts, n, bits_arena, arena_len, nullptr, out_atts, out_n_groups, group_of,
                                     out_bits_arena, out_arena_cap, nullptr, out_aggpk96, out_count);
     const bool dev_rows = rows_on_device(atts);
     const size_t sig_bytes = fmt == PE_SIG_G2_COMPRESSED ? 96 : 192;
+    // Device rows with aggregate keys on one GPU: the groups' keys and aggregate signatures also stay in device memory, in the
+    // arena's d_res_points, where pe_verify_resident decides them (engine_resident_verify.cpp)
+    const bool keep_points = dev_rows && out_aggpk96 != nullptr && !h->dist_ready();
     HostLap lap(&h->trace);
     {   // the arena's signature scratch, sized while nothing of this call is in flight
         if (!h->pipelining) PE_TRY(flush_pending(h));
         PE_TRY(ensure_quiesced_arenas(h, &pe_engine::PipeArena::d_sig_in, sig_bytes * n));
         PE_TRY(ensure_quiesced_arenas(h, &pe_engine::PipeArena::d_sig_pts, 192ull * n));
         PE_TRY(ensure_quiesced_arenas(h, &pe_engine::PipeArena::d_sig_status, 4ull * n));
+        if (keep_points) PE_TRY(ensure_quiesced_arenas(h, &pe_engine::PipeArena::d_res_points, res_points_layout(nullptr, n).bytes));
         // That scratch is ONE set per arena, not a cursor-allocated region: an earlier signed aggregate of THIS pipeline decodes
         // from / into the very words this call is about to fill.  Its leg goes out now if it is still collected (a streaming
         // pipeline), and everything of this call that touches the scratch -- the host signatures' copy below, this call's own
@@ -747,8 +754,11 @@ int pe_aggregate_signed(pe_engine* h, const pe_attestation* atts, uint32_t n, co
         group_of = gof_p->data();
     }
     lap.mark("sagg.1_prepare");
+    const ResPoints keep = keep_points ? res_points_layout(h->A().d_res_points.p, n) : ResPoints{nullptr, nullptr, nullptr, 0};
+    h->keep_pk = keep.pk_xyzz48;
     const int rc = pe_aggregate(h, atts, n, bits_arena, arena_len, nullptr, out_atts, out_n_groups, group_of, out_bits_arena,
                                 out_arena_cap, nullptr, out_aggpk96, out_count);
+    h->keep_pk = nullptr;
     if (rc) return rc;
     lap.mark("sagg.2_aggregate");
     pe_engine::PipeArena& A = h->A();
@@ -814,6 +824,8 @@ int pe_aggregate_signed(pe_engine* h, const pe_attestation* atts, uint32_t n, co
     seg.o_sig = ob.host<uint8_t>(off_sig);
     seg.o_bad = ob.host<uint32_t>(off_bad);
     seg.o_st = ob.host<int32_t>(off_st);
+    seg.keep_mont48 = keep.sig_mont48;
+    seg.keep_bad = keep.sig_bad;
     const bool collect = seg.compressed && h->streaming && h->pipelining && h->stream == h->own_stream && h->aux_stream != nullptr;
     seg.streaming = collect && h->last_agg_on_side && h->side_stream != nullptr;
     h->sig_batch.push_back(seg);
@@ -821,6 +833,14 @@ int pe_aggregate_signed(pe_engine* h, const pe_attestation* atts, uint32_t n, co
     if (!collect || h->sig_batch.size() >= (size_t)std::min<int>(std::max(h->tune.sig_batch, 1), (int)G2_BATCH_MAX)) {
         PE_TRY(sig_batch_flush(h));
         lap.mark("sagg.4_leg_flush");
+    }
+    if (keep_points) {
+        h->rv.valid = true;
+        h->rv.rr_generation = h->rr.generation;
+        h->rv.res_generation = h->res_generation;
+        h->rv.arena = h->cur;
+        h->rv.n_in = n;
+        h->rv.checked_subgroup = seg.check_subgroup;
     }
     const size_t base = ob.base;
     const int ai = h->cur;

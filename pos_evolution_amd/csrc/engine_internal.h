@@ -7,6 +7,7 @@
 //                      back), get_head
 //   engine_attest.cpp  on_attestation / process_attestation / aggregation over host rows
 //   engine_resident.cpp the same path over rows resident in device memory (grouping + validation on the device)
+//   engine_resident_verify.cpp the pairing check over the groups of a resident signed aggregate, from the points it left on the device
 //   engine_g1.cpp      G1 / G2 sums over caller-chosen groups, BLSPubkey / BLSSignature wire formats
 //   engine_dist.cpp    multi-GPU exchange: RCCL owned by the engine, function-table collectives
 //   engine_slash.cpp   slashing detection: the per-validator vote history and its scan (double and surround votes)
@@ -259,6 +260,18 @@ struct pe_engine {
     DevBuf d_ssz_level[2];         // the nodes between two passes of k_ssz_merkle, word form
     DevBuf d_ssz_chunks;           // pe_ssz_merkleize: the caller's chunks
     DevBuf d_bls;                  // pe_pairing_check: inputs | workspace rows | flags | Fp12 values | verdicts of one call (engine_bls.cpp)
+    // ---- pe_verify_resident (engine_resident_verify.cpp) ----
+    // which aggregate the arena's d_res_points belong to: valid while that is still the handle's last aggregate of either kind
+    struct ResidentVerify {
+        bool valid = false;
+        uint64_t rr_generation = 0, res_generation = 0;
+        int arena = 0;
+        uint32_t n_in = 0;             // input rows of that aggregate: the layout of d_res_points
+        bool checked_subgroup = false;  // its leg ran with PE_SIG_CHECK_SUBGROUP: sums of members of G2 lie in G2
+    } rv;
+    uint32_t* keep_pk = nullptr;       // pe_aggregate_signed, around its pe_aggregate: where k_g1_finish also leaves the XYZZ sums
+    std::vector<uint8_t> verify_head;  // pe_verify_resident: -g1 | point_of_row as uploaded (outlives the copy whatever the call returns)
+    uint32_t verify_resident_stats[PE_VERIFY_RESIDENT_STATS] = {};  // pe_profile_verify_resident_stats, of the last call
     // ---- pe_batch_verify (engine_batch.cpp) ----
     DevBuf d_batch;                // one call's inputs, Montgomery rows, scaled points, chunk rows, chunk values and product levels
     uint32_t batch_chunk = 2;      // c: live groups per chunk (pe_profile_batch_set_chunk)
@@ -302,6 +315,9 @@ struct pe_engine {
         // rows resident on the device (engine_resident.cpp): grouping table (self-cleaning) and the per-call scratch
         DevBuf d_rr_tab, d_rr;
         DevBuf d_sig_in, d_sig_pts, d_sig_status;  // pe_aggregate_signed: wire bytes | Montgomery points | decode status
+        // pe_aggregate_signed over device rows with aggregate keys: per group the key (XYZZ), the aggregate signature (affine
+        // Montgomery row) and the members left out of it, kept for pe_verify_resident (res_points_layout)
+        DevBuf d_res_points;
         uint32_t rr_rows_cap = 0, rr_comm_cap = 0, rr_tab_size = 0;
         // a second set of the same for the EXCHANGED aggregate of a committee-sharded step (pe_aggregate_exchange): the
         // local aggregate's descriptors and unions are still being read by its G1 chain when the gathered one is ingested
@@ -373,6 +389,7 @@ struct pe_engine {
         uint32_t* d_pts; int32_t* d_status;
         const UnionGroup* d_ug; const uint32_t* d_member_row; uint32_t ng_bound; const AttPlan* plan_dev;
         uint8_t* o_sig; uint32_t* o_bad; int32_t* o_st;
+        uint32_t* keep_mont48; uint32_t* keep_bad;  // nullable: the sums and counts kept on the device (PipeArena::d_res_points)
     };
     std::vector<SigSeg> sig_batch;
     hipEvent_t ev_sig = nullptr;        // a batch's decompression is done (on the accumulations' stream) -> its sums may start
@@ -441,6 +458,7 @@ struct pe_engine {
         TablesDev tables{};             // the candidate committee tables the groups were resolved against
         uint64_t generation = 0;
         int set = 0;                    // 0: the arena's own scratch, 1: the exchanged aggregate's (x_*)
+        uint32_t n_groups = 0;          // groups formed: known once that aggregate has completed
     } rr;
 
     // ---- accumulate-shape autotune (large pubkey aggregations) ----
@@ -579,6 +597,15 @@ using WireAt = std::function<const uint8_t*(uint32_t)>;
 int verify_pairs_run(pe_engine* h, const char* who, uint32_t n, const WireAt& pk_at, const WireAt& msg_at, const WireAt& sig_at,
                      int32_t* verdict);
 inline size_t up256(size_t v) { return (v + 255) & ~size_t(255); }  // sub-buffers of one allocation start 256-byte aligned
+// PipeArena::d_res_points for an aggregate over n input rows (n bounds its groups)
+struct ResPoints { uint32_t *pk_xyzz48, *sig_mont48, *sig_bad; size_t bytes; };
+inline ResPoints res_points_layout(void* base, uint32_t n)
+{
+    uint8_t* b = static_cast<uint8_t*>(base);
+    const size_t rows = std::max<uint32_t>(n, 1), o_sig = up256(192 * rows), o_bad = o_sig + up256(192 * rows);
+    return ResPoints{reinterpret_cast<uint32_t*>(b), reinterpret_cast<uint32_t*>(b + o_sig), reinterpret_cast<uint32_t*>(b + o_bad),
+                     o_bad + up256(4 * rows)};
+}
 // the calls that serve one GPU only
 inline int refuse_dist(pe_engine* h, const char* who)
 {
@@ -969,7 +996,7 @@ int aggregate_resident(pe_engine* h, const pe_attestation* d_rows, uint32_t n, c
                        uint8_t* out_bits_arena, uint64_t out_arena_cap, uint8_t* out_aggpk96, uint32_t* out_count,
                        uint32_t* dev_partials = nullptr, int set = 0, const uint32_t* n_dev = nullptr);
 // the pieces pe_aggregate_exchange packs: the resident aggregate's groups, unions and the caller's rows
-struct ResidentParts { const void* rows; const AttGroup* grp; const AttPlan* plan; const uint32_t* res_bits; const uint32_t* res_info; uint32_t n_in; };
+struct ResidentParts { const void* rows; AttGroup* grp; const AttPlan* plan; const uint32_t* res_bits; const uint32_t* res_info; uint32_t n_in; };
 int resident_parts(pe_engine* h, ResidentParts* out);
 // PE_ROWS_RESIDENT: PE_ERR_STATE unless a resident aggregate over device rows is valid and the store's clock and committee
 // tables are the ones it resolved against

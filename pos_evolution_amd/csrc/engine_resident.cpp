@@ -368,7 +368,9 @@ int aggregate_resident(pe_engine* h, const pe_attestation* d_rows, uint32_t n, c
         bound.n_partials = n;
         const G1Group* d_groups = L.g1;
         const AttPlan* d_plan = L.plan;
-        auto launch_g1 = [h, arena, d_points, tables, d_union, d_groups, bound, out_pk, on_side, d_plan, dev_partials, cm, by_cmpl]() -> int {
+        // pe_aggregate_signed keeps the sums for pe_verify_resident: k_g1_finish's XYZZ output, beside the wire bytes
+        uint32_t* dev_jac = dev_partials ? dev_partials : set == 0 ? h->keep_pk : nullptr;
+        auto launch_g1 = [h, arena, d_points, tables, d_union, d_groups, bound, out_pk, on_side, d_plan, dev_jac, cm, by_cmpl]() -> int {
             hipStream_t gs = on_side ? h->side_stream : h->stream;
             if (on_side) {  // behind everything enqueued on the engine's stream so far (see aggregate_impl)
                 HIP_TRY(h, hipEventRecord(h->ev_fork, h->stream));
@@ -379,7 +381,7 @@ int aggregate_resident(pe_engine* h, const pe_attestation* d_rows, uint32_t n, c
             } else {
                 g1_stream_guard(h, gs);
             }
-            PE_TRY(launch_g1_planned(h, d_points, tables.t[0].members, d_union, d_groups, bound, out_pk, dev_partials, gs,
+            PE_TRY(launch_g1_planned(h, d_points, tables.t[0].members, d_union, d_groups, bound, out_pk, dev_jac, gs,
                                      on_side ? h->fin_stream : gs, on_side ? &arena->d_partials : nullptr,
                                      on_side ? &arena->d_lane_partials : nullptr, d_plan, tables.t[1].members, 0,
                                      by_cmpl ? &cm : nullptr));
@@ -408,16 +410,19 @@ int aggregate_resident(pe_engine* h, const pe_attestation* d_rows, uint32_t n, c
     h->rr.rows = d_rows;
     h->rr.tables = tables;
     ++h->rr.generation;
+    h->rr.n_groups = NONE32;  // until the completion below has run
     const size_t base = ob.base;
     const int ai = h->cur;
+    const uint64_t gen = h->rr.generation;
     auto complete = [h, ai, base, off_plan, off_rows, off_gof, off_obits, off_oinfo, off_opk, off_ocm, by_cmpl, n, out_atts,
-                     out_n_groups, group_of, out_bits_arena, out_aggpk96, out_count]() -> int {
+                     out_n_groups, group_of, out_bits_arena, out_aggpk96, out_count, gen]() -> int {
         const uint8_t* pin = h->arena[ai].h_pin.as<uint8_t>() + base;
         const AttPlan P = *reinterpret_cast<const AttPlan*>(pin + off_plan);
         if (P.error) return plan_error_to_status(h, P.error == 0xFFFFFFFFu ? 1u : P.error, "pe_aggregate (rows in device memory)");
         const uint32_t ng = P.n_groups;
         if (ng > n) return fail(h, PE_ERR_NO_DEVICE, "k_att_plan returned more groups than rows");
         *out_n_groups = ng;
+        if (h->rr.generation == gen) h->rr.n_groups = ng;  // still the handle's last aggregate over device rows
         memcpy(out_atts, pin + off_rows, sizeof(pe_attestation) * (size_t)ng);
         if (group_of) memcpy(group_of, pin + off_gof, 4ull * n);
         const uint32_t* obits = reinterpret_cast<const uint32_t*>(pin + off_obits);

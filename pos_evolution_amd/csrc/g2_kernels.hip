@@ -451,7 +451,8 @@ __device__ __forceinline__ void g2_aggregate_rows_body(const uint32_t lane, cons
                                                        const int32_t* __restrict__ status, const UnionGroup* __restrict__ ug,
                                                        const uint32_t* __restrict__ member_row, uint32_t n_groups,
                                                        const AttPlan* __restrict__ plan_dev, uint8_t* __restrict__ out96,
-                                                       uint32_t* __restrict__ out_bad)
+                                                       uint32_t* __restrict__ out_bad, uint32_t* __restrict__ keep_mont48,
+                                                       uint32_t* __restrict__ keep_bad)
 {
     if (plan_dev) n_groups = min(n_groups, plan_dev->n_groups);
     const uint32_t g = lane >> 1;
@@ -472,6 +473,9 @@ __device__ __forceinline__ void g2_aggregate_rows_body(const uint32_t lane, cons
         g2x_add_affine(acc, qx, qy, q_inf, role);
     }
     if (!role) out_bad[g] = bad;
+    if (keep_bad && !role) keep_bad[g] = bad;
+    // (keep_mont48: the sum once more, for pe_verify_resident -- this lane's halves of the affine row, the zero row at infinity)
+    uint32_t* kp = keep_mont48 ? keep_mont48 + 48ull * g + (role ? 12 : 0) : nullptr;
     uint8_t* o = out96 + 96ull * g;
     uint8_t* ox = o + (role ? 0 : 48);  // wire order: x.c1 | x.c0 -- role 1 (c1) writes the leading 48 bytes
     if (g2x_is_inf(acc)) {
@@ -479,10 +483,21 @@ __device__ __forceinline__ void g2_aggregate_rows_body(const uint32_t lane, cons
 #pragma unroll
         for (int j = 0; j < 12; ++j) wx[j] = 0;
         if (role) o[0] = 0xC0;
+        if (kp) {
+            fp_vec16::st(kp, acc.zz);  // zero
+            fp_vec16::st(kp + 24, acc.zz);
+        }
         return;
     }
     fp x, y;
     g2x_to_affine_plain(x, y, acc, role);  // plain residues: this lane's component of x and of y
+    if (kp) {
+        fp m;
+        fp_to_mont(m, x);
+        fp_vec16::st(kp, m);
+        fp_to_mont(m, y);
+        fp_vec16::st(kp + 24, m);
+    }
     // y > -y on (c1, c0): c1 decides unless it is zero
     const bool mine_larger = limbs_gt(y, FP_HALF);
     const bool mine_zero = fp_is_zero(y);
@@ -503,7 +518,7 @@ k_g2_aggregate_rows(const G2AggregateRowsBatch b)
     uint32_t k = 0;
     while (k + 1 < b.count && blockIdx.x >= b.first_block[k + 1]) ++k;
     g2_aggregate_rows_body((blockIdx.x - b.first_block[k]) * 64 + threadIdx.x, b.pts[k], b.status[k], b.ug[k], b.member_row[k],
-                           b.n_groups[k], b.plan_dev[k], b.out96[k], b.out_bad[k]);
+                           b.n_groups[k], b.plan_dev[k], b.out96[k], b.out_bad[k], b.keep_mont48[k], b.keep_bad[k]);
 }
 
 void launch_g2_aggregate_rows(hipStream_t s, G2AggregateRowsBatch& b)

@@ -463,6 +463,9 @@ struct G2AggregateRowsBatch {
     const uint32_t* pts[G2_BATCH_MAX]; const int32_t* status[G2_BATCH_MAX]; const UnionGroup* ug[G2_BATCH_MAX];
     const uint32_t* member_row[G2_BATCH_MAX]; const AttPlan* plan_dev[G2_BATCH_MAX]; uint8_t* out96[G2_BATCH_MAX];
     uint32_t* out_bad[G2_BATCH_MAX]; uint32_t n_groups[G2_BATCH_MAX]; uint32_t first_block[G2_BATCH_MAX + 1]; uint32_t count;
+    // nullable, device memory (pe_verify_resident reads them where they lie): the group's sum as an affine Montgomery row
+    // [x0 x1 y0 y1] of 48 words (the rows launch_g2_subgroup_check reads; infinity = the zero row) and a second copy of out_bad
+    uint32_t* keep_mont48[G2_BATCH_MAX]; uint32_t* keep_bad[G2_BATCH_MAX];
 };
 void launch_g2_aggregate_rows(hipStream_t s, G2AggregateRowsBatch& b);
 // the per-signature statuses of up to G2_BATCH_MAX legs into their pinned output blocks, one launch (a copy command per leg cost
@@ -637,6 +640,37 @@ void launch_bls_miller(hipStream_t s, uint32_t* ws, const int32_t* pair_flag, co
 // verdict[g] = group_bad[g] ? 2 : gt[g]^((p^12 - 1) / r * 3) == 1; out576 (nullable): that power, 12 x 48 bytes big-endian
 void launch_bls_final_exp(hipStream_t s, const uint32_t* gt, const int32_t* group_bad, uint32_t n_groups, int32_t* verdict,
                           uint8_t* out576);
+
+// ---- the resident aggregate's verdicts (bls_resident_kernels.hip; host side: engine_resident_verify.cpp) ----
+// Group g of the last pe_aggregate_signed over device rows is the two pairs 2g = (aggregate key, H(m)), 2g + 1 = (-g1, aggregate
+// signature), built from what that aggregate left in device memory.
+struct BlsResidentArgs {
+    const uint32_t* pk_xyzz48;     // per group: the aggregate key as k_g1_finish's XYZZ words (ZZ = 0: the identity)
+    const uint32_t* sig_mont48;    // per group: the aggregate signature, G2AggregateRowsBatch::keep_mont48
+    const uint32_t* sig_bad;       // per group: members left out of it, G2AggregateRowsBatch::keep_bad
+    const uint8_t* msg192;         // the message points, wire bytes, 16-byte aligned
+    const uint32_t* point_of_row;  // nullable: group g takes point point_of_row[grp[g].rep], else point g
+    const uint8_t* neg_g1_be96;    // -g1, wire bytes
+    AttGroup* grp;                 // the aggregate's groups (sig_valid is written under PE_VERIFY_APPLY)
+    const uint32_t* union_info;    // [2g + 1]: the members of group g overlap
+    uint32_t n_groups;
+    uint32_t* ws; int32_t* pair_flag; uint32_t* offsets;  // the Miller workspace: 2 n_groups rows and flags, n_groups + 1 offsets
+    uint32_t* ident;               // per group: BLS_RES_ID_* of its three points
+    const int32_t* sig_status;     // per group: k_g2_subgroup_check's word over sig_mont48 (0 where the pass did not run)
+    const int32_t* fe_verdict;     // per group: k_bls_final_exp's word
+    int32_t* verdict;              // per group: out
+    uint32_t* stats;               // BLS_RES_REASONS counters, zeroed by the caller: groups per deciding row of the table
+    uint32_t apply;
+};
+enum { BLS_RES_ID_KEY = 1, BLS_RES_ID_SIG = 2, BLS_RES_ID_MSG = 4 };
+// the row of the rule table that decided a group (include/posevo.h, pe_verify_resident), in precedence order
+enum { BLS_RES_NO_COMMITTEE = 0, BLS_RES_BAD_MESSAGE, BLS_RES_OVERLAP, BLS_RES_BAD_MEMBER, BLS_RES_EMPTY_KEY, BLS_RES_IDENTITY_SIG,
+       BLS_RES_IDENTITY_MSG, BLS_RES_NOT_G2, BLS_RES_PAIRING, BLS_RES_REASONS };
+constexpr int32_t BLS_UNDECIDED = 3;  // PE_BLS_UNDECIDED
+// a lane pair per pair: workspace rows, pair flags, offsets and identity words of every group
+void launch_bls_resident_prepare(hipStream_t s, const BlsResidentArgs& a);
+// a lane per group: the rule table over the final exponentiation's word and everything the aggregate knew already
+void launch_bls_resident_settle(hipStream_t s, const BlsResidentArgs& a);
 
 // ---- batch verification by random linear combination (bls_batch_kernels.hip; host side: engine_batch.cpp) ----
 constexpr uint32_t BLS_BATCH_FAN = 8;  // F: Fp12 values one row of k_bls_gt_product multiplies per launch

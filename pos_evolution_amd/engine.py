@@ -295,6 +295,7 @@ class Engine:
         self._ring_ord = {}
         self._lag = int(self._lib.pe_pipeline_get_lag(self._h)) or 2
         self._resident_active = 0   # length of the list the last active_set left on the device
+        self._signed_device_rows = 0   # input rows of the last successful aggregate_signed over DeviceRows (verify_resident)
 
     def set_pipeline_lag(self, depth: int):
         """Lag depth of ``pipeline(lagged=True)`` blocks (pe_pipeline_set_lag): a block's outputs are complete when the
@@ -628,6 +629,7 @@ class Engine:
         arr, arena = packed if packed is not None else pack_attestations(rows)
         n = len(rows) if rows is not None else len(arr)
         m = max(n, 1)
+        self._signed_device_rows = 0   # verify_resident follows an aggregate_signed, not this
         if arr.__class__ is DeviceRows:  # rows in device memory: grouped / resolved / validated there
             assert sig_points96 is None and sig_points192 is None, "signature points take host rows"
             (out_atts, group_of, out_arena, out_pk, count, ng), (p_atts, p_gof, p_arena, p_pk, p_count, p_ng) = self._outs(
@@ -693,6 +695,7 @@ class Engine:
                                          ((m, 96), _U8) if want_aggregate_pubkeys else None, (m, _U32), (1, _U32),
                                          ((m, 96), _U8), (m, _I32)))
         ng[0] = 0
+        self._signed_device_rows = 0
         if self._pipe_keep is not None:
             self._pipe_keep.append((arr, arena, sig, out_atts, group_of, out_arena, out_pk, count, ng, osig, sst))
         rc = self._lib.pe_aggregate_signed(self._h, arr.ptr if dev else _att_ptr(arr), n, _ptr(arena, C.c_uint8), arena.size,
@@ -700,6 +703,7 @@ class Engine:
                                            p_sst, p_pk, p_count)
         if rc:
             self._check(rc)
+        self._signed_device_rows = n if dev else 0
         return ResidentAggregateResult(_raw=dict(n_groups=ng, atts=out_atts, group_of=group_of, out_arena=out_arena,
                                                  aggpk96=out_pk, count=count, sig96c=osig, sig_status=sst[:n]),
                                        sig96=None, sig192=None)
@@ -823,6 +827,39 @@ class Engine:
             r_ptr, _ptr(verdict, C.c_int32), _ptr(status, C.c_int32), _ptr(group, C.c_int32),
             _ptr(out, C.c_uint8) if aggregates else None))
         return verdict[:members], status[:members], group[:n_groups], (out[:n_groups] if aggregates else None)
+
+    def verify_resident(self, message_points192, point_of_row=None, apply: bool = True, cap: Optional[int] = None) -> np.ndarray:
+        """pe_verify_resident: int32[n_groups], one verdict per group of the last ``aggregate_signed`` over DeviceRows with
+        ``want_aggregate_pubkeys=True``, from the aggregate keys and signatures that call left in device memory: 1 valid,
+        0 not (also: overlapping members, a member that did not decode, an empty union, an identity signature or message
+        point, an aggregate signature outside G2), 2 = the message point is off its curve, 3 = the group has no committee.
+        message_points192: (n_points, 192) uint8 H(m), or a DeviceArena holding them; point_of_row: one point index per input
+        row of that aggregate (its group takes the point of its first row), None: group g takes point g.  ``apply``: the
+        verdict is ANDed into the groups' signature flag on the device, so that on_attestation_batch /
+        process_attestation_batch with (ROWS_RESIDENT, RESIDENT) answer PE_ATT_BAD_SIGNATURE for what did not verify.
+        ``cap``: entries of the verdict array handed to the library (default: that aggregate's input rows, which bound its groups)."""
+        if message_points192.__class__ is DeviceArena:
+            msg_ptr, n_points = message_points192.ptr, message_points192.size // 192
+        else:
+            msg = np.ascontiguousarray(message_points192, dtype=np.uint8).reshape(-1, 192)
+            msg_ptr, n_points = msg.ctypes.data, len(msg)
+        por = None if point_of_row is None else np.ascontiguousarray(point_of_row, dtype=np.uint32)
+        rows = self._signed_device_rows  # input rows of the last aggregate_signed over DeviceRows: bounds its groups
+        if por is not None and por.size != rows:
+            raise ValueError("one point index per input row of the resident aggregate")
+        cap = rows if cap is None else int(cap)
+        verdict = np.zeros(max(cap, 1), dtype=np.int32)
+        self._check(self._lib.pe_verify_resident(self._h, C.c_void_p(msg_ptr), n_points, _ptr(por, C.c_uint32) if por is not None else None,
+                                                 _abi.PE_VERIFY_APPLY if apply else 0, cap, _ptr(verdict, C.c_int32)))
+        return verdict[:self._profile_verify_resident_stats()["groups"]]
+
+    def _profile_verify_resident_stats(self) -> dict:
+        """pe_profile_verify_resident_stats: how the last verify_resident decided its groups, by row of the rule table."""
+        out = np.zeros(_abi.PE_VERIFY_RESIDENT_STATS, dtype=np.uint32)
+        self._check(self._lib.pe_profile_verify_resident_stats(self._h, _ptr(out, C.c_uint32)))
+        names = ("no_committee", "bad_message", "overlap", "bad_member", "empty_key", "identity_signature", "identity_message",
+                 "not_g2", "pairing", "subgroup_pass", "groups")
+        return dict(zip(names, (int(v) for v in out)))
 
     def _profile_verify_set_stripe(self, k: int) -> None:
         """pe_profile_verify_set_stripe: k, the members of one slot of verify_signatures' weighted sums."""

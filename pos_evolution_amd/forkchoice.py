@@ -389,6 +389,19 @@ def verify_attestation_signatures(store: Store, signers: Sequence[Sequence[int]]
     return [[int(v) == 1 for v in verdict[off[g]:off[g + 1]]] for g in range(len(lists))]
 
 
+def verify_resident_attestations(store: Store, message_points, point_of_row=None) -> list:
+    """The pairing check of is_valid_indexed_attestation (pe:736, 976, 1456) for every aggregate the engine's last
+    ``aggregate_signed`` over DeviceRows formed (with ``want_aggregate_pubkeys=True``), computed where the aggregate keys and
+    signatures lie; the verdicts take the place of the injected ``signature_valid``: ``on_attestation_batch`` /
+    ``process_attestation_batch`` with ``(ROWS_RESIDENT, RESIDENT)`` afterwards reject every group that did not verify with
+    PE_ATT_BAD_SIGNATURE.  ``message_points``: H(m) as 192-byte uncompressed G2 points (hash_to_curve is the caller's), one per
+    group in group order, or -- with ``point_of_row`` (one index per input row) -- in any order, named by row.  Returns one
+    entry per group: True / False, or None for a group without a committee (the handlers reject it for that reason)."""
+    msg = np.frombuffer(b"".join(bytes(m) for m in message_points), dtype=np.uint8)
+    verdict = store.engine.verify_resident(msg, point_of_row=point_of_row, apply=True)
+    return [None if int(v) == _abi.PE_BLS_UNDECIDED else int(v) == _abi.PE_BLS_VALID for v in verdict]
+
+
 def get_head(store: Store) -> bytes:
     """pe:1102-1116.  Raises (AssertionError) when the justified checkpoint has moved and the balances of its state
     have not been handed over (Store.ensure_justified_state)."""
