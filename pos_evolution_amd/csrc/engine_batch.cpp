@@ -60,33 +60,37 @@ int batch_run(pe_engine* h, const char* who, const uint8_t* pk96, const uint8_t*
         if (scalars[g] == 0) return fail(h, PE_ERR_INVALID_ARG, std::string(who) + ": a zero scalar");
 
     const size_t max_chunks = ((size_t)n + c - 1) / c, rows = (size_t)n + max_chunks, lvl = (max_chunks + F - 1) / F;
-    const size_t o_pk = 0, o_msg = o_pk + up256(96 * (size_t)n), o_sig = o_msg + up256(192 * (size_t)n),
-                 o_scal = o_sig + up256(192 * (size_t)n), o_neg = o_scal + up256(8 * (size_t)n), o_status = o_neg + 256,
-                 o_pkm = o_status + up256(4 * (size_t)n), o_msgm = o_pkm + up256(96 * (size_t)n),
-                 o_sigm = o_msgm + up256(192 * (size_t)n), o_live = o_sigm + up256(192 * (size_t)n),
-                 o_scaled = o_live + up256(4 * (size_t)n), o_ws = o_scaled + up256(384 * (size_t)n),
-                 o_flag = o_ws + up256(4 * (size_t)BLS_PAIR_WORDS * rows), o_off = o_flag + up256(4 * rows),
-                 o_gt = o_off + up256(4 * (max_chunks + 1)), o_lvl0 = o_gt + up256(4 * (size_t)BLS_GT_WORDS * max_chunks),
-                 o_lvl1 = o_lvl0 + up256(4 * (size_t)BLS_GT_WORDS * lvl), o_bad = o_lvl1 + up256(4 * (size_t)BLS_GT_WORDS * lvl),
-                 o_zero = o_bad + up256(4 * max_chunks), o_verdict = o_zero + 256, o_out = o_verdict + up256(4 * max_chunks),
-                 total = o_out + up256(576);
-    HIP_TRY(h, h->d_batch.ensure(total));
-    uint8_t* d = h->d_batch.as<uint8_t>();
-    auto w32 = [&](size_t o) { return reinterpret_cast<uint32_t*>(d + o); };
-    auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(d + o); };
-    HIP_TRY(h, hipMemcpyAsync(d + o_pk, pk96, 96 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(d + o_msg, msg192, 192 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(d + o_sig, sig192, 192 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(d + o_scal, scalars, 8 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(d + o_neg, NEG_G1_BE96, 96, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(d + o_zero, 0, 4, h->stream));
+    const size_t N = n;
+    Layout L;
+    const auto r_pk = L.take<uint8_t>(96 * N), r_msg = L.take<uint8_t>(192 * N), r_sig = L.take<uint8_t>(192 * N);
+    const auto r_scal = L.take<uint64_t>(N);
+    const auto r_neg = L.take_bytes(256);  // -g1, 96 wire bytes
+    const auto r_status = L.take<int32_t>(N);
+    const auto r_pkm = L.take<uint32_t>(24 * N), r_msgm = L.take<uint32_t>(48 * N), r_sigm = L.take<uint32_t>(48 * N);
+    const auto r_live = L.take<uint32_t>(N), r_scaled = L.take<uint32_t>(96 * N);
+    const auto r_ws = L.take<uint32_t>((size_t)BLS_PAIR_WORDS * rows);
+    const auto r_flag = L.take<int32_t>(rows);
+    const auto r_off = L.take<uint32_t>(max_chunks + 1), r_gt = L.take<uint32_t>((size_t)BLS_GT_WORDS * max_chunks);
+    const auto r_lvl0 = L.take<uint32_t>((size_t)BLS_GT_WORDS * lvl), r_lvl1 = L.take<uint32_t>((size_t)BLS_GT_WORDS * lvl);
+    const auto r_bad = L.take<int32_t>(max_chunks);
+    const auto r_zero = L.take_bytes<int32_t>(256);  // the "no bad point" flag of the one product
+    const auto r_verdict = L.take<int32_t>(max_chunks);
+    const auto r_out = L.take<uint8_t>(576);
+    Workspace w;
+    HIP_TRY(h, w.bind(h->d_batch, L, h->stream));
+    HIP_TRY(h, w.put(r_pk, pk96, 96 * N));
+    HIP_TRY(h, w.put(r_msg, msg192, 192 * N));
+    HIP_TRY(h, w.put(r_sig, sig192, 192 * N));
+    HIP_TRY(h, w.put(r_scal, scalars, N));
+    HIP_TRY(h, w.put(r_neg, NEG_G1_BE96, 96));
+    HIP_TRY(h, w.zero(r_zero, 1));
 
     // ---- settle: what never enters the batch
-    launch_bls_batch_settle(h->stream, d + o_pk, d + o_msg, d + o_sig, n, w32(o_pkm), w32(o_msgm), w32(o_sigm), i32(o_status));
-    launch_g2_subgroup_check(h->stream, w32(o_sigm), n, i32(o_status));  // the batch is sound over G2 only
+    launch_bls_batch_settle(h->stream, w(r_pk), w(r_msg), w(r_sig), n, w(r_pkm), w(r_msgm), w(r_sigm), w(r_status));
+    launch_g2_subgroup_check(h->stream, w(r_sigm), n, w(r_status));  // the batch is sound over G2 only
     HIP_TRY(h, hipGetLastError());
     std::vector<int32_t> status(n);
-    HIP_TRY(h, hipMemcpyAsync(status.data(), d + o_status, 4 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, w.get(r_status, status.data(), N));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     std::vector<uint32_t> live;
     live.reserve(n);
@@ -103,38 +107,37 @@ int batch_run(pe_engine* h, const char* who, const uint8_t* pk96, const uint8_t*
     std::vector<uint32_t> off((size_t)chunks + 1);
     for (uint32_t j = 0; j < chunks; ++j) off[j] = j * (c + 1);
     off[chunks] = n_live + chunks;
-    HIP_TRY(h, hipMemcpyAsync(d + o_live, live.data(), 4 * (size_t)n_live, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(d + o_off, off.data(), 4 * ((size_t)chunks + 1), hipMemcpyHostToDevice, h->stream));
-    const uint64_t* d_scal = reinterpret_cast<const uint64_t*>(d + o_scal);
-    launch_bls_scale_g1(h->stream, w32(o_live), n_live, c, d_scal, w32(o_pkm), w32(o_msgm), w32(o_ws), i32(o_flag));
-    launch_bls_scale_g2(h->stream, w32(o_live), n_live, d_scal, w32(o_sigm), w32(o_scaled));
-    launch_bls_chunk_sig(h->stream, w32(o_scaled), n_live, c, chunks, d + o_neg, w32(o_ws), i32(o_flag));
-    launch_bls_miller(h->stream, w32(o_ws), i32(o_flag), w32(o_off), chunks, w32(o_gt), i32(o_bad));
-    const uint32_t* top = w32(o_gt);  // the chunk values stay where they are: the fallback needs them
+    HIP_TRY(h, w.put(r_live, live.data(), n_live));
+    HIP_TRY(h, w.put(r_off, off.data(), (size_t)chunks + 1));
+    launch_bls_scale_g1(h->stream, w(r_live), n_live, c, w(r_scal), w(r_pkm), w(r_msgm), w(r_ws), w(r_flag));
+    launch_bls_scale_g2(h->stream, w(r_live), n_live, w(r_scal), w(r_sigm), w(r_scaled));
+    launch_bls_chunk_sig(h->stream, w(r_scaled), n_live, c, chunks, w(r_neg), w(r_ws), w(r_flag));
+    launch_bls_miller(h->stream, w(r_ws), w(r_flag), w(r_off), chunks, w(r_gt), w(r_bad));
+    const uint32_t* top = w(r_gt);  // the chunk values stay where they are: the fallback needs them
     uint32_t m = chunks, side = 0;
     while (m > 1) {
         const uint32_t m_out = (m + F - 1) / F;
-        uint32_t* out = w32(side ? o_lvl1 : o_lvl0);
+        uint32_t* out = w(side ? r_lvl1 : r_lvl0);
         launch_bls_gt_product(h->stream, top, m, out, m_out);
         top = out;
         m = m_out;
         side ^= 1;
         ++st[2];
     }
-    launch_bls_final_exp(h->stream, top, i32(o_zero), 1, i32(o_verdict), d + o_out);
+    launch_bls_final_exp(h->stream, top, w(r_zero), 1, w(r_verdict), w(r_out));
     st[3] = 1;
     HIP_TRY(h, hipGetLastError());
     int32_t all_valid = 0;
-    HIP_TRY(h, hipMemcpyAsync(&all_valid, d + o_verdict, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->batch_gt, d + o_out, 576, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, w.get(r_verdict, &all_valid, 1));
+    HIP_TRY(h, w.get(r_out, h->batch_gt, 576));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (all_valid == 1) return PE_OK;
 
     // ---- fallback: which chunks, then their live groups one by one
     std::vector<int32_t> chunk_ok(chunks);
-    launch_bls_final_exp(h->stream, w32(o_gt), i32(o_bad), chunks, i32(o_verdict), nullptr);
+    launch_bls_final_exp(h->stream, w(r_gt), w(r_bad), chunks, w(r_verdict), nullptr);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(chunk_ok.data(), d + o_verdict, 4 * (size_t)chunks, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, w.get(r_verdict, chunk_ok.data(), chunks));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     st[4] = chunks;
     std::vector<uint32_t> again;

@@ -31,30 +31,28 @@ int pairing_run(pe_engine* h, const char* who, const uint8_t* g1, const uint8_t*
         if (offsets[g + 1] < offsets[g]) return fail(h, PE_ERR_INVALID_ARG, std::string(who) + ": offsets not monotone");
     if (offsets[n_groups] > n_pairs) return fail(h, PE_ERR_INVALID_ARG, std::string(who) + ": offsets exceed the number of pairs");
     const size_t rows = std::max<uint64_t>(1, n_pairs);  // the kernels' idle lanes read row 0
-    const size_t o_g1 = 0, o_g2 = o_g1 + up256(96 * rows), o_off = o_g2 + up256(192 * rows),
-                 o_ws = o_off + up256(4 * ((size_t)n_groups + 1)), o_flag = o_ws + up256(4 * (size_t)BLS_PAIR_WORDS * rows),
-                 o_gt = o_flag + up256(4 * rows), o_bad = o_gt + up256(4 * (size_t)BLS_GT_WORDS * n_groups),
-                 o_verdict = o_bad + up256(4 * (size_t)n_groups), o_out = o_verdict + up256(4 * (size_t)n_groups),
-                 total = o_out + (out576 ? up256(576 * (size_t)n_groups) : 0);
-    HIP_TRY(h, h->d_bls.ensure(total));
-    uint8_t* d = h->d_bls.as<uint8_t>();
-    if (n_pairs == 0) HIP_TRY(h, hipMemsetAsync(d + o_flag, 0, 4, h->stream));
+    const size_t ng = n_groups;
+    Layout L;
+    const auto r_g1 = L.take<uint8_t>(96 * rows), r_g2 = L.take<uint8_t>(192 * rows);
+    const auto r_off = L.take<uint32_t>(ng + 1), r_ws = L.take<uint32_t>((size_t)BLS_PAIR_WORDS * rows);
+    const auto r_flag = L.take<int32_t>(rows);
+    const auto r_gt = L.take<uint32_t>((size_t)BLS_GT_WORDS * ng);
+    const auto r_bad = L.take<int32_t>(ng), r_verdict = L.take<int32_t>(ng);
+    const auto r_out = L.take<uint8_t>(out576 ? 576 * ng : 0);
+    Workspace w;
+    HIP_TRY(h, w.bind(h->d_bls, L, h->stream));
+    if (n_pairs == 0) HIP_TRY(h, w.zero(r_flag, 1));
     if (n_pairs) {
-        HIP_TRY(h, hipMemcpyAsync(d + o_g1, g1, 96 * n_pairs, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(d + o_g2, g2, 192 * n_pairs, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, w.put(r_g1, g1, 96 * n_pairs));
+        HIP_TRY(h, w.put(r_g2, g2, 192 * n_pairs));
     }
-    HIP_TRY(h, hipMemcpyAsync(d + o_off, offsets, 4 * ((size_t)n_groups + 1), hipMemcpyHostToDevice, h->stream));
-    uint32_t* ws = reinterpret_cast<uint32_t*>(d + o_ws);
-    int32_t* flag = reinterpret_cast<int32_t*>(d + o_flag);
-    uint32_t* gt = reinterpret_cast<uint32_t*>(d + o_gt);
-    int32_t* bad = reinterpret_cast<int32_t*>(d + o_bad);
-    int32_t* dv = reinterpret_cast<int32_t*>(d + o_verdict);
-    launch_bls_prepare(h->stream, d + o_g1, d + o_g2, n_pairs, ws, flag);
-    launch_bls_miller(h->stream, ws, flag, reinterpret_cast<const uint32_t*>(d + o_off), n_groups, gt, bad);
-    launch_bls_final_exp(h->stream, gt, bad, n_groups, dv, out576 ? d + o_out : nullptr);
+    HIP_TRY(h, w.put(r_off, offsets, ng + 1));
+    launch_bls_prepare(h->stream, w(r_g1), w(r_g2), n_pairs, w(r_ws), w(r_flag));
+    launch_bls_miller(h->stream, w(r_ws), w(r_flag), w(r_off), n_groups, w(r_gt), w(r_bad));
+    launch_bls_final_exp(h->stream, w(r_gt), w(r_bad), n_groups, w(r_verdict), out576 ? w(r_out) : nullptr);
     HIP_TRY(h, hipGetLastError());
-    if (verdict) HIP_TRY(h, hipMemcpyAsync(verdict, dv, 4 * (size_t)n_groups, hipMemcpyDeviceToHost, h->stream));
-    if (out576) HIP_TRY(h, hipMemcpyAsync(out576, d + o_out, 576 * (size_t)n_groups, hipMemcpyDeviceToHost, h->stream));
+    if (verdict) HIP_TRY(h, w.get(r_verdict, verdict, ng));
+    if (out576) HIP_TRY(h, w.get(r_out, out576, 576 * ng));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return PE_OK;
 }

@@ -294,6 +294,35 @@ bool sig_batch_holds(const pe_engine* h, int arena)
     return false;
 }
 
+
+// ---------------------------------------------------------------- the settle prelude of compressed signature lists
+int settle_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t n, size_t tail_words, bool check_subgroup,
+                      bool mark_identity, HostLap* lap, SettledSigs* out)
+{
+    hipStream_t s = h->stream;
+    const MemKind kind = mem_kind(signatures96);
+    const size_t rows = std::max<uint64_t>(n, 1);  // never an empty buffer: the kernels get pointers
+    Layout Lin, L;
+    const auto r_in = Lin.take<uint8_t>(reads_in_place(kind, signatures96) ? 0 : 96 * rows);
+    const auto r_pts = L.take<uint32_t>(48 * rows);
+    const auto r_status = L.take<int32_t>(rows);
+    const auto r_tail = L.take<uint32_t>(tail_words);
+    Workspace win, w;
+    const uint8_t* d_in = nullptr;
+    HIP_TRY(h, win.bind(h->d_tmp_be, Lin, s));
+    HIP_TRY(h, device_view(win, r_in, kind, signatures96, 96 * (size_t)n, &d_in));
+    HIP_TRY(h, w.bind(h->d_tmp_points, L, s));
+    if (lap) lap->mark("usig.1_checks_scratch");
+    launch_g2_decompress(s, d_in, n, w(r_pts), nullptr, w(r_status));  // a signature that does not decode becomes the (0, 0) row: infinity
+    if (lap) lap->mark("usig.2_decompress_launch");
+    if (check_subgroup) launch_g2_subgroup_check(s, w(r_pts), n, w(r_status));
+    if (mark_identity) launch_sv_mark_identity(s, w(r_pts), n, w(r_status), PE_SIG_STATUS_IDENTITY);
+    // a row with a non-zero status is left out of its sum like an undecodable one
+    if (check_subgroup || mark_identity) launch_g2_mask_bad(s, w(r_pts), n, w(r_status));
+    *out = SettledSigs{w(r_pts), w(r_status), w(r_tail)};
+    return PE_OK;
+}
+
 }  // namespace posevo
 
 extern "C" {
@@ -613,25 +642,11 @@ int pe_aggregate_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t 
         return fail(h, PE_ERR_INVALID_ARG, "offsets exceed the number of signatures");
     }
     hipStream_t s = h->stream;
-    // wire bytes: in place when they lie in device memory at a 16-byte boundary, else through the engine's scratch
-    const bool sig_dev = mem_kind(signatures96) == MemKind::Device;
-    const uint8_t* d_in = signatures96;
-    if (!(sig_dev && (reinterpret_cast<uintptr_t>(signatures96) & 15) == 0)) {
-        HIP_TRY(h, h->d_tmp_be.ensure(std::max<size_t>(96, 96ull * n)));
-        if (n) HIP_TRY(h, hipMemcpyAsync(h->d_tmp_be.p, signatures96, 96ull * n, sig_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-        d_in = h->d_tmp_be.as<uint8_t>();
-    }
-    HIP_TRY(h, h->d_tmp_points.ensure(std::max<size_t>(192, 192ull * n + 4ull * n + (idx_dev ? 4ull * total : 0) + 64)));
-    uint32_t* d_pts = h->d_tmp_points.as<uint32_t>();
-    int32_t* d_status = reinterpret_cast<int32_t*>(h->d_tmp_points.as<uint8_t>() + 192ull * n);
-    uint32_t* d_index_checked = reinterpret_cast<uint32_t*>(h->d_tmp_points.as<uint8_t>() + 196ull * n);  // a device index, range-checked
-    lap.mark("usig.1_checks_scratch");
-    launch_g2_decompress(s, d_in, n, d_pts, nullptr, d_status);  // a signature that does not decode becomes the (0, 0) row: infinity
-    lap.mark("usig.2_decompress_launch");
-    if (sig_flags & PE_SIG_CHECK_SUBGROUP) {
-        launch_g2_subgroup_check(s, d_pts, n, d_status);
-        launch_g2_mask_bad(s, d_pts, n, d_status);  // a decoded point outside G2 is left out of its sum like an undecodable one
-    }
+    SettledSigs sg;  // tail: a device index, range-checked
+    PE_TRY(settle_signatures(h, signatures96, n, idx_dev ? total : 0, (sig_flags & PE_SIG_CHECK_SUBGROUP) != 0, false, &lap, &sg));
+    uint32_t* const d_pts = sg.pts;
+    int32_t* const d_status = sg.status;
+    uint32_t* const d_index_checked = sg.tail;
     Stage st(h);
     PE_TRY(st.reserve(sizeof(G1Group) * (size_t)n_groups + (idx_dev ? 0 : 4ull * total) + 4096));
     const size_t off_g = st.alloc(sizeof(G1Group) * (size_t)n_groups);

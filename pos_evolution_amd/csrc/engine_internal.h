@@ -41,6 +41,7 @@
 #include "../../include/posevo.h"
 #include "../../include/posevo_profile.h"
 #include "att_row.h"
+#include "carve.h"
 #include "kernels.h"
 
 namespace posevo {
@@ -132,6 +133,39 @@ struct PinBuf {
         cap = 0;
     }
     template <typename T> T* as() const { return static_cast<T*>(p); }
+};
+
+// A Layout (carve.h) bound to the DevBuf that holds it: bind() is the layout's ONE ensure and yields the base, so there is no
+// pointer into the buffer before it has its size and none that a later growth could leave behind.  A call that reuses a buffer
+// for a second layout binds again.  Pointers come from regions, w(region); the transfers take elements, derive the bytes from
+// the region's type and refuse more than the region holds.
+struct Workspace {
+    uint8_t* base = nullptr;
+    hipStream_t s = nullptr;
+    hipError_t bind(DevBuf& b, const Layout& l, hipStream_t stream)
+    {
+        const hipError_t e = b.ensure(l.total());
+        base = b.as<uint8_t>();
+        s = stream;
+        return e;
+    }
+    template <typename T> T* operator()(const Region<T>& r) const { return r.at(base); }
+    template <typename T> hipError_t put(const Region<T>& r, const void* host, size_t n) const  // host -> region
+    {
+        assert(r.holds(n));
+        return r.holds(n) ? hipMemcpyAsync(r.at(base), host, n * sizeof(T), hipMemcpyHostToDevice, s) : hipErrorInvalidValue;
+    }
+    template <typename T> hipError_t get(const Region<T>& r, void* host, size_t n) const  // region -> host
+    {
+        assert(r.holds(n));
+        return r.holds(n) ? hipMemcpyAsync(host, r.at(base), n * sizeof(T), hipMemcpyDeviceToHost, s) : hipErrorInvalidValue;
+    }
+    template <typename T> hipError_t fill(const Region<T>& r, int byte, size_t n) const  // every byte of n elements
+    {
+        assert(r.holds(n));
+        return r.holds(n) ? hipMemsetAsync(r.at(base), byte, n * sizeof(T), s) : hipErrorInvalidValue;
+    }
+    template <typename T> hipError_t zero(const Region<T>& r, size_t n) const { return fill(r, 0, n); }
 };
 
 struct CommitteeTable {
@@ -259,7 +293,7 @@ struct pe_engine {
     DevBuf d_ssz_validator_roots;  // hash_tree_root(Validator) of every validator, u8[n_val][32]: the leaves of `validators`
     DevBuf d_ssz_level[2];         // the nodes between two passes of k_ssz_merkle, word form
     DevBuf d_ssz_chunks;           // pe_ssz_merkleize: the caller's chunks
-    DevBuf d_bls;                  // pe_pairing_check: inputs | workspace rows | flags | Fp12 values | verdicts of one call (engine_bls.cpp)
+    DevBuf d_bls;                  // one pairing run's workspace: the Layout of pairing_run (engine_bls.cpp) or of pe_verify_resident
     // ---- pe_verify_resident (engine_resident_verify.cpp) ----
     // which aggregate the arena's d_res_points belong to: valid while that is still the handle's last aggregate of either kind
     struct ResidentVerify {
@@ -273,12 +307,12 @@ struct pe_engine {
     std::vector<uint8_t> verify_head;  // pe_verify_resident: -g1 | point_of_row as uploaded (outlives the copy whatever the call returns)
     uint32_t verify_resident_stats[PE_VERIFY_RESIDENT_STATS] = {};  // pe_profile_verify_resident_stats, of the last call
     // ---- pe_batch_verify (engine_batch.cpp) ----
-    DevBuf d_batch;                // one call's inputs, Montgomery rows, scaled points, chunk rows, chunk values and product levels
+    DevBuf d_batch;                // one call's workspace: the Layout of batch_run
     uint32_t batch_chunk = 2;      // c: live groups per chunk (pe_profile_batch_set_chunk)
     uint32_t batch_stats[8] = {};  // pe_profile_batch_stats, of the last call
     uint8_t batch_gt[576] = {};    // pe_profile_batch_gt, of the last call
     // ---- pe_verify_signatures (engine_sigverify.cpp) ----
-    DevBuf d_verify;                // one call's member lists, scalars, plans, partials, sums and locate rows
+    DevBuf d_verify;                // one call's workspace: the Layouts of its sums, locate and aggregate phases, bound in turn
     uint32_t verify_stripe = 16;    // k: members per slot of the weighted sums (pe_profile_verify_set_stripe)
     uint32_t verify_stats[5] = {};  // pe_profile_verify_stats, of the last call
     std::vector<uint8_t> verify_sums_pk, verify_sums_sig;  // pe_profile_verify_sums, of the last call (96 / 192 bytes a group)
@@ -596,15 +630,14 @@ int pairing_run(pe_engine* h, const char* who, const uint8_t* g1, const uint8_t*
 using WireAt = std::function<const uint8_t*(uint32_t)>;
 int verify_pairs_run(pe_engine* h, const char* who, uint32_t n, const WireAt& pk_at, const WireAt& msg_at, const WireAt& sig_at,
                      int32_t* verdict);
-inline size_t up256(size_t v) { return (v + 255) & ~size_t(255); }  // sub-buffers of one allocation start 256-byte aligned
 // PipeArena::d_res_points for an aggregate over n input rows (n bounds its groups)
 struct ResPoints { uint32_t *pk_xyzz48, *sig_mont48, *sig_bad; size_t bytes; };
 inline ResPoints res_points_layout(void* base, uint32_t n)
 {
-    uint8_t* b = static_cast<uint8_t*>(base);
-    const size_t rows = std::max<uint32_t>(n, 1), o_sig = up256(192 * rows), o_bad = o_sig + up256(192 * rows);
-    return ResPoints{reinterpret_cast<uint32_t*>(b), reinterpret_cast<uint32_t*>(b + o_sig), reinterpret_cast<uint32_t*>(b + o_bad),
-                     o_bad + up256(4 * rows)};
+    const size_t rows = std::max<uint32_t>(n, 1);
+    Layout l;
+    const auto pk = l.take<uint32_t>(48 * rows), sig = l.take<uint32_t>(48 * rows), bad = l.take<uint32_t>(rows);
+    return ResPoints{pk.at(base), sig.at(base), bad.at(base), l.total()};
 }
 // the calls that serve one GPU only
 inline int refuse_dist(pe_engine* h, const char* who)
@@ -954,6 +987,28 @@ bool find_resident(const pe_engine* h, const pe_attestation& a, uint32_t* g_out,
 // Where a caller's pointer lives (engine_resident.cpp).  Pageable is also the answer for anything the runtime does not know.
 enum class MemKind { Pageable, Pinned, Device };
 MemKind mem_kind(const void* p);
+// What a kernel reads for the caller's `bytes` at src (kind = mem_kind(src)): src itself where it lies in device memory at a
+// 16-byte boundary (the kernels' widest loads), else `scratch`, behind a copy enqueued on the workspace's stream.
+inline bool reads_in_place(MemKind kind, const void* src)
+{
+    return kind == MemKind::Device && (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+}
+inline hipError_t device_view(const Workspace& w, const Region<uint8_t>& scratch, MemKind kind, const uint8_t* src, size_t bytes,
+                              const uint8_t** out)
+{
+    if (reads_in_place(kind, src)) { *out = src; return hipSuccess; }
+    assert(scratch.holds(bytes));
+    if (!scratch.holds(bytes)) return hipErrorInvalidValue;
+    *out = w(scratch);
+    if (bytes == 0) return hipSuccess;
+    return hipMemcpyAsync(w(scratch), src, bytes, kind == MemKind::Device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, w.s);
+}
+// The settle prelude of a list of n compressed signatures (engine_g1.cpp), on the engine's stream: wire bytes viewed or copied
+// (d_tmp_be) -> k_g2_decompress into d_tmp_points -> [the G2 subgroup test] -> [identities marked PE_SIG_STATUS_IDENTITY] ->
+// where either ran, rows with a non-zero status masked to infinity.  tail: `tail_words` more words of d_tmp_points, the caller's.
+struct SettledSigs { uint32_t* pts; int32_t* status; uint32_t* tail; };
+int settle_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t n, size_t tail_words, bool check_subgroup,
+                      bool mark_identity, HostLap* lap, SettledSigs* out);
 // The handlers and pe_get_indexed_attestations re-pack the caller's bits on the host: device memory would fault there.
 inline bool bits_on_device(const uint8_t* bits_arena) { return mem_kind(bits_arena) == MemKind::Device; }
 // slashing detection (engine_slash.cpp): drop every record and table, keep the allocation | free it

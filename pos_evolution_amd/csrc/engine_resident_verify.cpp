@@ -51,57 +51,60 @@ int pe_verify_resident(pe_engine* h, const uint8_t* message_points192, uint32_t 
     const ResPoints kept = res_points_layout(h->arena[rv.arena].d_res_points.p, n_in);
     // the message points: read in place from 16-byte aligned device memory, copied otherwise
     const MemKind msg_kind = mem_kind(message_points192);
-    const bool msg_in_place = msg_kind == MemKind::Device && (reinterpret_cast<uintptr_t>(message_points192) & 15) == 0;
-    const size_t o_head = 0, o_por = o_head + 256, o_msg = o_por + up256(point_of_row ? 4 * (size_t)n_in : 0),
-                 o_off = o_msg + up256(msg_in_place ? 0 : 192 * (size_t)n_points), o_ws = o_off + up256(4 * ((size_t)ng + 1)),
-                 o_flag = o_ws + up256(4 * (size_t)BLS_PAIR_WORDS * 2 * ng), o_gt = o_flag + up256(8 * (size_t)ng),
-                 o_gbad = o_gt + up256(4 * (size_t)BLS_GT_WORDS * ng), o_fe = o_gbad + up256(4 * (size_t)ng),
-                 o_ident = o_fe + up256(4 * (size_t)ng), o_sub = o_ident + up256(4 * (size_t)ng),
-                 o_out = o_sub + up256(4 * (size_t)ng), total = o_out + 64 + 4 * (size_t)ng;  // counters | verdicts: one copy out
-    HIP_TRY(h, h->d_bls.ensure(total));
-    uint8_t* d = h->d_bls.as<uint8_t>();
+    const bool msg_in_place = reads_in_place(msg_kind, message_points192);
+    const size_t G = ng, por_bytes = point_of_row ? 4 * (size_t)n_in : 0;
+    Layout L;
+    const auto r_head = L.take_bytes(256 + por_bytes);  // -g1 in 256 bytes | point_of_row: one copy in
+    const auto r_por = r_head.part<uint32_t>(256, por_bytes / 4);
+    const auto r_msg = L.take<uint8_t>(msg_in_place ? 0 : 192 * (size_t)n_points);
+    const auto r_off = L.take<uint32_t>(G + 1), r_ws = L.take<uint32_t>((size_t)BLS_PAIR_WORDS * 2 * G);
+    const auto r_flag = L.take<int32_t>(2 * G);
+    const auto r_gt = L.take<uint32_t>((size_t)BLS_GT_WORDS * G);
+    const auto r_gbad = L.take<int32_t>(G), r_fe = L.take<int32_t>(G);
+    const auto r_ident = L.take<uint32_t>(G);
+    const auto r_sub = L.take<int32_t>(G);
+    const auto r_out = L.take_bytes<uint32_t>(64 + 4 * G);  // counters | verdicts: one copy out
+    const auto r_stats = r_out.part<uint32_t>(0, 16);
+    const auto r_verdict = r_out.part<int32_t>(64, G);
     hipStream_t s = h->stream;
-    std::vector<uint8_t>& head = h->verify_head;  // -g1 | point_of_row, one copy in; the handle's, so that no return frees it early
-    head.assign(256 + (point_of_row ? 4 * (size_t)n_in : 0), 0);
+    Workspace w;
+    HIP_TRY(h, w.bind(h->d_bls, L, s));
+    std::vector<uint8_t>& head = h->verify_head;  // the handle's, so that no return frees it before the copy has read it
+    head.assign(256 + por_bytes, 0);
     memcpy(head.data(), NEG_G1_BE96, 96);
-    if (point_of_row) memcpy(head.data() + 256, point_of_row, 4 * (size_t)n_in);
-    HIP_TRY(h, hipMemcpyAsync(d + o_head, head.data(), head.size(), hipMemcpyHostToDevice, s));
-    if (!msg_in_place)
-        HIP_TRY(h, hipMemcpyAsync(d + o_msg, message_points192, 192 * (size_t)n_points,
-                                  msg_kind == MemKind::Device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemsetAsync(d + o_sub, 0, 4 * (size_t)ng, s));
-    HIP_TRY(h, hipMemsetAsync(d + o_out, 0, 64, s));
+    if (point_of_row) memcpy(head.data() + 256, point_of_row, por_bytes);
+    HIP_TRY(h, w.put(r_head, head.data(), head.size()));
     BlsResidentArgs a{};
+    HIP_TRY(h, device_view(w, r_msg, msg_kind, message_points192, 192 * (size_t)n_points, &a.msg192));
+    HIP_TRY(h, w.zero(r_sub, G));
+    HIP_TRY(h, w.zero(r_stats, 16));
     a.pk_xyzz48 = kept.pk_xyzz48;
     a.sig_mont48 = kept.sig_mont48;
     a.sig_bad = kept.sig_bad;
-    a.msg192 = msg_in_place ? message_points192 : d + o_msg;
-    a.point_of_row = point_of_row ? reinterpret_cast<const uint32_t*>(d + o_por) : nullptr;
-    a.neg_g1_be96 = d + o_head;
+    a.point_of_row = point_of_row ? w(r_por) : nullptr;
+    a.neg_g1_be96 = w(r_head);
     a.grp = P.grp;
     a.union_info = P.res_info;
     a.n_groups = ng;
-    a.ws = reinterpret_cast<uint32_t*>(d + o_ws);
-    a.pair_flag = reinterpret_cast<int32_t*>(d + o_flag);
-    a.offsets = reinterpret_cast<uint32_t*>(d + o_off);
-    a.ident = reinterpret_cast<uint32_t*>(d + o_ident);
-    a.sig_status = reinterpret_cast<const int32_t*>(d + o_sub);
-    a.fe_verdict = reinterpret_cast<const int32_t*>(d + o_fe);
-    a.stats = reinterpret_cast<uint32_t*>(d + o_out);
-    a.verdict = reinterpret_cast<int32_t*>(d + o_out + 64);
+    a.ws = w(r_ws);
+    a.pair_flag = w(r_flag);
+    a.offsets = w(r_off);
+    a.ident = w(r_ident);
+    a.sig_status = w(r_sub);
+    a.fe_verdict = w(r_fe);
+    a.stats = w(r_stats);
+    a.verdict = w(r_verdict);
     a.apply = (flags & PE_VERIFY_APPLY) ? 1u : 0u;
-    uint32_t* gt = reinterpret_cast<uint32_t*>(d + o_gt);
-    int32_t* gbad = reinterpret_cast<int32_t*>(d + o_gbad);
     launch_bls_resident_prepare(s, a);
     // sums of members of G2 lie in G2: the pass runs exactly when the leg did not check its members
     const bool subgroup_pass = !rv.checked_subgroup;
-    if (subgroup_pass) launch_g2_subgroup_check(s, kept.sig_mont48, ng, reinterpret_cast<int32_t*>(d + o_sub));
-    launch_bls_miller(s, a.ws, a.pair_flag, a.offsets, ng, gt, gbad);
-    launch_bls_final_exp(s, gt, gbad, ng, reinterpret_cast<int32_t*>(d + o_fe), nullptr);
+    if (subgroup_pass) launch_g2_subgroup_check(s, kept.sig_mont48, ng, w(r_sub));
+    launch_bls_miller(s, a.ws, a.pair_flag, a.offsets, ng, w(r_gt), w(r_gbad));
+    launch_bls_final_exp(s, w(r_gt), w(r_gbad), ng, w(r_fe), nullptr);
     launch_bls_resident_settle(s, a);
     HIP_TRY(h, hipGetLastError());
-    std::vector<uint32_t> out(16 + (size_t)ng);
-    HIP_TRY(h, hipMemcpyAsync(out.data(), d + o_out, 4 * out.size(), hipMemcpyDeviceToHost, s));
+    std::vector<uint32_t> out(16 + G);
+    HIP_TRY(h, w.get(r_out, out.data(), out.size()));
     HIP_TRY(h, hipStreamSynchronize(s));
     memcpy(verdict, out.data() + 16, 4ull * ng);
     if (cap > ng) memset(verdict + ng, 0, 4ull * (cap - ng));

@@ -50,23 +50,12 @@ int pe_verify_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t n, 
 
     // ---- settle: what never enters a sum
     hipStream_t s = h->stream;
-    const bool sig_dev = mem_kind(signatures96) == MemKind::Device;
-    const uint8_t* d_in = signatures96;
-    if (!(sig_dev && (reinterpret_cast<uintptr_t>(signatures96) & 15) == 0)) {
-        HIP_TRY(h, h->d_tmp_be.ensure(std::max<size_t>(96, 96ull * n)));
-        if (n) HIP_TRY(h, hipMemcpyAsync(h->d_tmp_be.p, signatures96, 96ull * n, sig_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-        d_in = h->d_tmp_be.as<uint8_t>();
-    }
-    HIP_TRY(h, h->d_tmp_points.ensure(std::max<size_t>(256, 196ull * n)));
-    uint32_t* d_pts = h->d_tmp_points.as<uint32_t>();
-    int32_t* d_status = reinterpret_cast<int32_t*>(h->d_tmp_points.as<uint8_t>() + 192ull * n);
-    launch_g2_decompress(s, d_in, n, d_pts, nullptr, d_status);
-    launch_g2_subgroup_check(s, d_pts, n, d_status);  // always: the combination is sound over G2 only
-    launch_sv_mark_identity(s, d_pts, n, d_status, PE_SIG_STATUS_IDENTITY);
-    launch_g2_mask_bad(s, d_pts, n, d_status);
+    SettledSigs settled;  // the subgroup test always: the combination is sound over G2 only
+    PE_TRY(settle_signatures(h, signatures96, n, 0, true, true, nullptr, &settled));
+    uint32_t* const d_pts = settled.pts;
     HIP_TRY(h, hipGetLastError());
     std::vector<int32_t> row_status(n);
-    if (n) HIP_TRY(h, hipMemcpyAsync(row_status.data(), d_status, 4ull * n, hipMemcpyDeviceToHost, s));
+    if (n) HIP_TRY(h, hipMemcpyAsync(row_status.data(), settled.status, 4ull * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     auto row_of = [&](uint32_t j) { return index ? index[j] : j; };
     std::vector<int32_t> mstatus(total), mverdict(total, 0);
@@ -85,31 +74,30 @@ int pe_verify_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t n, 
     plan_g1(n_groups, size_of, gr2.data(), &plan2, G2_WG_SLOTS, G1_TARGET_LANES / 2, k);
     plan_g1(n_groups, size_of, gr1.data(), &plan1, G1_WG, G1_TARGET_LANES, k);
     for (uint32_t g = 0; g < n_groups; ++g) gr2[g].member_start = gr1[g].member_start = offsets[g];
-    const size_t gbytes = sizeof(G1Group) * (size_t)n_groups;
-    const size_t o_index = 0, o_signer = o_index + up256(4ull * total), o_scal = o_signer + up256(4ull * total),
-                 o_gr2 = o_scal + up256(8ull * total), o_gr1 = o_gr2 + up256(gbytes), o_part2 = o_gr1 + up256(gbytes),
-                 o_part1 = o_part2 + up256(384ull * plan2.n_partials), o_pk = o_part1 + up256(192ull * plan1.n_partials),
-                 o_sig = o_pk + up256(96ull * n_groups), bytes = o_sig + up256(192ull * n_groups);
-    HIP_TRY(h, h->d_verify.ensure(bytes));
-    uint8_t* d = h->d_verify.as<uint8_t>();
-    auto w32 = [&](size_t o) { return reinterpret_cast<uint32_t*>(d + o); };
-    if (total) {
-        if (index) HIP_TRY(h, hipMemcpyAsync(d + o_index, index, 4ull * total, hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(d + o_signer, signer, 4ull * total, hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(d + o_scal, weight.data(), 8ull * total, hipMemcpyHostToDevice, s));
+    Workspace w;  // d_verify, bound to each phase's layout in turn: a later phase starts over from offset 0
+    {
+        Layout L;
+        const auto r_index = L.take<uint32_t>(total), r_signer = L.take<uint32_t>(total);
+        const auto r_scal = L.take<uint64_t>(total);
+        const auto r_gr2 = L.take<G1Group>(n_groups), r_gr1 = L.take<G1Group>(n_groups);
+        const auto r_part2 = L.take<uint32_t>(96ull * plan2.n_partials), r_part1 = L.take<uint32_t>(48ull * plan1.n_partials);
+        const auto r_pk = L.take<uint8_t>(96ull * n_groups), r_sig = L.take<uint8_t>(192ull * n_groups);
+        HIP_TRY(h, w.bind(h->d_verify, L, s));
+        if (total) {
+            if (index) HIP_TRY(h, w.put(r_index, index, total));
+            HIP_TRY(h, w.put(r_signer, signer, total));
+            HIP_TRY(h, w.put(r_scal, weight.data(), total));
+        }
+        HIP_TRY(h, w.put(r_gr2, gr2.data(), n_groups));
+        HIP_TRY(h, w.put(r_gr1, gr1.data(), n_groups));
+        launch_g2_weighted_accumulate(s, d_pts, index ? w(r_index) : nullptr, w(r_scal), w(r_gr2), n_groups, plan2.n_slots, w(r_part2));
+        launch_g2_finish(s, w(r_part2), w(r_gr2), n_groups, w(r_sig));
+        launch_g1_weighted_accumulate(s, h->d_points.as<uint32_t>(), w(r_signer), w(r_scal), w(r_gr1), n_groups, plan1.n_slots, w(r_part1));
+        launch_g1_finish(s, w(r_part1), w(r_gr1), n_groups, 0, 0, w(r_pk), nullptr);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, w.get(r_pk, h->verify_sums_pk.data(), 96ull * n_groups));
+        HIP_TRY(h, w.get(r_sig, h->verify_sums_sig.data(), 192ull * n_groups));
     }
-    HIP_TRY(h, hipMemcpyAsync(d + o_gr2, gr2.data(), gbytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(d + o_gr1, gr1.data(), gbytes, hipMemcpyHostToDevice, s));
-    const uint64_t* d_scal = reinterpret_cast<const uint64_t*>(d + o_scal);
-    const G1Group* d_gr2 = reinterpret_cast<const G1Group*>(d + o_gr2);
-    const G1Group* d_gr1 = reinterpret_cast<const G1Group*>(d + o_gr1);
-    launch_g2_weighted_accumulate(s, d_pts, index ? w32(o_index) : nullptr, d_scal, d_gr2, n_groups, plan2.n_slots, w32(o_part2));
-    launch_g2_finish(s, w32(o_part2), d_gr2, n_groups, d + o_sig);
-    launch_g1_weighted_accumulate(s, h->d_points.as<uint32_t>(), w32(o_signer), d_scal, d_gr1, n_groups, plan1.n_slots, w32(o_part1));
-    launch_g1_finish(s, w32(o_part1), d_gr1, n_groups, 0, 0, d + o_pk, nullptr);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(h->verify_sums_pk.data(), d + o_pk, 96ull * n_groups, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(h->verify_sums_sig.data(), d + o_sig, 192ull * n_groups, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
 
     // ---- decide: the pairs (sum r pk, H(m_g)), (-g1, sum r sig), one group of two per committee
@@ -152,17 +140,17 @@ int pe_verify_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t n, 
             while (again[t] >= offsets[g + 1]) ++g;
             group_of[t] = g;
         }
-        const size_t o_rows = 0, o_be96 = o_rows + up256(8ull * n_again), o_be192 = o_be96 + up256(96ull * n_again),
-                     need = o_be192 + up256(192ull * n_again);
-        HIP_TRY(h, h->d_verify.ensure(need));  // (the sums' buffers are done with)
-        d = h->d_verify.as<uint8_t>();
-        HIP_TRY(h, hipMemcpyAsync(d + o_rows, rows.data(), 8ull * n_again, hipMemcpyHostToDevice, s));
-        launch_sv_rows_g1(s, h->d_points.as<uint32_t>(), w32(o_rows), n_again, d + o_be96);
-        launch_sv_rows_g2(s, d_pts, w32(o_rows) + n_again, n_again, d + o_be192);
+        Layout L;  // (the sums' regions are done with)
+        const auto r_rows = L.take<uint32_t>(2ull * n_again);
+        const auto r_be96 = L.take<uint8_t>(96ull * n_again), r_be192 = L.take<uint8_t>(192ull * n_again);
+        HIP_TRY(h, w.bind(h->d_verify, L, s));
+        HIP_TRY(h, w.put(r_rows, rows.data(), 2ull * n_again));
+        launch_sv_rows_g1(s, h->d_points.as<uint32_t>(), w(r_rows), n_again, w(r_be96));
+        launch_sv_rows_g2(s, d_pts, w(r_rows) + n_again, n_again, w(r_be192));
         HIP_TRY(h, hipGetLastError());
         std::vector<uint8_t> pk((size_t)96 * n_again), sg((size_t)192 * n_again);
-        HIP_TRY(h, hipMemcpyAsync(pk.data(), d + o_be96, 96ull * n_again, hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(sg.data(), d + o_be192, 192ull * n_again, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, w.get(r_be96, pk.data(), 96ull * n_again));
+        HIP_TRY(h, w.get(r_be192, sg.data(), 192ull * n_again));
         HIP_TRY(h, hipStreamSynchronize(s));
         std::vector<int32_t> one_by_one(n_again);
         PE_TRY(verify_pairs_run(
@@ -185,18 +173,19 @@ int pe_verify_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t n, 
         G1Plan plan;
         plan_g1(n_groups, [&](uint32_t g) { return keep_off[g + 1] - keep_off[g]; }, gr2.data(), &plan, G2_WG_SLOTS, G1_TARGET_LANES / 2);
         for (uint32_t g = 0; g < n_groups; ++g) gr2[g].member_start = keep_off[g];
-        const size_t o_keep = 0, o_g = o_keep + up256(4ull * keep.size()), o_part = o_g + up256(gbytes),
-                     o_out = o_part + up256(384ull * plan.n_partials), need = o_out + up256(192ull * n_groups);
-        HIP_TRY(h, h->d_verify.ensure(need));
-        d = h->d_verify.as<uint8_t>();
-        if (!keep.empty()) HIP_TRY(h, hipMemcpyAsync(d + o_keep, keep.data(), 4ull * keep.size(), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(d + o_g, gr2.data(), gbytes, hipMemcpyHostToDevice, s));
-        const G1Group* d_g = reinterpret_cast<const G1Group*>(d + o_g);
-        launch_g2_accumulate(s, d_pts, w32(o_keep), d_g, n_groups, plan.n_slots, w32(o_part));
-        launch_g2_finish(s, w32(o_part), d_g, n_groups, d + o_out);
+        Layout L;
+        const auto r_keep = L.take<uint32_t>(keep.size());
+        const auto r_g = L.take<G1Group>(n_groups);
+        const auto r_part = L.take<uint32_t>(96ull * plan.n_partials);
+        const auto r_out = L.take<uint8_t>(192ull * n_groups);
+        HIP_TRY(h, w.bind(h->d_verify, L, s));
+        if (!keep.empty()) HIP_TRY(h, w.put(r_keep, keep.data(), keep.size()));
+        HIP_TRY(h, w.put(r_g, gr2.data(), n_groups));
+        launch_g2_accumulate(s, d_pts, w(r_keep), w(r_g), n_groups, plan.n_slots, w(r_part));
+        launch_g2_finish(s, w(r_part), w(r_g), n_groups, w(r_out));
         HIP_TRY(h, hipGetLastError());
         std::vector<uint8_t> out192((size_t)192 * n_groups);
-        HIP_TRY(h, hipMemcpyAsync(out192.data(), d + o_out, 192ull * n_groups, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, w.get(r_out, out192.data(), 192ull * n_groups));
         HIP_TRY(h, hipStreamSynchronize(s));
         PE_TRY(pe_g2_compress(out192.data(), n_groups, out_signatures96));
     }

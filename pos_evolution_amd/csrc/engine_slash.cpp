@@ -172,18 +172,21 @@ int ingest_resident_rows(pe_engine* h, uint32_t cap_rows, uint64_t W, uint32_t f
     uint32_t nc[2];
     for (int t = 0; t < 2; ++t) nc[t] = T.t[t].valid ? T.t[t].n_committees : 0u;
     const size_t n_keys = (size_t)nc[0] + nc[1] + 1;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off = (off + bytes + 255) & ~size_t(255); return at; };
-    const size_t o_err = take(16), o_status = take(4ull * ng), o_cslot = take(4ull * ng), o_id = take(4ull * ng),
-                 o_rows = take(sizeof(SlashRow) * (size_t)ng), o_cand = take(4ull * cand), o_cnt = take(4 * n_keys),
-                 o_start = take(4 * n_keys), o_cursor = take(4 * n_keys), o_list = take(4ull * ng),
-                 o_tabs = take(2 * sizeof(SlashTable));
-    hipError_t e = sl.d_work.ensure(off);
+    Layout L;
+    const auto r_err = L.take<uint32_t>(4);
+    const auto r_status = L.take<int32_t>(ng);
+    const auto r_cslot = L.take<uint32_t>(ng), r_id = L.take<uint32_t>(ng);
+    const auto r_rows = L.take<SlashRow>(ng);
+    const auto r_cand = L.take<uint32_t>(cand);
+    const auto r_cnt = L.take<uint32_t>(n_keys), r_start = L.take<uint32_t>(n_keys), r_cursor = L.take<uint32_t>(n_keys);
+    const auto r_list = L.take<uint32_t>(ng);
+    const auto r_tabs = L.take<SlashTable>(2);
+    Workspace wk;
+    hipError_t e = wk.bind(sl.d_work, L, h->stream);
     if (e == hipSuccess && cap) e = sl.d_evidence.ensure(sizeof(pe_slash_evidence) * (size_t)cap);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, PE_ERR_OOM, "pe_slasher_ingest: scratch of the call"); }
     std::vector<uint8_t> flags_back;
     if (flags & PE_SLASH_APPLY) flags_back.resize(h->n_val);
-    uint8_t* wk = sl.d_work.as<uint8_t>();
     const uint32_t H = sl.history;
     SlashRowsArgs ra{};
     ra.rows = P.rows;
@@ -198,21 +201,21 @@ int ingest_resident_rows(pe_engine* h, uint32_t cap_rows, uint64_t W, uint32_t f
     ra.data = sl.d_data.as<uint8_t>();
     ra.count = sl.d_count.as<uint32_t>();
     ra.tab = sl.d_tab.as<uint32_t>();
-    ra.status = reinterpret_cast<int32_t*>(wk + o_status);
-    ra.err = reinterpret_cast<uint32_t*>(wk + o_err);
-    ra.cand_tab = reinterpret_cast<uint32_t*>(wk + o_cand);
+    ra.status = wk(r_status);
+    ra.err = wk(r_err);
+    ra.cand_tab = wk(r_cand);
     ra.cand_mask = cand - 1;
-    ra.cand_slot = reinterpret_cast<uint32_t*>(wk + o_cslot);
-    ra.id = reinterpret_cast<uint32_t*>(wk + o_id);
-    ra.out_rows = reinterpret_cast<SlashRow*>(wk + o_rows);
+    ra.cand_slot = wk(r_cslot);
+    ra.id = wk(r_id);
+    ra.out_rows = wk(r_rows);
 
     // ---- nothing is changed yet: the check pass (it reads no table) and its error word
     if (ng) {
         uint32_t err = 0;
-        HIP_TRY(h, hipMemsetAsync(ra.err, 0, 16, h->stream));
+        HIP_TRY(h, wk.zero(r_err, 4));
         launch_slash_rows_check(h->stream, ra);
         HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipMemcpyAsync(&err, ra.err, 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, wk.get(r_err, &err, 1));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         if (err) return fail(h, PE_ERR_INVALID_ARG, "source and target epoch must fit 32 bits");
     }
@@ -225,7 +228,7 @@ int ingest_resident_rows(pe_engine* h, uint32_t cap_rows, uint64_t W, uint32_t f
         HIP_TRY(h, hipStreamSynchronize(h->stream));  // the window's memsets
         return PE_OK;
     }
-    HIP_TRY(h, hipMemsetAsync(ra.cand_tab, 0xFF, 4ull * cand, h->stream));
+    HIP_TRY(h, wk.fill(r_cand, 0xFF, cand));
     launch_slash_rows_lookup(h->stream, ra);
     launch_slash_rows_ids(h->stream, ra);
     launch_slash_rows_emit(h->stream, ra);
@@ -234,18 +237,18 @@ int ingest_resident_rows(pe_engine* h, uint32_t cap_rows, uint64_t W, uint32_t f
     la.rows = ra.out_rows;
     la.grp = P.grp;
     la.n_groups = ng;
-    la.cnt = reinterpret_cast<uint32_t*>(wk + o_cnt);
-    la.start = reinterpret_cast<uint32_t*>(wk + o_start);
-    la.cursor = reinterpret_cast<uint32_t*>(wk + o_cursor);
+    la.cnt = wk(r_cnt);
+    la.start = wk(r_start);
+    la.cursor = wk(r_cursor);
     for (int t = 0; t < 2; ++t) {
         la.n_committees[t] = nc[t];
         if (!nc[t]) continue;
         la.table_val[la.n_tables++] = SlashTable{T.t[t].inv_comm, T.t[t].inv_pos, la.start + (t ? nc[0] : 0u)};
         if (CommitteeTable* ct = find_table(h, T.t[t].epoch)) ct->stamp = ++h->table_stamp;
     }
-    la.crow_list = reinterpret_cast<uint32_t*>(wk + o_list);
-    la.tables = reinterpret_cast<SlashTable*>(wk + o_tabs);
-    HIP_TRY(h, hipMemsetAsync(la.cnt, 0, 4 * n_keys, h->stream));
+    la.crow_list = wk(r_list);
+    la.tables = wk(r_tabs);
+    HIP_TRY(h, wk.zero(r_cnt, n_keys));
     launch_slash_rows_lists(h->stream, la);
     HIP_TRY(h, hipGetLastError());
     ka.rows = ra.out_rows;
@@ -261,7 +264,7 @@ int ingest_resident_rows(pe_engine* h, uint32_t cap_rows, uint64_t W, uint32_t f
     ka.evidence = sl.d_evidence.as<uint32_t>();
     ka.cap = cap;
     ka.flags = (flags & PE_SLASH_APPLY) ? h->d_flags.as<uint8_t>() : nullptr;
-    HIP_TRY(h, hipMemcpyAsync(status, ra.status, 4ull * ng, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, wk.get(r_status, status, ng));
     HIP_TRY(h, hipMemcpyAsync(sl.dev_count.data(), sl.d_count.p, 4ull * H, hipMemcpyDeviceToHost, h->stream));
     if (la.n_tables == 0) {  // no group had a committee: nothing to scan
         HIP_TRY(h, hipStreamSynchronize(h->stream));
