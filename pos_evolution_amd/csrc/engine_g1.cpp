@@ -70,6 +70,16 @@ int launch_g1_planned(pe_engine* h, const uint32_t* d_points, const uint32_t* d_
     // 147 KB workgroup would find no CU while accumulations follow each other, so those stores keep the old signature).
     const bool chain = fin != s && fin == h->fin_stream;
     const int exclusive = chain && h->tune.exclusive && h->blocks.size() <= 4096 ? 1 : 0;
+    // The sparse route (POSEVO_G1_SPARSE): only where a complement is passed with the unions' popcounts.  k_g1_absentees goes
+    // directly in front of the accumulation, on its stream: it reads what the accumulation reads (descriptors, verdicts, union
+    // words: all behind the row chain this stream has waited for) and writes the partials where a single-task group's
+    // accumulation lane would -- so whatever keeps that write behind the arena's previous finish keeps this one there, and the
+    // acc -> tree -> finish events order it before the finish that reads its words.  No allocation: the partials are sized above.
+    const uint32_t sparse_max = cm && cm->info ? h->tune.g1_sparse_max() : 0u;
+    const uint32_t* sparse_info = sparse_max ? cm->info : nullptr;
+    if (sparse_max)
+        launch_g1_absentees(s, d_points30, d_members, d_members1, d_bits, d_groups, plan.n_groups, plan_dev, cm->cmpl, sparse_info,
+                            sparse_max, partials->as<uint32_t>());
     {
         // Since the paired launches (round 5) the accumulations of a streaming run follow each other on their stream with
         // nothing but queue packets in between, and every packet there is step time: the two event records of a bracket cost
@@ -91,7 +101,7 @@ int launch_g1_planned(pe_engine* h, const uint32_t* d_points, const uint32_t* d_
         }
         launch_g1_accumulate(s, d_points30, d_members, d_bits, d_groups, plan.n_groups, plan.n_slots,
                              lane_partials->as<uint32_t>(), partials->as<uint32_t>(), plan_dev, d_members1, exclusive, clock_rec,
-                             cm ? cm->cmpl : nullptr);
+                             cm ? cm->cmpl : nullptr, sparse_info, sparse_max);
     }
     hipStream_t ts = fin;  // (on the accumulation's own stream the tree measured 0.433 vs 0.338 ms per step, round 3)
     if (ts != s) {
@@ -102,7 +112,7 @@ int launch_g1_planned(pe_engine* h, const uint32_t* d_points, const uint32_t* d_
         ProfScope ps(h, PE_KERNEL_G1_TREE, ts);
         launch_g1_tree(ts, lane_partials->as<uint32_t>(), d_groups, plan.n_groups, plan.n_slots, partials->as<uint32_t>(),
                        /*one_per_cu=*/ts != s ? 1 : 0,   // on its own stream it meets the next step's k_tree: leave it room
-                       plan_dev, /*solo=*/exclusive);
+                       plan_dev, /*solo=*/exclusive, sparse_max ? cm->cmpl : nullptr, sparse_info, sparse_max);
     }
     hipStream_t ns = fin;
     if (chain && h->norm_stream) {  // the finish gets a stream of its own

@@ -469,6 +469,14 @@ struct pe_engine {
         int queue_probe = env("POSEVO_QUEUE_PROBE", 1);
         // per-committee pubkey sums with every committee table, and aggregates by complement against them (0 = neither)
         int committee_sums = env("POSEVO_COMMITTEE_SUMS", 1);
+        // complement groups with few absentees go to k_g1_absentees: 0 = never (the launches of the dense
+        // complement route, unchanged), 1 = up to G1_SPARSE_MAX absentees per group; a larger value IS the threshold (at most
+        // G1_SPARSE_CAP), for measurement
+        int g1_sparse = env("POSEVO_G1_SPARSE", 1);
+        uint32_t g1_sparse_max() const
+        {
+            return g1_sparse <= 0 ? 0u : g1_sparse == 1 ? G1_SPARSE_MAX : std::min<uint32_t>((uint32_t)g1_sparse, G1_SPARSE_CAP);
+        }
         // log2 of the nodes one workgroup of k_ssz_merkle reduces per pass; for measurement
         uint32_t ssz_tile_log2 = (uint32_t)std::min<int>(SSZ_TILE_LOG2, std::max<int>(SSZ_TILE_LOG2_MIN, env("POSEVO_SSZ_TILE_LOG2", SSZ_TILE_LOG2)));
     } tune;
@@ -913,6 +921,7 @@ int build_points30(pe_engine* h, uint64_t n);  // after the registry's points ch
 // the events that mark their builds' ends (null where a table has none: its groups' verdicts are NONE32)
 struct G1Complement {
     const uint32_t* cmpl = nullptr;
+    const uint32_t* info = nullptr;  // the unions' popcounts, [2 g] (k_bits_union wrote them beside the verdicts): the sparse route's rule
     const uint32_t* sums[2] = {nullptr, nullptr};
     hipEvent_t ev[2] = {nullptr, nullptr};
 };

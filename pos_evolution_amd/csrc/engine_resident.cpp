@@ -264,7 +264,10 @@ int aggregate_resident(pe_engine* h, const pe_attestation* d_rows, uint32_t n, c
         }
     const size_t off_ocm = by_cmpl ? ob.alloc(4ull * n) : 0;
     PE_TRY(ob.ensure());
-    if (by_cmpl) cm.cmpl = L.cmpl;
+    if (by_cmpl) {
+        cm.cmpl = L.cmpl;
+        cm.info = RS.info.as<uint32_t>();  // k_bits_union's popcounts, resident beside the unions (UnionArgs::out_info)
+    }
     if (want_pk) {  // scratch of the G1 chain, sized by the bounds before anything is in flight
         PE_TRY(ensure_quiesced_arenas(h, &pe_engine::PipeArena::d_partials, std::max<size_t>(PE_G1_PARTIAL_BYTES, (size_t)PE_G1_PARTIAL_BYTES * n)));
         PE_TRY(ensure_quiesced_arenas(h, &pe_engine::PipeArena::d_lane_partials, (size_t)G1_LANE_PARTIAL_BYTES * slot_cap));

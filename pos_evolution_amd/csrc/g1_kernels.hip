@@ -10,6 +10,8 @@
 //                    registry
 //   k_g1_accumulate  HOT: per-lane XYZZ accumulation of k gathered points (mixed adds over the S30 form), one
 //                    partial per lane slot
+//   k_g1_absentees   a complement group with few absentees (g1_group_sparse): one wave scans the bits, compacts the
+//                    absentees' indices and sums them; accumulation and tree skip such a group
 //   k_g1_tree        the compacting pairwise tree over a workgroup's 256 partials staged in LDS (limb-major), one XYZZ
 //                    partial out per (group, workgroup)
 //   k_g1_finish      per group: add the few workgroup (or rank) partials, normalise
@@ -28,6 +30,7 @@
 #include "g1_s30.h"
 #include "fp_sqrt.h"
 #include "kernels.h"
+#include "wave64.h"
 
 namespace posevo {
 
@@ -276,6 +279,19 @@ __device__ __forceinline__ uint32_t find_group(const G1Group* __restrict__ group
         if (groups[mid].slot_base <= slot) lo = mid; else hi = mid;
     }
     return lo;
+}
+
+// The sparse route's verdict, one rule for every G1 kernel (k_g1_absentees sums such a group, k_g1_accumulate and k_g1_tree
+// leave it alone): the group goes by complement (cmpl[g], k_bits_union's verdict), sits inside one block, and at most
+// `sparse_max` of its members are absent -- n_members minus the union's popcount, info[2 g], which k_bits_union wrote beside
+// the verdict.  sparse_max == 0 (or no info words): no group is sparse.
+__device__ __forceinline__ bool g1_group_sparse(const G1Group& d, uint32_t g, const uint32_t* __restrict__ cmpl,
+                                                const uint32_t* __restrict__ info, uint32_t sparse_max)
+{
+    if (!cmpl || !info || sparse_max == 0) return false;
+    if (cmpl[g] == NONE32 || d.log2_block > 8 || d.bits_word == NONE32) return false;
+    const uint32_t present = info[2 * g];
+    return present <= d.n_members && d.n_members - present <= min(sparse_max, G1_SPARSE_CAP);
 }
 
 // tools/g1_phases.hip builds this file with POSEVO_G1_PHASE_TIMING to stamp the phases of one workgroup.
@@ -529,7 +545,8 @@ __device__ __forceinline__ void g1_slot_block(const G1Group* __restrict__ groups
 template <bool SOLO>
 __device__ __forceinline__ void g1_tree_body(const uint32_t* __restrict__ lane_partials, const G1Group* __restrict__ groups,
                                              uint32_t n_groups, uint32_t n_slots, uint32_t* __restrict__ wg_partials,
-                                             const AttPlan* __restrict__ plan_dev)
+                                             const AttPlan* __restrict__ plan_dev, const uint32_t* __restrict__ cmpl,
+                                             const uint32_t* __restrict__ sparse_info, uint32_t sparse_max)
 {
     if (SOLO) asm volatile("" ::: "a7");
     if (plan_dev) {
@@ -545,8 +562,10 @@ __device__ __forceinline__ void g1_tree_body(const uint32_t* __restrict__ lane_p
     const uint32_t slot = wg * G1_WG + tid;
     uint32_t my_out, my_size, t;
     G1Group d{};  // padding lanes (slot >= n_slots) read zeros, not an unwritten struct
-    g1_slot_block(groups, n_groups, n_slots, slot, my_out, my_size, d, t);
+    uint32_t g = 0;
+    g1_slot_block(groups, n_groups, n_slots, slot, my_out, my_size, d, t, &g);
     if (my_size == 1) my_size = 0;  // written by k_g1_accumulate
+    if (my_size && g1_group_sparse(d, g, cmpl, sparse_info, sparse_max)) my_size = 0;  // written by k_g1_absentees
     {
         const uint32_t* b = lane_partials + (size_t)wg * G1S_WORDS * G1_WG + tid;
 #pragma unroll
@@ -554,7 +573,8 @@ __device__ __forceinline__ void g1_tree_body(const uint32_t* __restrict__ lane_p
     }
     lds_out[tid] = my_out;
     lds_sz[tid] = my_size;
-    __syncthreads();
+    // a slab without a live block (every group of it sparse, single-task or padding): nothing to add, and nobody reads the LDS
+    if (!__syncthreads_or(my_size != 0)) continue;
     G1_STAMP(2);
 #ifdef POSEVO_G1_PHASE_TIMING
     int g1_level = 0;
@@ -689,15 +709,17 @@ __device__ __forceinline__ void g1_tree_body(const uint32_t* __restrict__ lane_p
 
 __global__ void __launch_bounds__(G1_WG) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_g1_tree(const uint32_t* __restrict__ lane_partials, const G1Group* __restrict__ groups, uint32_t n_groups,
-          uint32_t n_slots, uint32_t* __restrict__ wg_partials, const AttPlan* __restrict__ plan_dev)
+          uint32_t n_slots, uint32_t* __restrict__ wg_partials, const AttPlan* __restrict__ plan_dev,
+          const uint32_t* __restrict__ cmpl, const uint32_t* __restrict__ sparse_info, uint32_t sparse_max)
 {
-    s30::g1_tree_body<false>(lane_partials, groups, n_groups, n_slots, wg_partials, plan_dev);
+    s30::g1_tree_body<false>(lane_partials, groups, n_groups, n_slots, wg_partials, plan_dev, cmpl, sparse_info, sparse_max);
 }
 __global__ void __launch_bounds__(G1_WG) __attribute__((amdgpu_waves_per_eu(1, 1), amdgpu_num_vgpr(256)))
 k_g1_tree_solo(const uint32_t* __restrict__ lane_partials, const G1Group* __restrict__ groups, uint32_t n_groups,
-               uint32_t n_slots, uint32_t* __restrict__ wg_partials, const AttPlan* __restrict__ plan_dev)
+               uint32_t n_slots, uint32_t* __restrict__ wg_partials, const AttPlan* __restrict__ plan_dev,
+               const uint32_t* __restrict__ cmpl, const uint32_t* __restrict__ sparse_info, uint32_t sparse_max)
 {
-    s30::g1_tree_body<true>(lane_partials, groups, n_groups, n_slots, wg_partials, plan_dev);
+    s30::g1_tree_body<true>(lane_partials, groups, n_groups, n_slots, wg_partials, plan_dev, cmpl, sparse_info, sparse_max);
 }
 
 // ---------------------------------------------------------------- the accumulation (S30 field form)
@@ -771,7 +793,8 @@ __device__ __forceinline__ void g1_accumulate_body(const uint32_t* __restrict__ 
                                                    uint32_t* __restrict__ wg_partials, const AttPlan* __restrict__ plan_dev,
                                                    const uint32_t* __restrict__ members1,
                                                    unsigned long long* __restrict__ clock_rec,
-                                                   const uint32_t* __restrict__ cmpl)
+                                                   const uint32_t* __restrict__ cmpl,
+                                                   const uint32_t* __restrict__ sparse_info, uint32_t sparse_max)
 {
     const int tid = threadIdx.x;
     if (plan_dev) {
@@ -808,6 +831,11 @@ __device__ __forceinline__ void g1_accumulate_body(const uint32_t* __restrict__ 
         first = t * gk;
         count = min(gk, d.n_members - first);
         if (cmpl) invert = cmpl[g] != NONE32 ? 1u : 0u;
+        // k_g1_absentees sums a sparse group: no loads, no adds here, and nothing for a single-task group's own hand-over
+        if (invert && g1_group_sparse(d, g, cmpl, sparse_info, sparse_max)) {
+            count = 0;
+            my_size = 0;
+        }
     }
     // Two loads deep: while point j is added, the row of point j + 1 is in flight (its index arrived an iteration ago) and
     // so are the index and the bit word of point j + 2 -- the wave never waits for an address it needs at once.  (One
@@ -894,10 +922,11 @@ k_g1_accumulate(const uint32_t* __restrict__ pts30, const uint32_t* __restrict__
                 const uint32_t* __restrict__ bit_arena, const G1Group* __restrict__ groups, uint32_t n_groups,
                 uint32_t n_slots, uint32_t* __restrict__ lane_partials, uint32_t* __restrict__ wg_partials,
                 const AttPlan* __restrict__ plan_dev, const uint32_t* __restrict__ members1,
-                unsigned long long* __restrict__ clock_rec, const uint32_t* __restrict__ cmpl)
+                unsigned long long* __restrict__ clock_rec, const uint32_t* __restrict__ cmpl,
+                const uint32_t* __restrict__ sparse_info, uint32_t sparse_max)
 {
     s30::g1_accumulate_body(pts30, members, bit_arena, groups, n_groups, n_slots, lane_partials, wg_partials, plan_dev,
-                            members1, clock_rec, cmpl);
+                            members1, clock_rec, cmpl, sparse_info, sparse_max);
 }
 
 void launch_g1_table_s30(hipStream_t s, const uint32_t* points_mont24, uint32_t* points_s30, uint64_t n)
@@ -908,7 +937,8 @@ void launch_g1_table_s30(hipStream_t s, const uint32_t* points_mont24, uint32_t*
 void launch_g1_accumulate(hipStream_t s, const uint32_t* points_s30, const uint32_t* members,
                               const uint32_t* bit_arena, const G1Group* groups, uint32_t n_groups, uint32_t n_slots,
                               uint32_t* lane_partials, uint32_t* wg_partials48, const AttPlan* plan_dev,
-                              const uint32_t* members1, int exclusive, unsigned long long* clock_rec, const uint32_t* cmpl)
+                              const uint32_t* members1, int exclusive, unsigned long long* clock_rec, const uint32_t* cmpl,
+                              const uint32_t* sparse_info, uint32_t sparse_max)
 {
     if (n_groups == 0 || n_slots == 0) return;
     const unsigned blocks = (n_slots + G1_WG - 1) / G1_WG;
@@ -927,7 +957,8 @@ void launch_g1_accumulate(hipStream_t s, const uint32_t* points_s30, const uint3
                                       (int)G1_ACC_EXCLUSIVE_LDS);
     }
     hipLaunchKernelGGL(k_g1_accumulate, dim3(blocks), dim3(G1_WG), lds_bytes, s, points_s30, members, bit_arena,
-                       groups, n_groups, n_slots, lane_partials, wg_partials48, plan_dev, members1, clock_rec, cmpl);
+                       groups, n_groups, n_slots, lane_partials, wg_partials48, plan_dev, members1, clock_rec, cmpl, sparse_info,
+                       sparse_max);
 }
 
 // one_per_cu (the tree of a streaming step, on its own stream): ask for 84 KB of LDS instead of the 54 KB the kernel uses,
@@ -951,7 +982,8 @@ void launch_g1_accumulate(hipStream_t s, const uint32_t* points_s30, const uint3
 //    only made rarer (6 steps of 20 at 340-370 us on one box, profiles/r05_engine_timeline_cold20_before_exclusive.txt); this kernel then
 //    keeps its workgroups apart by registers instead (k_g1_tree_solo: more than 256 registers) and asks for the 54 KB it uses.
 void launch_g1_tree(hipStream_t s, const uint32_t* lane_partials, const G1Group* groups, uint32_t n_groups,
-                    uint32_t n_slots, uint32_t* wg_partials48, int one_per_cu, const AttPlan* plan_dev, int solo)
+                    uint32_t n_slots, uint32_t* wg_partials48, int one_per_cu, const AttPlan* plan_dev, int solo,
+                    const uint32_t* cmpl, const uint32_t* sparse_info, uint32_t sparse_max)
 {
     if (n_groups == 0 || n_slots == 0) return;
     const unsigned blocks = (n_slots + G1_WG - 1) / G1_WG;
@@ -960,7 +992,7 @@ void launch_g1_tree(hipStream_t s, const uint32_t* lane_partials, const G1Group*
         // beside an accumulation that asks for G1_ACC_EXCLUSIVE_LDS: one workgroup per CU by registers (264), the LDS request
         // is what the kernel uses (54 KB)
         hipLaunchKernelGGL(k_g1_tree_solo, dim3(blocks), dim3(G1_WG), lds_bytes, s, lane_partials, groups, n_groups, n_slots,
-                           wg_partials48, plan_dev);
+                           wg_partials48, plan_dev, cmpl, sparse_info, sparse_max);
         return;
     }
     if (one_per_cu) {
@@ -971,7 +1003,128 @@ void launch_g1_tree(hipStream_t s, const uint32_t* lane_partials, const G1Group*
         lds_bytes = padded;
     }
     hipLaunchKernelGGL(k_g1_tree, dim3(blocks), dim3(G1_WG), lds_bytes, s, lane_partials, groups, n_groups, n_slots,
-                       wg_partials48, plan_dev);
+                       wg_partials48, plan_dev, cmpl, sparse_info, sparse_max);
+}
+
+// ---------------------------------------------------------------- the absentees of a sparse group
+// A committee of 512 in which 99 % attest has ~5 absentees: a 16-word bit scan and 4 additions, for which the dense chain
+// walks 16 members in each of 32 lanes and climbs an 8-level tree.  One wave per group here (a workgroup IS one wave: the
+// barrier below orders the wave's own LDS traffic only):
+//   1. the lanes stride the union's words (tail word masked by n_members, as k_bits_union does), count their zero bits, rank
+//      them by a wave scan and write the absent members' indices into one list in LDS;
+//   2. lane l takes entries l, l + 64, ...: the first becomes its accumulator as it is, further ones (more than 64 absentees)
+//      are added by the complete affine add over called products -- every case of the group law in place, no filter, no redo;
+//   3. the live lanes -- the first min(n, 64), contiguous by construction -- are added pairwise, lane l += lane l + off, with
+//      the complete XYZZ add; a level without a live pair is skipped (the test is on the count: wave-uniform);
+//   4. lanes 0..3 convert one coordinate each to the 12 x 32 words k_g1_finish reads, at wg_partials[out_base]: the hand-over
+//      of k_g1_accumulate's single-task groups.  No absentee: all-zero words, infinity.
+// The limbs travel between lanes by shuffles; the LDS holds the list alone.
+namespace s30 {
+__device__ __forceinline__ void g1q_from_lane_down(g1q& q, const g1q& p, int off)  // q = p of lane + off
+{
+#pragma unroll
+    for (int j = 0; j < FQ_N; ++j) {
+        q.x.l[j] = __shfl_down(p.x.l[j], off, 64);
+        q.y.l[j] = __shfl_down(p.y.l[j], off, 64);
+        q.zz.l[j] = __shfl_down(p.zz.l[j], off, 64);
+        q.zzz.l[j] = __shfl_down(p.zzz.l[j], off, 64);
+    }
+    q.inf = __shfl_down((int)p.inf, off, 64) != 0;
+    q.affine = false;  // zz = zzz = one are held, which is all g1q_add reads
+}
+__device__ __forceinline__ void g1_absentees_body(const uint32_t* __restrict__ pts30, const uint32_t* __restrict__ members,
+                                                  const uint32_t* __restrict__ members1,
+                                                  const uint32_t* __restrict__ bit_arena, const G1Group* __restrict__ groups,
+                                                  uint32_t n_groups, const AttPlan* __restrict__ plan_dev,
+                                                  const uint32_t* __restrict__ cmpl,
+                                                  const uint32_t* __restrict__ sparse_info, uint32_t sparse_max,
+                                                  uint32_t* __restrict__ wg_partials)
+{
+    __shared__ uint32_t list[G1_SPARSE_CAP];
+    if (plan_dev) n_groups = min(n_groups, plan_dev->n_groups);
+    const uint32_t g = blockIdx.x;
+    if (g >= n_groups) return;
+    const G1Group d = groups[g];
+    if (!g1_group_sparse(d, g, cmpl, sparse_info, sparse_max)) return;  // workgroup-uniform
+    const uint32_t lane = threadIdx.x;
+    const uint32_t n_words = (d.n_members + 31) >> 5;
+    const uint32_t tail_mask = (d.n_members & 31) ? ((1u << (d.n_members & 31)) - 1u) : 0xFFFFFFFFu;
+    uint32_t total = 0;  // absentees so far: the same in every lane
+    for (uint32_t w0 = 0; w0 < n_words; w0 += 64) {
+        const uint32_t w = w0 + lane;
+        uint32_t absent = 0;
+        if (w < n_words) absent = ~bit_arena[d.bits_word + w] & (w == n_words - 1 ? tail_mask : 0xFFFFFFFFu);
+        const uint32_t mine = (uint32_t)__builtin_popcount(absent);
+        uint32_t pos = total + wave_incl_scan(mine) - mine;
+        while (absent) {
+            if (pos < G1_SPARSE_CAP) list[pos] = 32u * w + (uint32_t)__builtin_ctz(absent);
+            ++pos;
+            absent &= absent - 1;
+        }
+        total += wave_sum(mine);
+    }
+    total = min(total, G1_SPARSE_CAP);  // (the verdict promises it: n_members - popcount <= sparse_max <= G1_SPARSE_CAP)
+    __syncthreads();
+    const uint32_t* __restrict__ mem = (d.k >> 31) ? members1 : members;
+    g1q acc;
+    g1q_set_inf(acc);
+    for (uint32_t e = lane; e < total; e += 64) {
+        const uint32_t i = list[e];
+        const uint32_t idx = mem ? mem[d.member_start + i] : d.member_start + i;
+        fq qx, qy;
+        const bool have = load_point_s30(qx, qy, pts30, idx);
+        g1q_add_affine<FqCalled>(acc, qx, qy, !have);
+    }
+    uint32_t live = min(total, 64u);
+#pragma nounroll
+    for (uint32_t off = 32; off >= 1; off >>= 1) {
+        if (live <= off) continue;
+        g1q q;
+        g1q_from_lane_down(q, acc, (int)off);
+        if (lane < off && lane + off < live) g1q_add<FqCalled>(acc, q);
+        live = off;
+    }
+    // lane c < 4 takes coordinate c of lane 0's sum
+    fq coord;
+#pragma unroll
+    for (int j = 0; j < FQ_N; ++j) {
+        const int32_t x = __shfl(acc.x.l[j], 0, 64), y = __shfl(acc.y.l[j], 0, 64);
+        const int32_t zz = __shfl(acc.zz.l[j], 0, 64), zzz = __shfl(acc.zzz.l[j], 0, 64);
+        coord.l[j] = lane == 0 ? x : lane == 1 ? y : lane == 2 ? zz : zzz;
+    }
+    const bool inf = __shfl((int)acc.inf, 0, 64) != 0;
+    if (lane < 4) {
+        uint32_t w[12];
+        fq_to_mont32_via<FqCalled>(w, coord);
+        uint4* dst = reinterpret_cast<uint4*>(wg_partials + (size_t)G1X_WORDS * d.out_base + 12 * lane);
+        dst[0] = inf ? make_uint4(0, 0, 0, 0) : make_uint4(w[0], w[1], w[2], w[3]);
+        dst[1] = inf ? make_uint4(0, 0, 0, 0) : make_uint4(w[4], w[5], w[6], w[7]);
+        dst[2] = inf ? make_uint4(0, 0, 0, 0) : make_uint4(w[8], w[9], w[10], w[11]);
+    }
+}
+}  // namespace s30
+
+// Registers: both operands of the complete add live in registers (104) beside a called product's arguments and result (39)
+// -- 215 in all, no scratch; held to 128 the allocator spills 384 bytes per lane.  Two waves fit a SIMD, which is what a
+// step's 2048 groups ask of 1024 SIMDs; the wave priority is not raised.
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 8)))
+k_g1_absentees(const uint32_t* __restrict__ pts30, const uint32_t* __restrict__ members,
+               const uint32_t* __restrict__ members1, const uint32_t* __restrict__ bit_arena,
+               const G1Group* __restrict__ groups, uint32_t n_groups, const AttPlan* __restrict__ plan_dev,
+               const uint32_t* __restrict__ cmpl, const uint32_t* __restrict__ sparse_info, uint32_t sparse_max,
+               uint32_t* __restrict__ wg_partials)
+{
+    s30::g1_absentees_body(pts30, members, members1, bit_arena, groups, n_groups, plan_dev, cmpl, sparse_info, sparse_max,
+                           wg_partials);
+}
+
+void launch_g1_absentees(hipStream_t s, const uint32_t* points_s30, const uint32_t* members, const uint32_t* members1,
+                         const uint32_t* bit_arena, const G1Group* groups, uint32_t n_groups, const AttPlan* plan_dev,
+                         const uint32_t* cmpl, const uint32_t* sparse_info, uint32_t sparse_max, uint32_t* wg_partials48)
+{
+    if (n_groups == 0 || !cmpl || !sparse_info || sparse_max == 0) return;
+    hipLaunchKernelGGL(k_g1_absentees, dim3(n_groups), dim3(64), 0, s, points_s30, members, members1, bit_arena, groups,
+                       n_groups, plan_dev, cmpl, sparse_info, sparse_max, wg_partials48);
 }
 
 // ---------------------------------------------------------------- finish

@@ -61,20 +61,33 @@ void launch_g1_accumulate(hipStream_t s, const uint32_t* points_s30, const uint3
                           const uint32_t* bit_arena, const G1Group* groups, uint32_t n_groups, uint32_t n_slots,
                           uint32_t* lane_partials, uint32_t* wg_partials48, const AttPlan* plan_dev = nullptr,
                           const uint32_t* members1 = nullptr, int exclusive = 0, unsigned long long* clock_rec = nullptr,
-                          const uint32_t* cmpl = nullptr);
+                          const uint32_t* cmpl = nullptr, const uint32_t* sparse_info = nullptr, uint32_t sparse_max = 0);
 // cmpl (nullable): one word per group, written by k_bits_union (UnionArgs::cmpl): NONE32 = the group is summed directly, else
 // committee id | candidate table << 31 = the group goes by complement: the accumulation sums the members whose bit is NOT set,
 // and k_g1_finish subtracts that from the committee's sum (sums0 / sums1: the candidate tables' per-committee XYZZ sums, 48
 // words each, built with the table -- launch_g1_committee_groups + the accumulation + the tree).
 void launch_g1_committee_groups(hipStream_t s, const uint32_t* offsets, uint32_t n_committees, uint32_t k, uint32_t log2_block,
                                 G1Group* groups);
+// The sparse route of the complement: a group that goes by complement, sits inside one block and has at most sparse_max
+// absentees (n_members - sparse_info[2 g], the union's popcount as k_bits_union wrote it beside the verdict) is summed by
+// k_g1_absentees -- one wave per group: bit scan, compacted index list, a handful of complete adds -- into
+// wg_partials48[out_base], the words k_g1_finish reads; k_g1_accumulate and k_g1_tree evaluate the same rule and leave such a
+// group alone (sparse_info null or sparse_max 0: no group is sparse, and the three kernels do what they did without the
+// route).  The grid covers the upper bound n_groups, like k_g1_finish's.  G1_SPARSE_MAX: the default threshold, a measured
+// choice (profiles/NOTES_r17.md); G1_SPARSE_CAP: the most a launch may ask for (the kernel's index list).
+constexpr uint32_t G1_SPARSE_MAX = 128;
+constexpr uint32_t G1_SPARSE_CAP = 256;
+void launch_g1_absentees(hipStream_t s, const uint32_t* points_s30, const uint32_t* members, const uint32_t* members1,
+                         const uint32_t* bit_arena, const G1Group* groups, uint32_t n_groups, const AttPlan* plan_dev,
+                         const uint32_t* cmpl, const uint32_t* sparse_info, uint32_t sparse_max, uint32_t* wg_partials48);
 // exclusive: the launch asks for this much LDS it never touches (more than half a CU's): at most one of its workgroups per CU
 constexpr size_t G1_ACC_EXCLUSIVE_LDS = 82 * 1024;
 // The compacting LDS tree over each workgroup's 256 lane partials: one 48-u32 XYZZ partial (192 bytes) per
 // (group, workgroup) into wg_partials48.
 void launch_g1_tree(hipStream_t s, const uint32_t* lane_partials, const G1Group* groups, uint32_t n_groups,
                     uint32_t n_slots, uint32_t* wg_partials48, int one_per_cu = 0, const AttPlan* plan_dev = nullptr,
-                    int solo = 0);
+                    int solo = 0, const uint32_t* cmpl = nullptr, const uint32_t* sparse_info = nullptr,
+                    uint32_t sparse_max = 0);
 // Per group: add its n_parts partials (stride = part_stride partials apart, starting at first[g] or
 // g when first == null), then either write the XYZZ sum (48 u32) or normalise to 96-byte affine.
 void launch_g1_finish(hipStream_t s, const uint32_t* partials48, const G1Group* groups, uint32_t n_groups,
