@@ -2,10 +2,11 @@
 // validator) as an argument, with the helpers and constants they need and the host helpers that size their grids.
 // Included at file scope by att_kernels.hip, which wraps each body in a __global__ kernel of its own and launches it, and by
 // pair_kernels.hip, which runs the same bodies as block ranges of the paired launches: one text, so the two forms cannot
-// differ.  Like fp381_lazy.inc it has no include guard; unlike it, it opens namespace posevo itself.  No __global__
-// function, no launcher and no __device__ variable belongs here.
+// differ.  Which status a row gets is att_rules.h, one text with the host routes: the bodies supply the data.  Like
+// fp381_lazy.inc it has no include guard; unlike it, it opens namespace posevo itself.  No __global__ function, no launcher
+// and no __device__ variable belongs here.
 #include <algorithm>
-#include "att_row.h"
+#include "att_rules.h"
 #include "kernels.h"
 #include "wave64.h"
 
@@ -14,12 +15,7 @@ namespace posevo {
 namespace {
 
 constexpr uint32_t VAL_EQUIVOCATING_BIT = 0x04u;
-constexpr uint32_t FLAG_SIG_VALID = 0x1u, FLAG_FROM_BLOCK = 0x2u, FLAG_OVERLAPPING = 0x4u;  // PE_ATT_FLAG_* of include/posevo.h
-// pe_att_status values (include/posevo.h)
-constexpr int32_t ST_OK = 0, ST_EPOCH_TIME = 1, ST_EPOCH_SLOT = 2, ST_UNKNOWN_TARGET = 3, ST_UNKNOWN_BLOCK = 4,
-                  ST_BLOCK_AFTER_SLOT = 5, ST_TARGET_NOT_ANCESTOR = 6, ST_SLOT_NOT_PAST = 7, ST_NO_TABLE = 8,
-                  ST_INDEX_RANGE = 9, ST_BITS_LENGTH = 10, ST_EMPTY = 11, ST_BAD_SIGNATURE = 12, ST_INCLUSION = 13,
-                  ST_SOURCE = 14;
+// (the pe_att_status values ST_* and the row flags FLAG_* are att_rules.h's)
 // -pe_status values reported through AttPlan::error
 constexpr uint32_t ERR_INVALID_ARG = 1, ERR_CAPACITY = 10, ERR_NO_COMMITTEES = 11;
 
@@ -198,23 +194,22 @@ __device__ __forceinline__ void att_plan_body(const uint32_t bid, const uint32_t
     const unsigned long long spe = a.tables.slots_per_epoch;
     const unsigned long long slot_no = u64_of(q0.x, q0.y), index = u64_of(q0.z, q0.w), tep = u64_of(q5.z, q5.w);
     const uint32_t nbits = q8.y;
-    uint32_t size = 0, table = NONE32, pos = 0, mbase = 0, index_over = 0;
-    int32_t st = ST_OK;
+    uint32_t size = 0, table = NONE32, pos = 0, mbase = 0;
     if (a.tables.t[0].valid && a.tables.t[0].epoch == tep) table = 0;
     else if (a.tables.t[1].valid && a.tables.t[1].epoch == tep) table = 1;
-    if (table == NONE32) st = ST_NO_TABLE;
-    else if (in) {
+    CommitteePos cp{0, false, false};
+    if (table != NONE32 && in) {
         const TableDev& t = a.tables.t[table];
-        const CommitteePos cp = att_committee_pos(t.n_committees, spe, slot_no, index);  // (att_row.h: who requires what)
-        index_over = cp.index_over ? 1u : 0u;
-        if (!cp.exists) st = ST_INDEX_RANGE;
-        else {
+        cp = att_committee_pos(t.n_committees, spe, slot_no, index);
+        if (cp.exists) {
             pos = cp.pos;
             mbase = t.offsets[pos];
             size = t.offsets[pos + 1] - mbase;
-            if (nbits != size) st = ST_BITS_LENGTH;  // len(aggregation_bits) == len(committee), pe:730
         }
     }
+    // the fork choice's reading over resident bits; k_att_validate_state adds pe:727 from index_over (att_rules.h)
+    const int32_t st = att_committee_status(table != NONE32, cp, nbits, size, ATT_FC_RESIDENT_BITS);
+    const uint32_t index_over = cp.index_over ? 1u : 0u;
     if (in) a.rep_of[i] = rep;
     const bool is_rep = in && rep == i && !dead;
     const bool ok = is_rep && st == ST_OK;
@@ -339,7 +334,8 @@ __device__ __forceinline__ void att_plan_body(const uint32_t bid, const uint32_t
     // sums / maxima over all groups: one atomic per wave and value that has something to say
     {
         // the host path fails the whole aggregate on a group without a committee when pubkeys are wanted (engine_attest.cpp)
-        const uint32_t e = (is_rep && (st != ST_OK || index_over) && a.want_pk) ? (st == ST_NO_TABLE ? ERR_NO_COMMITTEES : ERR_INVALID_ARG) : 0u;
+        const int32_t st_pk = att_committee_state_status(st, index_over != 0);  // pe_aggregate asks what pe:727-730 ask
+        const uint32_t e = (is_rep && st_pk != ST_OK && a.want_pk) ? (st_pk == ST_NO_TABLE ? ERR_NO_COMMITTEES : ERR_INVALID_ARG) : 0u;
         const uint32_t w_err = wave_max(e);
         const uint32_t w_size = wave_max(ok ? size : 0u);
         // word layout == byte layout as long as every union but the LAST one is a whole number of words: remember the first
@@ -520,6 +516,21 @@ __device__ __forceinline__ uint32_t find_block_dev(const BlockTableDev& bt, cons
         h = (h + 1) & bt.root_mask;
     }
 }
+// the store adapter of att_fork_choice_status (att_rules.h) over the device block table: blocks by insertion index, the
+// walk over pre-order positions (slots strictly increase along parent links)
+struct Root2 { uint4 lo, hi; };
+struct BlockStoreDev {
+    const BlockTableDev& bt;
+    __device__ __forceinline__ uint32_t find(const Root2& r) const { return find_block_dev(bt, r.lo, r.hi); }
+    __device__ __forceinline__ uint32_t handle(uint32_t idx) const { return bt.pos_of_idx[idx]; }
+    __device__ __forceinline__ unsigned long long slot_of(uint32_t idx) const { return bt.slot_pos[bt.pos_of_idx[idx]]; }
+    __device__ __forceinline__ uint32_t ancestor(uint32_t idx, unsigned long long slot) const
+    {
+        uint32_t p = bt.pos_of_idx[idx];
+        while (bt.slot_pos[p] > slot && bt.parent_pos[p] != NONE32) p = bt.parent_pos[p];
+        return p;
+    }
+};
 }  // namespace
 
 // ------------------------------------------------------------------ validate_on_attestation (A.4) per group
@@ -549,53 +560,13 @@ __device__ __forceinline__ void att_validate_fc_body(const uint32_t g /* group o
     Row9 r;
     load_row(r, rows, G.rep);
     const unsigned long long slot = row_slot(r), tep = row_target_epoch(r), spe = fc.slots_per_epoch;
-    const uint32_t flags = r.q[8].z;
-    int32_t st = ST_OK;
-    uint32_t blk = NONE32;
-    // validate_target_epoch_against_current_time (skipped for attestations from blocks, pe:1423)
-    if (!(flags & FLAG_FROM_BLOCK) && tep != fc.cur_epoch && tep != fc.prev_epoch) st = ST_EPOCH_TIME;
-    else if (tep != slot / spe) st = ST_EPOCH_SLOT;
-    else {
-        const uint32_t tgt = find_block_dev(bt, r.q[6], r.q[7]);
-        if (tgt == NONE32) st = ST_UNKNOWN_TARGET;
-        else {
-            blk = find_block_dev(bt, r.q[1], r.q[2]);
-            if (blk == NONE32) st = ST_UNKNOWN_BLOCK;
-            else {
-                uint32_t p = bt.pos_of_idx[blk];
-                if (bt.slot_pos[p] > slot) st = ST_BLOCK_AFTER_SLOT;
-                else {
-                    // get_ancestor(store, beacon_block_root, compute_start_slot_at_epoch(target.epoch)) (A.2): the
-                    // block's slot is <= data.slot and the epoch is data.slot's, so the walk is at most
-                    // SLOTS_PER_EPOCH parent steps (slots strictly increase along parent links)
-                    const unsigned long long start = tep * spe;
-                    while (bt.slot_pos[p] > start && bt.parent_pos[p] != NONE32) p = bt.parent_pos[p];
-                    if (p != bt.pos_of_idx[tgt]) st = ST_TARGET_NOT_ANCESTOR;
-                    else if (fc.cur_slot < slot + 1) st = ST_SLOT_NOT_PAST;
-                }
-            }
-        }
-    }
-    if (st == ST_OK && G.status_agg) st = (int32_t)G.status_agg;  // committee resolution: table, index, bits length
-    // is_valid_indexed_attestation (A.7): the signature verdict, then what the OR-ed bits say (overlap, emptiness)
+    const FcVerdict v = att_fork_choice_status(BlockStoreDev{bt}, (r.q[8].z & FLAG_FROM_BLOCK) != 0, slot, tep, Root2{r.q[6], r.q[7]},
+                                               Root2{r.q[1], r.q[2]}, fc.cur_slot, fc.cur_epoch, fc.prev_epoch, spe);
+    int32_t st = v.status;
+    if (st == ST_OK) st = (int32_t)G.status_agg;  // the committee, as k_att_plan resolved it
     const uint32_t cnt = union_info[2 * g], overlap = union_info[2 * g + 1];
-    if (st == ST_OK) {
-        if (!G.sig_valid) st = ST_BAD_SIGNATURE;
-        else if (overlap) st = ST_BAD_SIGNATURE;
-        else if (cnt == 0) st = ST_EMPTY;
-    }
-    AttRow o;
-    o.member_base = G.member_base;
-    o.n_bits = G.size;
-    o.bits_word = G.out_word;
-    o.block_idx = blk;
-    o.epoch_p1 = (uint32_t)tep + 1;
-    o.order = g;
-    o.flag_mask = 0;
-    o.which = 0;
-    o.slot = (uint32_t)slot;
-    o.gate = g;
-    out_rows[g] = o;
+    if (st == ST_OK) st = att_indexed_status(G.sig_valid != 0, overlap != 0, cnt);
+    out_rows[g] = att_row_fork_choice(G.member_base, G.size, G.out_word, v.block, tep, slot, g, g);
     status_dev[g] = st;
     status_host[g] = st;
     if (count_host) count_host[g] = st == ST_OK ? cnt : 0u;

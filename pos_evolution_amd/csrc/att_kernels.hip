@@ -19,6 +19,7 @@
 //                         pe_att_status per group.
 //   k_att_validate_state  the asserts of process_attestation (pe:724-730) and
 //                         get_attestation_participation_flag_indices (A.9) per group.
+//                         (Both validators ask att_rules.h for the status: one text with the host routes.)
 //   k_lmd_vm_tables       update_latest_messages (pe:1435-1441), validator-major, both candidate tables in one launch.
 //   k_participation_tables the flag loop of pe:745-749, one wave per committee, rows of a committee in batch order.
 //
@@ -185,6 +186,34 @@ __device__ __forceinline__ bool root_equals(const uint8_t* root32, const uint4& 
     return w[0] == r0.x && w[1] == r0.y && w[2] == r0.z && w[3] == r0.w && w[4] == r1.x && w[5] == r1.y && w[6] == r1.z &&
            w[7] == r1.w;
 }
+// the row adapter of att_state_status (att_rules.h): the committee as k_att_plan resolved it, the source against the
+// justified checkpoint of the row's epoch, and the block roots of the state's chain the host resolved (StateCtxDev)
+struct StateRowDev {
+    const Row9& r;
+    const AttGroup& G;
+    const BlockTableDev& bt;
+    const StateCtxDev& S;
+    const bool is_cur;
+    const unsigned long long slot;
+    __device__ __forceinline__ int32_t committee_status() const { return (int32_t)G.status_agg; }
+    __device__ __forceinline__ bool index_over() const { return G.index_over != 0; }
+    __device__ __forceinline__ bool source_matches() const
+    {
+        const uint4 s0 = make_uint4(r.q[3].z, r.q[3].w, r.q[4].x, r.q[4].y), s1 = make_uint4(r.q[4].z, r.q[4].w, r.q[5].x, r.q[5].y);
+        return row_source_epoch(r) == (is_cur ? S.cj_epoch : S.pj_epoch) && root_equals(is_cur ? S.cj_root : S.pj_root, s0, s1);
+    }
+    __device__ __forceinline__ bool matching_target() const
+    {
+        const uint32_t tgt_blk = S.tgt_blk[is_cur ? 0 : 1];
+        return tgt_blk != NONE32 && root_equals(bt.roots + 32ull * tgt_blk, r.q[6], r.q[7]);
+    }
+    __device__ __forceinline__ bool matching_head() const
+    {
+        const unsigned long long j = slot + S.slots_per_epoch - S.slot;  // pe:726 puts data.slot into [state.slot - spe, state.slot)
+        const uint32_t head_blk = j < 64 ? S.head_blk[j] : NONE32;
+        return head_blk != NONE32 && root_equals(bt.roots + 32ull * head_blk, r.q[1], r.q[2]);
+    }
+};
 }  // namespace
 __global__ void __launch_bounds__(256)
 k_att_validate_state(const uint4* __restrict__ rows, const AttGroup* __restrict__ grp, const AttPlan* __restrict__ plan,
@@ -203,53 +232,14 @@ k_att_validate_state(const uint4* __restrict__ rows, const AttGroup* __restrict_
     const AttGroup G = grp[g];
     Row9 r;
     load_row(r, rows, G.rep);
-    const unsigned long long slot = row_slot(r), tep = row_target_epoch(r), spe = S.slots_per_epoch;
-    int32_t st = ST_OK;
-    uint32_t flag_mask = 0;
-    if (tep != S.prev_epoch && tep != S.cur_epoch) st = ST_EPOCH_TIME;                                   // pe:724
-    else if (tep != slot / spe) st = ST_EPOCH_SLOT;                                                       // pe:725
-    else if (!(slot + S.min_inclusion_delay <= S.slot && S.slot <= slot + spe)) st = ST_INCLUSION;        // pe:726
-    else if (G.status_agg == (uint32_t)ST_NO_TABLE) st = ST_NO_TABLE;
-    else if (G.index_over) st = ST_INDEX_RANGE;                                                           // pe:727
-    else if (G.status_agg) st = (int32_t)G.status_agg;                                                    // pe:729-730
-    else {
-        // get_attestation_participation_flag_indices (A.9)
-        const bool is_cur = tep == S.cur_epoch;
-        const unsigned long long j_epoch = is_cur ? S.cj_epoch : S.pj_epoch;
-        const uint8_t* j_root = is_cur ? S.cj_root : S.pj_root;
-        const uint4 s0 = make_uint4(r.q[3].z, r.q[3].w, r.q[4].x, r.q[4].y), s1 = make_uint4(r.q[4].z, r.q[4].w, r.q[5].x, r.q[5].y);
-        if (row_source_epoch(r) != j_epoch || !root_equals(j_root, s0, s1)) st = ST_SOURCE;  // assert is_matching_source
-        else {
-            const uint32_t tgt_blk = S.tgt_blk[is_cur ? 0 : 1];
-            const bool matching_target = tgt_blk != NONE32 && root_equals(bt.roots + 32ull * tgt_blk, r.q[6], r.q[7]);
-            const unsigned long long j = slot + spe - S.slot;  // pe:726 puts data.slot into [state.slot - spe, state.slot)
-            const uint32_t head_blk = j < 64 ? S.head_blk[j] : NONE32;
-            const bool matching_head = matching_target && head_blk != NONE32 &&
-                                       root_equals(bt.roots + 32ull * head_blk, r.q[1], r.q[2]);
-            const unsigned long long delay = S.slot - slot;
-            if (delay <= S.sqrt_spe) flag_mask |= 1u;                               // TIMELY_SOURCE
-            if (matching_target && delay <= spe) flag_mask |= 2u;                   // TIMELY_TARGET
-            if (matching_head && delay == S.min_inclusion_delay) flag_mask |= 4u;   // TIMELY_HEAD
-        }
-    }
+    const unsigned long long slot = row_slot(r), tep = row_target_epoch(r);
+    const uint32_t which = att_which(tep, S.cur_epoch);
+    const StateClock sc{S.slot, S.cur_epoch, S.prev_epoch, S.slots_per_epoch, S.min_inclusion_delay, S.sqrt_spe};
+    const StateVerdict v = att_state_status(StateRowDev{r, G, bt, S, which == 0, slot}, slot, tep, sc);
+    int32_t st = v.status;
     const uint32_t cnt = union_info[2 * g], overlap = union_info[2 * g + 1];
-    if (st == ST_OK) {
-        if (!G.sig_valid) st = ST_BAD_SIGNATURE;   // pe:736
-        else if (overlap) st = ST_BAD_SIGNATURE;
-        else if (cnt == 0) st = ST_EMPTY;
-    }
-    AttRow o;
-    o.member_base = G.member_base;
-    o.n_bits = G.size;
-    o.bits_word = G.out_word;
-    o.block_idx = 0;
-    o.epoch_p1 = 0;
-    o.order = g;
-    o.flag_mask = flag_mask;
-    o.which = tep == S.cur_epoch ? 0u : 1u;  // pe:739-742
-    o.slot = 0;
-    o.gate = g;
-    out_rows[g] = o;
+    if (st == ST_OK) st = att_indexed_status(G.sig_valid != 0, overlap != 0, cnt);  // pe:736
+    out_rows[g] = att_row_flags(G.member_base, G.size, G.out_word, v.flag_mask, which, g, g);
     status_dev[g] = st;
     status_host[g] = st;
 }

@@ -1,9 +1,9 @@
-// att_row.h -- the two pure rules every route asks of an attestation row before it reads the row's bits or its committee:
-// do the bits lie inside the arena, and which committee of the target epoch's table does (slot, index) name.  One text for
-// the host paths (engine_attest.cpp, engine_slash.cpp, through engine_internal.h) and the device bodies (att_bodies.inc), so
-// that the routes tests/test_gpu_att_rules.py compares cannot disagree here.  Neither rule decides a status: what a missing
-// committee or an index beyond committees_per_slot means, and in which order, stays with the caller.  Like the field headers
-// it compiles under hipcc and under a plain host compiler (pe_hd.h).
+// att_row.h -- where an attestation row's bits and committee lie: do the bits lie inside the arena, and which committee of the
+// target epoch's table does (slot, index) name.  One text for the host paths (engine_attest.cpp, engine_slash.cpp, through
+// engine_internal.h) and the device bodies (att_bodies.inc), so that the routes tests/test_gpu_att_rules.py compares cannot
+// disagree here.  What a missing committee or an index beyond committees_per_slot means for the row's status, and in which
+// order, is att_rules.h, over this header (the slasher keeps a ladder of its own).  Like the field headers it compiles under
+// hipcc and under a plain host compiler (pe_hd.h).
 #pragma once
 #include <stdint.h>
 

@@ -1,42 +1,44 @@
 // engine_attest.cpp -- on_attestation (pe:963-979, 1423-1428), process_attestation (pe:722-754) and aggregation
 // (validator guide A.8; pe:474/659/715/1536) over attestation rows in HOST memory: validate_on_attestation (A.4) and
 // the grouping run here, the bit / point / table work on the device.  engine_resident.cpp is the same path with the
-// rows resident in device memory.  The two row rules both share with the device bodies (bits inside the arena, committee
-// position) are att_row.h; resolve_committee (engine_internal.h) applies the second to a loaded table.
+// rows resident in device memory.  Which status a row gets is att_rules.h, one text with the device validators: the loops
+// here supply the store (MemoStore), the committee (committee_status, engine_internal.h) and the state's chain (TipRow).
 #include "engine_internal.h"
 
 using namespace posevo;
 
-namespace posevo {
-
+namespace {
+// the store adapter of att_fork_choice_status (att_rules.h) over the batch's memo: blocks by insertion index
+struct MemoStore {
+    const pe_engine* h;
+    BatchMemo* memo;
+    uint32_t find(const uint8_t* root) const { uint32_t idx; return memo->find(h, root, &idx) ? idx : NONE32; }
+    uint32_t handle(uint32_t idx) const { return idx; }
+    uint64_t slot_of(uint32_t idx) const { return h->blocks[idx].slot; }
+    uint32_t ancestor(uint32_t idx, uint64_t slot) const { return memo->ancestor(h, idx, slot); }
+};
 // validate_on_attestation (A.4) + committee resolution for on_attestation (pe:970-976).
-int32_t validate_for_fork_choice(pe_engine* h, const pe_attestation& a, Resolved* out, BatchMemo* memo)
+int32_t validate_for_fork_choice(pe_engine* h, const pe_attestation& a, AttCommitteeReading bits, Resolved* out, BatchMemo* memo)
 {
-    const bool from_block = (a.flags & PE_ATT_FLAG_FROM_BLOCK) != 0;
-    const uint64_t cur_slot = current_slot(h);
-    if (!from_block) {  // validate_target_epoch_against_current_time
-        const uint64_t cur_epoch = epoch_at_slot(h, cur_slot);
-        const uint64_t prev_epoch = cur_epoch > 0 ? cur_epoch - 1 : 0;
-        if (a.target_epoch != cur_epoch && a.target_epoch != prev_epoch)
-            return PE_ATT_TARGET_EPOCH_NOT_CURRENT_OR_PREVIOUS;
-    }
-    if (a.target_epoch != epoch_at_slot(h, a.slot)) return PE_ATT_TARGET_EPOCH_SLOT_MISMATCH;
-    uint32_t tgt_idx, blk_idx;
-    if (!memo->find(h, 1, a.target_root, &tgt_idx)) return PE_ATT_UNKNOWN_TARGET_ROOT;
-    if (!memo->find(h, 0, a.beacon_block_root, &blk_idx)) return PE_ATT_UNKNOWN_BEACON_BLOCK_ROOT;
-    if (h->blocks[blk_idx].slot > a.slot) return PE_ATT_BLOCK_AFTER_ATTESTATION_SLOT;
-    if (memo->ancestor(h, blk_idx, start_slot(h, a.target_epoch)) != tgt_idx) return PE_ATT_TARGET_NOT_ANCESTOR;
-    if (cur_slot < a.slot + 1) return PE_ATT_SLOT_NOT_IN_PAST;
-    // get_indexed_attestation -> get_beacon_committee(target_state, slot, index) (A.6)
-    CommitteeTable* t = find_table(h, a.target_epoch);
-    if (!t) return PE_ATT_NO_COMMITTEE_TABLE;
-    if (!resolve_committee(h, t, a, out).exists) return PE_ATT_COMMITTEE_INDEX_OUT_OF_RANGE;
-    if (a.n_bits < out->size) return PE_ATT_BITS_LENGTH_MISMATCH;  // bits[i] would raise for i >= len(bits)
-    out->block_idx = blk_idx;
-    return PE_ATT_OK;
+    const uint64_t cur_slot = current_slot(h), cur_epoch = epoch_at_slot(h, cur_slot);
+    const FcVerdict v = att_fork_choice_status(MemoStore{h, memo}, (a.flags & PE_ATT_FLAG_FROM_BLOCK) != 0, a.slot, a.target_epoch,
+                                               a.target_root, a.beacon_block_root, cur_slot, cur_epoch,
+                                               cur_epoch > 0 ? cur_epoch - 1 : 0, h->cfg.slots_per_epoch);
+    if (v.status != PE_ATT_OK) return v.status;
+    out->block_idx = v.block;
+    return committee_status(h, a, bits, out);  // get_indexed_attestation -> get_beacon_committee(target_state, slot, index) (A.6)
 }
-
-}  // namespace posevo
+// is_valid_indexed_attestation (A.7) of a host row: the signature verdict is the row's flag, overlap is the aggregate's to
+// report (resident_verdict), `cnt` is 1 where the bits are resident.
+int32_t host_indexed_status(const pe_attestation& a, bool resident, uint32_t cnt)
+{
+    // Bits in host memory: emptiness is tested BEFORE the verdict, so a row with no bit set and a false verdict answers
+    // PE_ATT_EMPTY_OR_INVALID_INDICES here and PE_ATT_BAD_SIGNATURE over resident bits and device rows.  The spec has one
+    // assert for both defects; the difference between the routes is kept as it is.
+    if (!resident && cnt == 0) return PE_ATT_EMPTY_OR_INVALID_INDICES;
+    return att_indexed_status((a.flags & PE_ATT_FLAG_SIGNATURE_VALID) != 0, /*overlap=*/false, cnt);
+}
+}  // namespace
 
 // ---------------------------------------------------------------- on_attestation
 // Rows handed over resident (bits_arena == PE_BITS_RESIDENT): which group of the last pe_aggregate is this row?
@@ -54,8 +56,7 @@ static inline uint32_t att_data_tag(const pe_attestation& a)
 static int resident_verdict(pe_engine* h, const std::vector<uint32_t>& info, uint32_t g, int32_t* status, uint32_t* count = nullptr)
 {
     if (2 * (size_t)g + 1 >= info.size()) return fail(h, PE_ERR_STATE, "resident aggregate did not complete");
-    if (info[2 * g + 1]) *status = PE_ATT_BAD_SIGNATURE;
-    else if (info[2 * g] == 0) *status = PE_ATT_EMPTY_OR_INVALID_INDICES;
+    *status = att_indexed_status(/*sig_valid=*/true, info[2 * g + 1] != 0, info[2 * g]);  // (the verdict was asked before the row was accepted)
     if (count) *count = *status == PE_ATT_OK ? info[2 * g] : 0;
     return PE_OK;
 }
@@ -138,38 +139,18 @@ int pe_on_attestation_batch(pe_engine* h, const pe_attestation* atts, uint32_t n
     BatchMemo memo;
     for (uint32_t i = 0; i < n; ++i) {
         const pe_attestation& a = atts[i];
-        int32_t stt = validate_for_fork_choice(h, a, &res[i], &memo);
+        int32_t stt = validate_for_fork_choice(h, a, resident ? ATT_FC_RESIDENT_BITS : ATT_FC_HOST_BITS, &res[i], &memo);
         uint32_t cnt = 0;
         if (stt == PE_ATT_OK) {
             const uint32_t use = res[i].size;  // bits beyond the committee length are never read (A.6)
-            uint32_t bits_word;
-            if (resident) {
-                // the OR-ed bits are on the device: emptiness (and member overlap) is settled there -- an empty or
-                // gated row changes nothing -- and reported when the call completes
-                if (a.n_bits != use) stt = PE_ATT_BITS_LENGTH_MISMATCH;
-                bits_word = h->res_groups[res_group[i]].word;
-                cnt = 1;
-            } else {
-                cnt = use ? pack_bits(bits_arena + a.bits_offset, use, words + n_words) : 0;
-                bits_word = n_words;
-            }
-            // is_valid_indexed_attestation (A.7): non-empty sorted-unique indices, then the signature verdict
+            // resident: the OR-ed bits are on the device: emptiness (and member overlap) is settled there -- an empty or gated
+            // row changes nothing -- and reported when the call completes
+            cnt = resident ? 1u : use ? pack_bits(bits_arena + a.bits_offset, use, words + n_words) : 0;
+            stt = host_indexed_status(a, resident, cnt);
             if (stt == PE_ATT_OK) {
-                if (cnt == 0) stt = PE_ATT_EMPTY_OR_INVALID_INDICES;
-                else if (!(a.flags & PE_ATT_FLAG_SIGNATURE_VALID)) stt = PE_ATT_BAD_SIGNATURE;
-            }
-            if (stt == PE_ATT_OK) {
-                AttRow& r = rows[n_rows];
-                r.member_base = res[i].table->offsets[res[i].pos];
-                r.n_bits = use;
-                r.bits_word = bits_word;
-                r.block_idx = res[i].block_idx;
-                r.epoch_p1 = (uint32_t)a.target_epoch + 1;
-                r.order = n_rows;
-                r.flag_mask = 0;
-                r.which = 0;
-                r.slot = (uint32_t)a.slot;
-                r.gate = resident ? 2 * res_group[i] + 1 : NONE32;
+                rows[n_rows] = att_row_fork_choice(res[i].table->offsets[res[i].pos], use,
+                                                   resident ? h->res_groups[res_group[i]].word : n_words, res[i].block_idx,
+                                                   a.target_epoch, a.slot, n_rows, resident ? 2 * res_group[i] + 1 : NONE32);
                 if (!resident) n_words += (use + 31) / 32;
                 row_src.push_back(i);
                 ++n_rows;
@@ -333,25 +314,16 @@ int pe_get_indexed_attestations(pe_engine* h, const pe_attestation* atts, uint32
     uint64_t total = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const pe_attestation& a = atts[i];
-        int32_t s = PE_ATT_OK;
-        CommitteeTable* t = find_table(h, a.target_epoch);
         Resolved c;
         uint32_t cnt = 0;
-        if (!t) s = PE_ATT_NO_COMMITTEE_TABLE;
-        else if (!resolve_committee(h, t, a, &c).exists) s = PE_ATT_COMMITTEE_INDEX_OUT_OF_RANGE;
-        else if (a.n_bits < c.size) s = PE_ATT_BITS_LENGTH_MISMATCH;
-        else if (c.size > 8192) return fail(h, PE_ERR_CAPACITY, "committee larger than 8192 members");
-        else {
+        const int32_t s = committee_status(h, a, ATT_FC_HOST_BITS, &c);
+        if (s == PE_ATT_OK) {
+            if (c.size > 8192) return fail(h, PE_ERR_CAPACITY, "committee larger than 8192 members");
             cnt = c.size ? pack_bits(bits_arena + a.bits_offset, c.size, words + n_words) : 0;
-            AttRow& r = rows[n_rows];
-            r.member_base = t->offsets[c.pos];
-            r.n_bits = c.size;
-            r.bits_word = n_words;
-            r.block_idx = r.epoch_p1 = r.order = r.flag_mask = r.which = r.slot = 0;
-            r.gate = NONE32;
+            rows[n_rows] = att_row_flags(c.table->offsets[c.pos], c.size, n_words, 0, 0, 0, NONE32);
             offs[n_rows] = (uint32_t)total;
             n_words += (c.size + 31) / 32;
-            row_table.push_back(t);
+            row_table.push_back(c.table);
             row_src.push_back(i);
             ++n_rows;
         }
@@ -495,8 +467,10 @@ int aggregate_impl(pe_engine* h, const pe_attestation* atts, uint32_t n, const u
     if (want_pk) {
         for (uint32_t g = 0; g < ng; ++g) {
             const pe_attestation& a = atts[rep[g]];
-            CommitteeTable* t = find_table(h, a.target_epoch);
-            if (!t) return fail(h, PE_ERR_NO_COMMITTEES, "no committee table for a group's target epoch");
+            // what process_attestation asks of the committee (pe:727, pe:730); its failures are errors of the call here
+            const int32_t cs = committee_status(h, a, ATT_STATE, &gres[g]);
+            if (cs == PE_ATT_NO_COMMITTEE_TABLE) return fail(h, PE_ERR_NO_COMMITTEES, "no committee table for a group's target epoch");
+            CommitteeTable* t = gres[g].table;
             if (table_pk && t != table_pk) {
                 // a batch around an epoch boundary: the groups of the first table go through the main launch, the
                 // others through one (synchronous-stream) launch per further table -- see "further tables" below
@@ -506,8 +480,8 @@ int aggregate_impl(pe_engine* h, const pe_attestation* atts, uint32_t n, const u
             } else {
                 table_pk = t;
             }
-            if (resolve_committee(h, t, a, &gres[g]).index_over) return fail(h, PE_ERR_INVALID_ARG, "committee index out of range");
-            if (a.n_bits != gres[g].size) return fail(h, PE_ERR_INVALID_ARG, "len(aggregation_bits) != len(committee)");  // pe:730
+            if (cs == PE_ATT_COMMITTEE_INDEX_OUT_OF_RANGE) return fail(h, PE_ERR_INVALID_ARG, "committee index out of range");
+            if (cs == PE_ATT_BITS_LENGTH_MISMATCH) return fail(h, PE_ERR_INVALID_ARG, "len(aggregation_bits) != len(committee)");
         }
     }
     // ---- lay everything out in the staging block ----
@@ -868,7 +842,6 @@ int pe_process_attestation_batch(pe_engine* h, const pe_state_ctx* st, const pe_
     const uint64_t spe = h->cfg.slots_per_epoch;
     const uint64_t cur_epoch = st->slot / spe;
     const uint64_t prev_epoch = cur_epoch > 0 ? cur_epoch - 1 : 0;
-    const uint64_t sqrt_spe = isqrt64(spe);
     Checkpoint cj, pj;
     cj.epoch = st->current_justified_epoch; cj.root = to_root(st->current_justified_root);
     pj.epoch = st->previous_justified_epoch; pj.root = to_root(st->previous_justified_root);
@@ -906,58 +879,45 @@ int pe_process_attestation_batch(pe_engine* h, const pe_state_ctx* st, const pe_
     std::vector<Acc> acc;
     acc.reserve(n);
     uint32_t n_words = 0;
+    // the row adapter of att_state_status (att_rules.h): the committee of a loaded table, the source against the justified
+    // checkpoint of the row's epoch, and get_block_root(state, epoch) / get_block_root_at_slot(state, slot) -- the state's
+    // chain is the ancestry of chain_tip_root (both slots are < state.slot by pe:726)
+    struct TipRow {
+        pe_engine* h;
+        const pe_attestation& a;
+        const Checkpoint& justified;
+        decltype(tip_ancestor)& ancestor;
+        uint64_t spe;
+        Resolved* c;
+        int32_t committee_status() const { return posevo::committee_status(h, a, ATT_FC_RESIDENT_BITS, c); }
+        bool index_over() const { return c->index_over; }
+        bool source_matches() const
+        {
+            Checkpoint src;
+            src.epoch = a.source_epoch; src.root = to_root(a.source_root);
+            return src == justified;
+        }
+        bool matching_target() const { return memcmp(h->blocks[ancestor(a.target_epoch * spe)].root.data(), a.target_root, 32) == 0; }
+        bool matching_head() const { return memcmp(h->blocks[ancestor(a.slot)].root.data(), a.beacon_block_root, 32) == 0; }
+    };
+    const StateClock clk{st->slot, cur_epoch, prev_epoch, spe, h->cfg.min_attestation_inclusion_delay, isqrt64(spe)};
     for (uint32_t i = 0; i < n; ++i) {
         const pe_attestation& a = atts[i];
         out_numerators[i] = 0;
-        int32_t s = PE_ATT_OK;
-        CommitteeTable* t = nullptr;
         Resolved c;
-        if (a.target_epoch != prev_epoch && a.target_epoch != cur_epoch) s = PE_ATT_TARGET_EPOCH_NOT_CURRENT_OR_PREVIOUS;  // pe:724
-        else if (a.target_epoch != a.slot / spe) s = PE_ATT_TARGET_EPOCH_SLOT_MISMATCH;                                  // pe:725
-        else if (!(a.slot + h->cfg.min_attestation_inclusion_delay <= st->slot && st->slot <= a.slot + spe))
-            s = PE_ATT_INCLUSION_WINDOW;                                                                                 // pe:726
-        else if (!(t = find_table(h, a.target_epoch))) s = PE_ATT_NO_COMMITTEE_TABLE;
-        else if (resolve_committee(h, t, a, &c).index_over) s = PE_ATT_COMMITTEE_INDEX_OUT_OF_RANGE;                     // pe:727
-        else if (a.n_bits != c.size) s = PE_ATT_BITS_LENGTH_MISMATCH;                                                    // pe:730
-        uint32_t flag_mask = 0;
-        if (s == PE_ATT_OK) {
-            // get_attestation_participation_flag_indices (A.9)
-            const Checkpoint& justified = a.target_epoch == cur_epoch ? cj : pj;
-            Checkpoint src;
-            src.epoch = a.source_epoch; src.root = to_root(a.source_root);
-            if (!(src == justified)) s = PE_ATT_SOURCE_MISMATCH;  // assert is_matching_source
-            else {
-                // get_block_root(state, epoch) / get_block_root_at_slot(state, slot): the state's chain is the
-                // ancestry of chain_tip_root (both slots are < state.slot by pe:726)
-                const uint32_t tgt_blk = tip_ancestor(a.target_epoch * spe);
-                const bool matching_target = memcmp(h->blocks[tgt_blk].root.data(), a.target_root, 32) == 0;
-                const uint32_t head_blk = tip_ancestor(a.slot);
-                const bool matching_head = matching_target && memcmp(h->blocks[head_blk].root.data(), a.beacon_block_root, 32) == 0;
-                const uint64_t delay = st->slot - a.slot;
-                if (delay <= sqrt_spe) flag_mask |= 1u;                                        // TIMELY_SOURCE
-                if (matching_target && delay <= spe) flag_mask |= 2u;                          // TIMELY_TARGET
-                if (matching_head && delay == h->cfg.min_attestation_inclusion_delay) flag_mask |= 4u;  // TIMELY_HEAD
-            }
-        }
+        const uint32_t which = att_which(a.target_epoch, cur_epoch);
+        const StateVerdict v = att_state_status(TipRow{h, a, which == 0 ? cj : pj, tip_ancestor, spe, &c}, a.slot, a.target_epoch, clk);
+        int32_t s = v.status;
         if (s == PE_ATT_OK) {
             // resident rows: emptiness / member overlap are settled on the device and reported at completion
             const uint32_t cnt = resident ? 1u : c.size ? pack_bits(bits_arena + a.bits_offset, c.size, words + n_words) : 0;
-            if (cnt == 0) s = PE_ATT_EMPTY_OR_INVALID_INDICES;                                 // pe:736
-            else if (!(a.flags & PE_ATT_FLAG_SIGNATURE_VALID)) s = PE_ATT_BAD_SIGNATURE;
+            s = host_indexed_status(a, resident, cnt);                                         // pe:736
             if (s == PE_ATT_OK) {
                 Acc e;
-                e.row.member_base = t->offsets[c.pos];
-                e.row.n_bits = c.size;
-                e.row.bits_word = resident ? h->res_groups[res_group[i]].word : n_words;
-                e.row.gate = resident ? 2 * res_group[i] + 1 : NONE32;
-                e.row.block_idx = 0;
-                e.row.epoch_p1 = 0;
-                e.row.order = 0;
-                e.row.slot = 0;
-                e.row.flag_mask = flag_mask;
-                e.row.which = a.target_epoch == cur_epoch ? 0u : 1u;                           // pe:739-742
+                e.row = att_row_flags(c.table->offsets[c.pos], c.size, resident ? h->res_groups[res_group[i]].word : n_words,
+                                      v.flag_mask, which, 0, resident ? 2 * res_group[i] + 1 : NONE32);
                 e.src = i;
-                e.table = t;
+                e.table = c.table;
                 e.pos = c.pos;
                 acc.push_back(e);
                 if (!resident) n_words += (c.size + 31) / 32;

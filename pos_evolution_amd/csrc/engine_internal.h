@@ -15,7 +15,8 @@
 //   engine_epoch.cpp   the working-state view (validators, participation flags, FFG balances) and the epoch boundary over
 //                      it: the active set, proposer sampling, rewards and penalties over resident balances and the
 //                      effective-balance hysteresis
-// The row rules host and device share (bits inside the arena, committee position) are att_row.h.
+// What host and device share of an attestation row: where its bits and its committee lie (att_row.h) and which status it
+// gets (att_rules.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -40,11 +41,24 @@
 
 #include "../../include/posevo.h"
 #include "../../include/posevo_profile.h"
-#include "att_row.h"
+#include "att_rules.h"
 #include "carve.h"
 #include "kernels.h"
 
 namespace posevo {
+
+// att_rules.h does not see include/posevo.h (the device files include it): its constants are the ABI's
+static_assert(ST_OK == PE_ATT_OK && ST_EPOCH_TIME == PE_ATT_TARGET_EPOCH_NOT_CURRENT_OR_PREVIOUS &&
+              ST_EPOCH_SLOT == PE_ATT_TARGET_EPOCH_SLOT_MISMATCH && ST_UNKNOWN_TARGET == PE_ATT_UNKNOWN_TARGET_ROOT &&
+              ST_UNKNOWN_BLOCK == PE_ATT_UNKNOWN_BEACON_BLOCK_ROOT && ST_BLOCK_AFTER_SLOT == PE_ATT_BLOCK_AFTER_ATTESTATION_SLOT &&
+              ST_TARGET_NOT_ANCESTOR == PE_ATT_TARGET_NOT_ANCESTOR && ST_SLOT_NOT_PAST == PE_ATT_SLOT_NOT_IN_PAST &&
+              ST_NO_TABLE == PE_ATT_NO_COMMITTEE_TABLE && ST_INDEX_RANGE == PE_ATT_COMMITTEE_INDEX_OUT_OF_RANGE &&
+              ST_BITS_LENGTH == PE_ATT_BITS_LENGTH_MISMATCH && ST_EMPTY == PE_ATT_EMPTY_OR_INVALID_INDICES &&
+              ST_BAD_SIGNATURE == PE_ATT_BAD_SIGNATURE && ST_INCLUSION == PE_ATT_INCLUSION_WINDOW &&
+              ST_SOURCE == PE_ATT_SOURCE_MISMATCH, "att_rules.h: ST_* are the pe_att_status of include/posevo.h");
+static_assert(FLAG_SIG_VALID == PE_ATT_FLAG_SIGNATURE_VALID && FLAG_FROM_BLOCK == PE_ATT_FLAG_FROM_BLOCK &&
+              FLAG_OVERLAPPING == PE_ATT_FLAG_OVERLAPPING_BITS, "att_rules.h: FLAG_* are the PE_ATT_FLAG_* of include/posevo.h");
+static_assert(ATT_NO_BLOCK == NONE32, "att_rules.h: a store adapter's \"no such root\" is the engine's NONE32");
 
 using Root = std::array<uint8_t, 32>;
 struct RootHash {
@@ -947,18 +961,27 @@ struct Resolved {
     uint32_t pos = 0;        // committee id in the table
     uint32_t size = 0;       // committee length
     uint32_t block_idx = 0;  // beacon_block_root
+    bool index_over = false;  // data.index >= committees per slot (pe:727)
 };
 // The committee (a.slot, a.index) names in table t (att_row.h): table / pos / size are filled where the position exists.
-// Which of `exists` and `index_over` refuses the row, and with what, is the caller's rule.
 inline CommitteePos resolve_committee(const pe_engine* h, CommitteeTable* t, const pe_attestation& a, Resolved* out)
 {
     const CommitteePos cp = att_committee_pos(t->n_committees, h->cfg.slots_per_epoch, a.slot, a.index);
+    out->index_over = cp.index_over;
     if (cp.exists) {
         out->table = t;
         out->pos = cp.pos;
         out->size = t->offsets[cp.pos + 1] - t->offsets[cp.pos];
     }
     return cp;
+}
+// ... in the table of the row's target epoch, and the status its absence or the length of the row's bits earns under
+// `reading` (att_rules.h)
+inline int32_t committee_status(pe_engine* h, const pe_attestation& a, AttCommitteeReading reading, Resolved* out)
+{
+    CommitteeTable* t = out->table = find_table(h, a.target_epoch);  // (the table also where it holds no such committee)
+    const CommitteePos cp = t ? resolve_committee(h, t, a, out) : CommitteePos{0, false, false};
+    return att_committee_status(t != nullptr, cp, a.n_bits, out->size, reading);
 }
 
 // Per-call memo for the host-side walks of a batch: consecutive rows mostly name the same few roots.
@@ -969,7 +992,7 @@ struct BatchMemo {
     Slot slots[256];
     std::vector<uint64_t> anc;  // per block index: (slot + 1) << 32 | ancestor index of the last get_ancestor asked
     BatchMemo() { for (auto& s : slots) s.used = 0; }
-    bool find(const pe_engine* h, int /*which*/, const uint8_t* root, uint32_t* idx)
+    bool find(const pe_engine* h, const uint8_t* root, uint32_t* idx)
     {
         Slot& s = slots[root[0]];  // roots are hash outputs: any byte is uniform
         if (s.used && memcmp(s.root, root, 32) == 0) { *idx = s.idx; return true; }
@@ -990,7 +1013,6 @@ struct BatchMemo {
     }
 };
 
-int32_t validate_for_fork_choice(pe_engine* h, const pe_attestation& a, Resolved* out, BatchMemo* memo);
 // rows handed over with PE_BITS_RESIDENT: which group of the last pe_aggregate is this row (engine_attest.cpp)
 bool find_resident(const pe_engine* h, const pe_attestation& a, uint32_t* g_out, uint32_t guess);
 // Where a caller's pointer lives (engine_resident.cpp).  Pageable is also the answer for anything the runtime does not know.

@@ -125,6 +125,18 @@ struct AttRow {
     uint32_t gate;         // index into the gate array (NONE32 = ungated): a non-zero gate word voids the row on the
                            // device (rows handed over resident by pe_aggregate whose members overlapped, A.8)
 };
+// the row of an accepted attestation: for update_latest_messages (the fork-choice pass) ...
+__host__ __device__ inline AttRow att_row_fork_choice(uint32_t member_base, uint32_t n_bits, uint32_t bits_word, uint32_t block_idx,
+                                                      uint64_t target_epoch, uint64_t slot, uint32_t order, uint32_t gate)
+{
+    return AttRow{member_base, n_bits, bits_word, block_idx, (uint32_t)target_epoch + 1, order, 0u, 0u, (uint32_t)slot, gate};
+}
+// ... and for the flag loop of process_attestation (pe:745-749)
+__host__ __device__ inline AttRow att_row_flags(uint32_t member_base, uint32_t n_bits, uint32_t bits_word, uint32_t flag_mask,
+                                                uint32_t which, uint32_t order, uint32_t gate)
+{
+    return AttRow{member_base, n_bits, bits_word, 0u, 0u, order, flag_mask, which, 0u, gate};
+}
 // update_latest_messages for a batch: phase 1 atomicMax of (epoch+1, ~order), phase 2 winners write.
 void launch_lmd_update(hipStream_t s, const AttRow* rows, uint32_t n_rows, const uint32_t* members,
                        const uint32_t* bit_arena, const uint8_t* flags, uint64_t* vote_key, uint32_t* vote_block,

@@ -177,6 +177,46 @@ def test_boundary_matrix_equals_the_model(world, si, route):
         e.close()
 
 
+BITS_ROUTES = ("host bits", "resident bits", "device rows")
+
+
+@pytest.mark.parametrize("route", BITS_ROUTES)
+def test_no_bit_set_and_a_false_verdict_answers_by_route(world, route):
+    """The one row the model refuses (is_valid_indexed_attestation is ONE assert, A.7; att_rules_model._indexed_status): no
+    bit set AND a false signature verdict.  Host rows over bits in host memory test emptiness first; host rows over
+    PE_BITS_RESIDENT and device rows (PE_ROWS_RESIDENT) ask the verdict first.  A known difference between the routes
+    (DESIGN.md 7), pinned here on both sides so that no change moves it unseen; the rows beside it are accepted everywhere."""
+    w = world
+    sc = w.scenarios[0]
+    b = C._Batch(w, sc["state"])
+    b.add("valid", 59, 0, "A59", 1, "A32")
+    b.add("no bit set, signature verdict false", 57, 0, "A57", 1, "A32", bits=[0] * C.SIZE, sig_valid=False)
+    b.add("valid", 58, 1, "A58", 1, "A32")
+    rows = b.done()
+    want = M.EMPTY if route == "host bits" else M.BAD_SIGNATURE
+    atts, arena = _pack(rows)
+    ctx = _ctx(w, sc)
+    e = _engine(w, sc)
+    try:
+        if route == "host bits":
+            status, _, count = e.on_attestation_batch(packed=(atts, arena))
+            pst, num = e.process_attestation_batch(ctx, packed=(atts, arena))
+        elif route == "resident bits":
+            agg = e.aggregate(packed=(atts, arena), want_aggregate_pubkeys=False)
+            assert agg["n_groups"] == len(rows) and np.array_equal(agg["group_of"], np.arange(len(rows)))
+            status, _, count = e.on_attestation_batch(packed=(agg["atts"], RES))
+            pst, num = e.process_attestation_batch(ctx, packed=(agg["atts"], RES))
+        else:
+            agg, status, count, pst, num = _resident_calls(e, _dev_rows(atts), arena, ctx, head=False)
+            assert int(agg["n_groups"]) == len(rows)
+        assert [int(x) for x in status[:3]] == [M.OK, want, M.OK]
+        assert [int(x) for x in pst[:3]] == [M.OK, want, M.OK]
+        assert int(num[1]) == 0 and int(num[0]) > 0 and int(num[2]) > 0
+        assert [int(x) for x in count[:3]] == [rows[0]["popcount"], 0, rows[2]["popcount"]]
+    finally:
+        e.close()
+
+
 def wrap_rows(w):
     """-> (scenario, [a plain valid row, the row whose position wraps a 64-bit sum onto committee 0]) of state.slot 69."""
     sc = next(sc for sc in w.scenarios if sc["name"] == "state.slot 69")
