@@ -682,7 +682,12 @@ int pe_ssz_merkleize(pe_engine* h, const uint8_t* chunks32, uint64_t n_chunks, u
                      uint8_t out_root[32]);
 
 /* Plain G1 sum over caller-chosen groups: out[g] = sum_{j in [offsets[g], offsets[g+1])}
- * points[index[j]] (index NULL = identity).  points96 NULL = the validators' pubkeys. */
+ * points[index[j]] (index NULL = identity).  points96 NULL = the validators' pubkeys.
+ * The input points are NOT validated, here or in pe_g2_sum, pe_g1_key_validate, pe_g2_subgroup_check and pe_set_validators
+ * (one converter each for G1 and G2 feeds them all): no test for coordinates < p, none for the curve equation.  Bit 6 of
+ * byte 0 set is the identity whatever else the encoding holds; bits 7 and 5 of byte 0 are masked and ignored (the pairing
+ * calls below REFUSE bit 7); a coordinate >= p is reduced.  A caller that needs the checks has the pairing calls, or the
+ * decompress calls, which build y themselves. */
 int pe_g1_sum(pe_engine* h, const uint8_t* points96, uint64_t n_points,
               const uint32_t* index, const uint32_t* offsets, uint32_t n_groups, uint8_t* out96);
 
@@ -706,7 +711,9 @@ int pe_g1_compress(const uint8_t* in96, uint64_t n, uint8_t* out48);
 /* bls.Aggregate over real BLSSignature points (type pe:37, Attestation.signature pe:717; aggregation prose pe:659,
  * pe:1536): plain G2 sum over caller-chosen groups, out[g] = sum_{j in [offsets[g], offsets[g+1])} points[index[j]]
  * (index NULL = identity).  Points are 192-byte uncompressed affine, ZCash order x.c1 | x.c0 | y.c1 | y.c0, each 48
- * bytes big-endian; bit 6 of byte 0 flags infinity.  Outputs are canonical affine in the same format (exact). */
+ * bytes big-endian; bit 6 of byte 0 flags infinity.  Outputs are canonical affine in the same format (exact).
+ * Like pe_g1_sum, pe_g2_sum and pe_g2_subgroup_check validate nothing: bits 7 and 5 of byte 0 are ignored, no coordinate is
+ * tested against p or the curve (see pe_g1_sum). */
 #define PE_G2_POINT_BYTES 192
 /* BLSSignature wire format (pe:37, pe:717): 96 bytes x.c1 | x.c0, flag bits as for BLSPubkey with the sign taken on
  * (y.c1, y.c0).  pe_g2_decompress runs on the GPU (an Fp2 square root per point: two Fp exponentiations, ~0.95 ms
@@ -855,7 +862,13 @@ int pe_g2_subgroup_check(pe_engine* h, const uint8_t* points192, uint64_t n, int
 /* ---- the pairing check (is_valid_indexed_attestation's last step, pe:736, 976, 1456) ------------------------------
  * Batched optimal-ate pairing products on the device.  Points in the formats above: 96-byte uncompressed G1 (x | y),
  * 192-byte uncompressed G2 in ZCash order (x.c1 | x.c0 | y.c1 | y.c0), infinity = bit 6 of byte 0.  All arrays in host
- * memory.  Every point is checked against its curve equation (and for canonical coordinates) on the device.
+ * memory.  Every point is checked against its curve equation (and for canonical coordinates) on the device:
+ *   bit 6 of byte 0 set            infinity, whatever else the encoding holds (0xC0.., 0x60.., 0x40 over non-zero bytes)
+ *   otherwise bit 7 of byte 0 set  PE_BLS_BAD_POINT: the compressed form is refused (pe_g1_sum / pe_g2_sum ignore the bit)
+ *   bit 5 of byte 0                no part of the leading coordinate: ignored
+ *   any coordinate >= p            PE_BLS_BAD_POINT (x + p is no second spelling of x); the elements after the first are
+ *                                  plain 384-bit integers, so any of their top three bits set is >= p
+ *   off the curve                  PE_BLS_BAD_POINT
  * verdict[g]: 1  the product of e(P_j, Q_j) over j in [offsets[g], offsets[g+1]) is 1
  *             0  it is not
  *             2  a point of the group is not on its curve (PE_BLS_BAD_POINT)

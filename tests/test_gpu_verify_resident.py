@@ -21,6 +21,8 @@ from pos_evolution_amd import _abi
 from pos_evolution_amd._abi import pe_state_ctx
 from tests import helpers as H
 from tests import verify_resident_model as vm
+from tests import wire_cases as wc
+from tests import wire_model as wm
 from tests.test_gpu_g2 import _off_subgroup_point
 from tests.test_gpu_resident_rows import _dev_rows
 
@@ -32,6 +34,7 @@ A, B = 0x1234567, 0x89ABCDE                                   # sk_v = A + v B: 
 MSG = [(0x5A3C19E0F1D2B4A6978877665544332211FFEEDDCCBBAA990011223344556677 * (j + 1) + 97 * j) % R for j in range(4)]
 D = 0xD00DFEEDFACE                                            # the cancelling pair: sig_a + D G2, sig_b - D G2
 P_FIELD = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
+WIRE_H = wc.BASE_K["g2"]                                      # the base point of tests/wire_cases.py as a message point
 BAD_SIGNATURE = 12                                            # PE_ATT_BAD_SIGNATURE
 INVALID_ARG = -1                                               # PE_ERR_INVALID_ARG
 
@@ -180,9 +183,11 @@ def test_layout_edges_by_construction_and_against_fast_aggregate_verify(engine_f
 
 
 # ------------------------------------------------------------------ the rule table
-def _rule_table_rows(w, subgroup_member_scalar=None):
+def _rule_table_rows(w, subgroup_member_scalar=None, wire_cases=()):
     """One group per row of the table (except 'no committee', which an aggregate with pubkeys cannot hold: see
-    test_an_aggregate_with_a_group_without_committee_fails), honest groups between them.  -> (Rows, model, extras)."""
+    test_an_aggregate_with_a_group_without_committee_fails), honest groups between them; then one honest group per case of
+    `wire_cases` signing WIRE_H G2, whose message point (index 8 + k) the caller replaces by the case's bytes.
+    -> (Rows, model, extras)."""
     rows, model, note = Rows(w), [], {}
 
     def honest(c, j=0, parts=((0, 1, 2), (3, 4))):
@@ -225,14 +230,19 @@ def _rule_table_rows(w, subgroup_member_scalar=None):
     # an identity message point: own point index 7
     note["identity_message"] = honest(9, j=0)
     honest(10, j=1)
+    for k, c in enumerate(wire_cases):
+        key = _sk_sum(w, 11 + k, _bits(0, 1, 2))
+        rows.add(11 + k, 0, _bits(0, 1, 2), key * WIRE_H % R, 8 + k)
+        note["wire", c.name] = len(model)
+        model.append(vm.Group(key=key, h=WIRE_H, sig=key * WIRE_H % R))
     return rows, model, note
 
 
-@pytest.mark.parametrize("check_subgroup", [False, True])
-def test_every_row_of_the_rule_table(engine_factory, tool, check_subgroup):
+def _rule_table_call(engine_factory, tool, check_subgroup, wire_cases=()):
+    """The rule table decided by one pe_verify_resident; -> (verdicts, model, note, stats)."""
     w = _world(engine_factory)
     e = w["e"]
-    rows, model, note = _rule_table_rows(w)
+    rows, model, note = _rule_table_rows(w, wire_cases=wire_cases)
     atts, arena, sigs, msg_of_row = rows.build(tool)
     sigs[note["undecodable_row"]] = 0                       # no compression flag: malformed
     sigs[note["off_subgroup_row"]] = np.frombuffer(g2.compress(_off_subgroup_point()), dtype=np.uint8)
@@ -242,7 +252,13 @@ def test_every_row_of_the_rule_table(engine_factory, tool, check_subgroup):
     else:
         model[g_off].sig_in_g2 = False                      # it enters the sum: the call's own pass finds the aggregate
     # points 0..3 = MSG; 4: off its curve; 5: unused; 6: not canonical; 7: the identity
-    msgs = np.concatenate([_msg_points(tool), np.zeros((4, 192), dtype=np.uint8)])
+    msgs = np.concatenate([_msg_points(tool), np.zeros((4 + len(wire_cases), 192), dtype=np.uint8)])
+    for k, c in enumerate(wire_cases):
+        msgs[8 + k] = np.frombuffer(c.enc, dtype=np.uint8)
+        if c.expect == wm.BAD:
+            model[note["wire", c.name]].bad_message = True
+        elif c.expect == wm.INFINITY:
+            model[note["wire", c.name]].h = 0
     good = g2.mul(MSG[1], g2.G2)
     msgs[4] = np.frombuffer(g2.to_bytes192((good[0], ((good[1][0] + 1) % P_FIELD, good[1][1]))), dtype=np.uint8)
     msgs[5] = msgs[0]
@@ -265,13 +281,37 @@ def test_every_row_of_the_rule_table(engine_factory, tool, check_subgroup):
             model[g].bad_message = True
     assert first == sorted(first)
     got = e.verify_resident(msgs, point_of_row=point, apply=False)
+    return got, model, note, e._profile_verify_resident_stats()
+
+
+@pytest.mark.parametrize("check_subgroup", [False, True])
+def test_every_row_of_the_rule_table(engine_factory, tool, check_subgroup):
+    got, model, note, st = _rule_table_call(engine_factory, tool, check_subgroup)
     assert got.tolist() == [vm.decide(m)[0] for m in model]
-    st = e._profile_verify_resident_stats()
     want = vm.stats(model, subgroup_pass=not check_subgroup)
     assert st == {**want, "no_committee": 0}
     for row in ("bad_message", "overlap", "bad_member", "empty_key", "identity_signature", "identity_message", "pairing"):
         assert st[row] >= 1, row
     assert st["not_g2"] == (0 if check_subgroup else 1) and st["bad_message"] == 2
+
+
+def test_every_wire_case_on_the_message_point(engine_factory, tool):
+    """k_bls_resident_prepare decodes the message point with wire_load_g2 (wire_points.h): every case of tests/wire_cases.py
+    as the message point of an honest group behind the rule table's own groups, whose verdicts must not move.  A bad encoding is
+    row 2 of the table (verdict 2), every spelling of infinity the identity message (0), bit 5 on x.c1 changes nothing (1)."""
+    cases = wc.cases("g2")
+    got, model, note, st = _rule_table_call(engine_factory, tool, False, wire_cases=cases)
+    want = [vm.decide(m)[0] for m in model]
+    by_class = {wc.SAME: 1, wm.INFINITY: 0, wm.BAD: 2}
+    for c in cases:
+        assert want[note["wire", c.name]] == by_class[c.expect], c.name
+    seen = [(c.name, int(got[note["wire", c.name]]), by_class[c.expect]) for c in cases]
+    print(seen)
+    assert not [s for s in seen if s[1] != s[2]]
+    assert got.tolist() == want
+    assert st == {**vm.stats(model, subgroup_pass=True), "no_committee": 0}
+    assert st["bad_message"] == 2 + sum(c.expect == wm.BAD for c in cases)
+    assert st["identity_message"] == 1 + sum(c.expect == wm.INFINITY for c in cases)
 
 
 def test_an_aggregate_with_a_group_without_committee_fails(engine_factory, tool):

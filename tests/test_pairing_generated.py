@@ -38,7 +38,8 @@ def test_committed_vectors_are_the_generated_ones():
     gen = _generator()
     assert open(gen.JSON_PATH).read() == gen.json_text(), "pairing_vectors.json: run tests/golden/generate_pairing.py"
     names = [g["name"] for g in gen.vectors()["groups"]]
-    assert names == ["one_pair", "two_pairs", "three_pairs", "with_infinity"]
+    assert names == ["one_pair", "two_pairs", "three_pairs", "with_infinity", "seven_pairs", "thirteen_pairs",
+                     "thirteen_pairs_infinity_at_6_and_12"]
 
 
 def test_no_kernel_of_the_pairing_check_uses_scratch():
