@@ -681,6 +681,67 @@ int pe_state_roots(pe_engine* h, uint32_t which, uint32_t limit_log2, pe_state_r
 int pe_ssz_merkleize(pe_engine* h, const uint8_t* chunks32, uint64_t n_chunks, uint32_t depth, int64_t mix_length,
                      uint8_t out_root[32]);
 
+/* ---- deposits: process_deposit over the resident registry (pe:139-175) ------- */
+/* DepositData (pe:91-95) as it travels: 184 bytes, no padding. */
+typedef struct pe_deposit_data {
+    uint8_t pubkey[48];
+    uint8_t withdrawal_credentials[32];
+    uint64_t amount;
+    uint8_t signature[96];
+} pe_deposit_data;
+typedef struct pe_deposit_params {
+    uint64_t effective_balance_increment;  /* 10^9 */
+    uint64_t max_effective_balance;        /* 32 * 10^9; at most 65535 increments */
+    uint64_t far_future_epoch;             /* 2^64 - 1: the four epochs of a new validator */
+} pe_deposit_params;
+void pe_deposit_params_default(pe_deposit_params* out);
+typedef enum pe_deposit_status {
+    PE_DEP_APPENDED = 0,               /* a new pubkey with a valid signature: state.validators.append (pe:166-170) */
+    PE_DEP_TOPUP = 1,                  /* the pubkey is in the registry (or was created earlier in this batch): increase_balance */
+    PE_DEP_IGNORED_BAD_SIGNATURE = 2,  /* a new pubkey whose bls.Verify is false (pe:165): the key does not decode or fails
+                                          KeyValidate, the signature does not decode or lies outside G2, or the pairing
+                                          product is not 1.  The reference skips such a deposit silently */
+    PE_DEP_BAD_PROOF = 3               /* is_valid_merkle_branch false (pe:141): the reference's assert */
+} pe_deposit_status;
+typedef struct pe_deposit_stats {
+    uint32_t n_appended, n_topups, n_ignored, n_bad_proof;
+    uint64_t n_validators;             /* pe_num_validators(h) after the call */
+} pe_deposit_stats;
+/* out_roots32[32 i ..] = compute_signing_root(DepositMessage(deposit i), domain) (pe:157-163), hashed on the device:
+ * H(hash_tree_root(DepositMessage) || domain).  hash_to_curve of these is the caller's, as for every BLS call here; its
+ * results are pe_process_deposits' message_points192.  Synchronous; needs no registry. */
+int pe_deposit_signing_roots(pe_engine* h, const pe_deposit_data* deposits, uint32_t n, const uint8_t domain[32],
+                             uint8_t* out_roots32);
+/* process_deposit for n deposits, with the reference's semantics applied sequentially in batch order: a deposit's pubkey is
+ * looked up in the registry as the deposits before it left it (where the registry holds a pubkey twice the lowest index is
+ * the match, as .index() returns it); the first deposit of a new pubkey with a valid signature creates validator
+ * pe_num_validators + (validators created before it in this batch); later deposits of that pubkey are top-ups whose
+ * signature is not looked at; earlier ones with a bad signature are ignored.
+ * proofs: n x 33 x 32 bytes, the branch of deposit i against deposit_root at index eth1_deposit_index + i (depth 33: the
+ * length mix-in is the last node; the leaf is hash_tree_root(DepositData)); NULL = proofs are not checked (genesis).  If ANY
+ * deposit fails its proof nothing is applied: the failing ones read PE_DEP_BAD_PROOF, the others the status they would have
+ * had, every out_index is 0xFFFFFFFF, out->n_appended = n_topups = 0 and the call returns PE_OK.
+ * message_points192: H(signing_root_i) in the 192-byte form of pe_pairing_check, one per deposit (read for new pubkeys
+ * only; may be NULL when the caller knows there are none -- a new pubkey then fails with PE_ERR_INVALID_ARG).
+ * status[i]: pe_deposit_status.  out_index[i] (may be NULL): the validator credited, or 0xFFFFFFFF.  out may be NULL.
+ * What grows: every resident per-validator array, by capacity doubling, contents kept -- the working-state view (effective
+ * balance min(amount - amount % increment, max), not active, not slashed; a view that still mirrored the pe_set_validators
+ * data becomes one of its own), activation / exit / eligibility / withdrawable epochs (far_future_epoch), balances
+ * (amount), inactivity scores and both participation lists (0), pubkey leaves and withdrawal credentials, the G1 pubkey
+ * table (where keys are loaded) and the pubkey index itself.  The justified-state arrays of pe_set_validators take
+ * effective balance 0, inactive, no latest message until the caller's next pe_set_validators(new n, ...): get_head does not
+ * see the new validators.  Dropped, as derived from n: the resident active list (pe_active_set) and the committee sums.
+ * Committee tables of past epochs name old indices only and stay.
+ * Synchronous (completes open pipelines first); one GPU.
+ *   PE_ERR_STATE        pe_dist_init* active; the slasher is enabled (its history is sized for n: pe_slasher_disable first);
+ *                       pe_registry_set_static, pe_state_set_balances or pe_registry_set_epochs missing; the registry
+ *                       would grow beyond 2^32 - 2 validators.  Nothing changes.
+ *   PE_ERR_INVALID_ARG  an amount above 2^63 (increase_balance does not saturate: the sums of a call then cannot wrap);
+ *                       increment 0 or max_effective_balance above 65535 increments.  Nothing changes. */
+int pe_process_deposits(pe_engine* h, const pe_deposit_data* deposits, uint32_t n, const uint8_t* proofs,
+                        uint64_t eth1_deposit_index, const uint8_t deposit_root[32], const uint8_t* message_points192,
+                        const pe_deposit_params* params, int32_t* status, uint32_t* out_index, pe_deposit_stats* out);
+
 /* Plain G1 sum over caller-chosen groups: out[g] = sum_{j in [offsets[g], offsets[g+1])}
  * points[index[j]] (index NULL = identity).  points96 NULL = the validators' pubkeys.
  * The input points are NOT validated, here or in pe_g2_sum, pe_g1_key_validate, pe_g2_subgroup_check and pe_set_validators

@@ -103,6 +103,13 @@ int pe_profile_verify_sums(const pe_engine* h, uint32_t n_groups, uint8_t* out_p
 #define PE_VERIFY_RESIDENT_STATS 11
 int pe_profile_verify_resident_stats(const pe_engine* h, uint32_t out[PE_VERIFY_RESIDENT_STATS]);
 
+/* pe_process_deposits.  The pubkey index the handle keeps: *out_slots = its u32 slots (0 = none: never built, or dropped with
+ * the static part), a power of two: at a build the smallest one >= max(64, 2 (validators + the call's deposits)), doubled until
+ * that holds again when a later call outgrows it; a pubkey's first slot is the first four bytes of its leaf, little-endian,
+ * masked; *out_keys = validators in it; *out_build_ms = device time of the last full build (paid once per handle and static
+ * part, not per call).  Any output may be NULL. */
+int pe_profile_deposit_index(const pe_engine* h, uint32_t* out_slots, uint64_t* out_keys, float* out_build_ms);
+
 #ifdef __cplusplus
 }
 #endif

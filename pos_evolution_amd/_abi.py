@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("POSEVO_LIB_PATH") or os.path.join(_HERE, "libposevo.so")
 
 PE_OK = 0
+PE_ERR_INVALID_ARG = -1
 PE_ERR_NO_DEVICE = -2
 PE_ERR_UNKNOWN_PARENT = -4
 PE_ERR_UNKNOWN_ROOT = -9
@@ -135,6 +136,25 @@ class pe_slashings_stats(C.Structure):
                 ("n_penalised", C.c_uint64), ("penalties", C.c_uint64), ("n_saturated", C.c_uint64)]
 
 
+class pe_deposit_data(C.Structure):
+    """struct pe_deposit_data (include/posevo.h): DepositData as it travels, 184 bytes."""
+    _fields_ = [("pubkey", C.c_uint8 * 48), ("withdrawal_credentials", C.c_uint8 * 32), ("amount", C.c_uint64),
+                ("signature", C.c_uint8 * 96)]
+
+
+class pe_deposit_params(C.Structure):
+    """struct pe_deposit_params (include/posevo.h): the constants of get_validator_from_deposit."""
+    _fields_ = [("effective_balance_increment", C.c_uint64), ("max_effective_balance", C.c_uint64),
+                ("far_future_epoch", C.c_uint64)]
+
+
+class pe_deposit_stats(C.Structure):
+    """struct pe_deposit_stats (include/posevo.h): what one pe_process_deposits did."""
+    _fields_ = [("n_appended", C.c_uint32), ("n_topups", C.c_uint32), ("n_ignored", C.c_uint32), ("n_bad_proof", C.c_uint32),
+                ("n_validators", C.c_uint64)]
+
+
+PE_DEP_APPENDED, PE_DEP_TOPUP, PE_DEP_IGNORED_BAD_SIGNATURE, PE_DEP_BAD_PROOF = 0, 1, 2, 3
 PE_REWARDS_INACTIVITY, PE_REWARDS_DELTAS = 1, 2
 PE_ROOT_BALANCES, PE_ROOT_INACTIVITY, PE_ROOT_PART_PREV, PE_ROOT_PART_CUR, PE_ROOT_VALIDATORS = 1, 2, 4, 8, 16
 
@@ -228,6 +248,10 @@ SIGNATURES = {
     "pe_registry_get_static": (C.c_int, [_H, C.c_uint64, _u8p, _u8p, _u64p, C.c_void_p]),
     "pe_state_roots": (C.c_int, [_H, C.c_uint32, C.c_uint32, _P(pe_state_root_set), _u8p]),
     "pe_ssz_merkleize": (C.c_int, [_H, _u8p, C.c_uint64, C.c_uint32, C.c_int64, _u8p]),
+    "pe_deposit_params_default": (None, [_P(pe_deposit_params)]),
+    "pe_deposit_signing_roots": (C.c_int, [_H, _u8p, C.c_uint32, _u8p, _u8p]),
+    "pe_process_deposits": (C.c_int, [_H, _u8p, C.c_uint32, _u8p, C.c_uint64, _u8p, _u8p, _P(pe_deposit_params), _i32p, _u32p,
+                                      _P(pe_deposit_stats)]),
     "pe_g1_sum": (C.c_int, [_H, _u8p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u8p]),
     "pe_prune": (C.c_int, [_H, C.c_void_p]),
     "pe_set_block_checkpoints": (C.c_int, [_H, C.c_uint32, C.c_uint64, _u8p, C.c_uint64, _u8p]),
@@ -294,6 +318,7 @@ SIGNATURES = {
     "pe_profile_batch_gt": (C.c_int, [_H, _u8p]),
     "pe_profile_verify_set_stripe": (C.c_int, [_H, C.c_uint32]),
     "pe_profile_verify_stats": (C.c_int, [_H, _u32p]),
+    "pe_profile_deposit_index": (C.c_int, [_H, _u32p, _u64p, C.c_void_p]),
     "pe_profile_verify_sums": (C.c_int, [_H, C.c_uint32, _u8p, _u8p]),
     "pe_profile_verify_resident_stats": (C.c_int, [_H, _u32p]),
 }

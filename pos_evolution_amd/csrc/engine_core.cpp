@@ -552,7 +552,8 @@ void pe_engine_destroy(pe_engine* h)
                       &h->d_activation_epoch, &h->d_exit_epoch, &h->d_active, &h->d_active_wg, &h->d_registry_wg,
                       &h->d_rbalance, &h->d_inactivity, &h->d_withdrawable,
                       &h->d_pubkey_leaf, &h->d_withdrawal_credentials, &h->d_activation_eligibility, &h->d_ssz_zero,
-                      &h->d_ssz_validator_roots, &h->d_ssz_level[0], &h->d_ssz_level[1], &h->d_ssz_chunks, &h->d_bls, &h->d_batch, &h->d_verify})
+                      &h->d_ssz_validator_roots, &h->d_ssz_level[0], &h->d_ssz_level[1], &h->d_ssz_chunks, &h->d_bls, &h->d_batch, &h->d_verify,
+                      &h->d_dep_index, &h->d_deposit})
         b->release();
     if (h->ev_active_read) (void)hipEventDestroy(h->ev_active_read);
     for (auto& t : h->tables) {

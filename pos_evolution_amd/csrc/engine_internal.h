@@ -15,6 +15,7 @@
 //   engine_epoch.cpp   the working-state view (validators, participation flags, FFG balances) and the epoch boundary over
 //                      it: the active set, proposer sampling, rewards and penalties over resident balances and the
 //                      effective-balance hysteresis
+//   engine_deposit.cpp process_deposit over the resident registry: the pubkey index, proofs, verdicts of new keys, registry_grow
 // What host and device share of an attestation row: where its bits and its committee lie (att_row.h) and which status it
 // gets (att_rules.h).
 #pragma once
@@ -308,6 +309,15 @@ struct pe_engine {
     DevBuf d_ssz_level[2];         // the nodes between two passes of k_ssz_merkle, word form
     DevBuf d_ssz_chunks;           // pe_ssz_merkleize: the caller's chunks
     DevBuf d_bls;                  // one pairing run's workspace: the Layout of pairing_run (engine_bls.cpp) or of pe_verify_resident
+    // ---- deposits (engine_deposit.cpp) ----
+    // the pubkey index over d_pubkey_leaf: u32[dep_index_slots] open addressing, entry = the lowest validator index with the
+    // slot's leaf; validators [0, dep_index_keys) are in it.  dep_index_slots = 0: none (dropped where the static part is)
+    DevBuf d_dep_index;
+    uint32_t dep_index_slots = 0;
+    uint64_t dep_index_keys = 0;
+    float dep_index_build_ms = 0;  // pe_profile_deposit_index: the last full build, launch to completion
+    DevBuf d_deposit;              // one call's workspace: the Layout of pe_process_deposits
+    uint64_t reg_capacity = 0;     // validators every resident per-validator array has room for (registry_grow doubles it)
     // ---- pe_verify_resident (engine_resident_verify.cpp) ----
     // which aggregate the arena's d_res_points belong to: valid while that is still the handle's last aggregate of either kind
     struct ResidentVerify {
@@ -751,6 +761,11 @@ void resident_balances_drop(pe_engine* h);
 void registry_static_drop(pe_engine* h);
 // a working-state view that still mirrors the registry becomes a view of its own, flags included (engine_epoch.cpp)
 int materialise_state_view(pe_engine* h);
+// Every resident per-validator array gets room for n_new validators with its contents kept (capacity doubling), the rows
+// [n_val, n_new) take the values of a validator nobody has written yet (zero balances, scores, participation and justified
+// data, no latest message) and n_val becomes n_new; what is derived from n -- the resident active list, the committee sums --
+// is dropped.  The caller writes the rows' other columns (engine_deposit.cpp).
+int registry_grow(pe_engine* h, uint64_t n_new);
 
 // Re-pack one attestation's bits into 32-bit words (zero padded, masked to n_use bits); returns popcount.
 uint32_t pack_bits(const uint8_t* src, uint32_t n_use, uint32_t* dst_words);

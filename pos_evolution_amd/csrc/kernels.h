@@ -732,4 +732,66 @@ void launch_sv_mark_identity(hipStream_t s, const uint32_t* points_mont48, uint6
 void launch_sv_rows_g1(hipStream_t s, const uint32_t* points_mont, const uint32_t* rows, uint32_t n, uint8_t* out_be96);
 void launch_sv_rows_g2(hipStream_t s, const uint32_t* points_mont48, const uint32_t* rows, uint32_t n, uint8_t* out_be192);
 
+// ---- process_deposit (deposit_kernels.hip; host side: engine_deposit.cpp; the rules per deposit: deposit_row.h) ----
+// The pubkey index: tab[T] (T a power of two, mask = T - 1) = open addressing over 32-byte leaves (8 words each, memory order),
+// entry = the LOWEST key index that holds the slot's leaf, NONE32 = empty.  Keys [first, end) of `leaves` are inserted; where
+// only_if_none is not null key v takes part only if only_if_none[v] == NONE32.  out_slot (nullable): the slot key v's leaf
+// lives in (NONE32 where it took no part).  The table must keep at least as many empty slots as keys.
+void launch_deposit_index_build(hipStream_t s, const uint32_t* leaves, uint64_t first, uint64_t end, const uint32_t* only_if_none,
+                                uint32_t* tab, uint32_t mask, uint32_t* out_slot);
+// One lane per deposit: the pubkey's leaf (digest bytes, as d_pubkey_leaf holds them), hash_tree_root(DepositData) walked up
+// the 33 nodes of its branch (proofs null: not walked, proof_ok = 1) and compare with deposit_root, and (signing_roots not
+// null) compute_signing_root(DepositMessage, domain) as digest bytes.
+struct DepositLeavesArgs {
+    const uint32_t* rows;        // n x DEPOSIT_ROW_WORDS: pe_deposit_data
+    uint32_t n;
+    const uint32_t* proofs;      // nullable: n x 33 x 8 words
+    uint64_t index0;             // eth1_deposit_index of deposit 0
+    uint32_t root[8];            // deposit_root, SHA word form
+    uint32_t domain[8];          // the domain, SHA word form (read where signing_roots is not null)
+    uint32_t* leaf;              // n x 8 words
+    uint32_t* proof_ok;          // n
+    uint32_t* signing_roots;     // nullable: n x 8 words
+};
+void launch_deposit_leaves(hipStream_t s, const DepositLeavesArgs& a);
+// reg_index[i] = the registry's lowest index whose leaf equals deposit i's in all 32 bytes, or NONE32
+void launch_deposit_probe(hipStream_t s, const uint32_t* dep_leaf, uint32_t n, const uint32_t* reg_leaves, const uint32_t* tab,
+                          uint32_t mask, uint32_t* reg_index);
+// ONE workgroup.  For the deposits that missed the registry (reg_index NONE32; key_slot = their slot of the batch's own table,
+// launch_deposit_index_build over dep_leaf): first_valid[slot] (NONE32 on entry) = the key's first position whose sig_ok is
+// set; then deposit_status per deposit, the creators' new indices n_val + (creators before them, in batch order), and the
+// index every deposit credits (NONE32: none).  counts[0] = creators.
+struct DepositResolveArgs {
+    uint32_t n;
+    uint32_t n_val;
+    const uint32_t* reg_index;
+    const uint32_t* key_slot;
+    const uint32_t* sig_ok;
+    const uint32_t* proof_ok;
+    uint32_t* first_valid;
+    uint32_t* rank;              // n: scratch
+    int32_t* status;
+    uint32_t* out_index;
+    uint32_t* counts;
+};
+void launch_deposit_resolve(hipStream_t s, const DepositResolveArgs& a);
+// One lane per deposit: a credited deposit adds its amount to balances[out_index] (64-bit atomic: several deposits may credit
+// one validator; a new validator's balance starts at 0), a creator also writes its validator's rows.
+struct DepositApplyArgs {
+    const uint32_t* rows;
+    uint32_t n;
+    const int32_t* status;
+    const uint32_t* out_index;
+    const uint32_t* dep_leaf;
+    uint64_t increment, max_effective_balance, far_future_epoch;  // DepositParams
+    uint64_t* balances;
+    uint64_t* eff_balance;       // the working-state view ...
+    uint8_t* sflags;
+    uint16_t* increments;
+    uint64_t *activation_eligibility, *activation_epoch, *exit_epoch, *withdrawable_epoch;
+    uint32_t* pubkey_leaf;       // 8 words per validator
+    uint32_t* withdrawal_credentials;
+};
+void launch_deposit_apply(hipStream_t s, const DepositApplyArgs& a);
+
 }  // namespace posevo

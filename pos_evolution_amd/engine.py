@@ -185,6 +185,12 @@ REWARDS_INACTIVITY, REWARDS_DELTAS = _abi.PE_REWARDS_INACTIVITY, _abi.PE_REWARDS
 ROOT_BALANCES, ROOT_INACTIVITY, ROOT_PART_PREV, ROOT_PART_CUR, ROOT_VALIDATORS = (
     _abi.PE_ROOT_BALANCES, _abi.PE_ROOT_INACTIVITY, _abi.PE_ROOT_PART_PREV, _abi.PE_ROOT_PART_CUR, _abi.PE_ROOT_VALIDATORS)
 ROOT_ALL = ROOT_BALANCES | ROOT_INACTIVITY | ROOT_PART_PREV | ROOT_PART_CUR | ROOT_VALIDATORS
+DEP_APPENDED, DEP_TOPUP, DEP_IGNORED_BAD_SIGNATURE, DEP_BAD_PROOF = (
+    _abi.PE_DEP_APPENDED, _abi.PE_DEP_TOPUP, _abi.PE_DEP_IGNORED_BAD_SIGNATURE, _abi.PE_DEP_BAD_PROOF)
+# struct pe_deposit_data as a numpy row: 184 bytes, no padding
+DEPOSIT_DTYPE = np.dtype([("pubkey", np.uint8, 48), ("withdrawal_credentials", np.uint8, 32), ("amount", "<u8"),
+                          ("signature", np.uint8, 96)])
+assert DEPOSIT_DTYPE.itemsize == C.sizeof(_abi.pe_deposit_data) == 184
 _ROOT_FIELDS = ((ROOT_BALANCES, "balances"), (ROOT_INACTIVITY, "inactivity_scores"),
                 (ROOT_PART_PREV, "previous_epoch_participation"), (ROOT_PART_CUR, "current_epoch_participation"),
                 (ROOT_VALIDATORS, "validators"))
@@ -1160,6 +1166,70 @@ class Engine:
         self._check(self._lib.pe_ssz_merkleize(self._h, _ptr(ch if ch.size else None, C.c_uint8), ch.size // 32, int(depth),
                                                -1 if mix_length is None else int(mix_length), _ptr(out, C.c_uint8)))
         return out.tobytes()
+
+    # -- deposits -----------------------------------------------------------
+    @staticmethod
+    def _deposit_rows(deposits) -> np.ndarray:
+        """DEPOSIT_DTYPE rows, or an iterable of (pubkey48, withdrawal_credentials32, amount, signature96)."""
+        if isinstance(deposits, np.ndarray) and deposits.dtype == DEPOSIT_DTYPE:
+            return np.ascontiguousarray(deposits)
+        items = list(deposits)
+        rows = np.zeros(len(items), dtype=DEPOSIT_DTYPE)
+        for i, (pk, wc, amount, sig) in enumerate(items):
+            rows[i] = (np.frombuffer(bytes(pk), dtype=np.uint8), np.frombuffer(bytes(wc), dtype=np.uint8), int(amount),
+                       np.frombuffer(bytes(sig), dtype=np.uint8))
+        return rows
+
+    def deposit_params(self, **overrides):
+        """pe_deposit_params with the mainnet defaults, fields replaced by keyword."""
+        p = _abi.pe_deposit_params()
+        self._lib.pe_deposit_params_default(C.byref(p))
+        for k, v in overrides.items():
+            assert hasattr(p, k), k
+            setattr(p, k, int(v))
+        return p
+
+    def deposit_signing_roots(self, deposits, domain: bytes) -> np.ndarray:
+        """compute_signing_root(DepositMessage, domain) of every deposit, hashed on the GPU (pe_deposit_signing_roots):
+        uint8[n, 32].  The caller hashes these to the curve: the results are ``process_deposits``' message points."""
+        rows = self._deposit_rows(deposits)
+        dom = np.frombuffer(bytes(domain), dtype=np.uint8).copy()
+        assert dom.size == 32
+        out = np.zeros((max(rows.size, 1), 32), dtype=np.uint8)
+        self._check(self._lib.pe_deposit_signing_roots(self._h, _ptr(rows if rows.size else None), rows.size, _ptr(dom), _ptr(out)))
+        return out[:rows.size]
+
+    def process_deposits(self, deposits, message_points192=None, proofs=None, eth1_deposit_index: int = 0,
+                         deposit_root: Optional[bytes] = None, params=None) -> dict:
+        """process_deposit for a batch, sequential semantics, over the resident registry (pe_process_deposits).
+        proofs: uint8[n, 33, 32] or None (not checked: genesis); message_points192: uint8[n, 192], H(signing_root_i), needed
+        where a deposit's pubkey is new.  params: ``deposit_params(...)``, a dict of its overrides, or None.
+        -> {"status": int32[n] (DEP_*), "index": uint32[n] (validator credited, 0xFFFFFFFF = none), and pe_deposit_stats}."""
+        rows = self._deposit_rows(deposits)
+        n = rows.size
+        if params is None or isinstance(params, dict):
+            params = self.deposit_params(**(params or {}))
+        pr = None if proofs is None else np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1)
+        assert pr is None or pr.size == n * 33 * 32, "a proof is 33 nodes of 32 bytes"
+        mp = None if message_points192 is None else np.ascontiguousarray(message_points192, dtype=np.uint8).reshape(-1)
+        assert mp is None or mp.size == n * 192, "one 192-byte message point per deposit"
+        root = None if deposit_root is None else np.frombuffer(bytes(deposit_root), dtype=np.uint8).copy()
+        assert root is None or root.size == 32
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        index = np.full(max(n, 1), 0xFFFFFFFF, dtype=np.uint32)
+        st = _abi.pe_deposit_stats()
+        self._check(self._lib.pe_process_deposits(self._h, _ptr(rows if n else None), n, _ptr(pr if n else None),
+                                                  int(eth1_deposit_index), _ptr(root), _ptr(mp if n else None),
+                                                  C.byref(params), _ptr(status), _ptr(index), C.byref(st)))
+        res = {name: int(getattr(st, name)) for name, _ in _abi.pe_deposit_stats._fields_}
+        res["status"], res["index"] = status[:n], index[:n]
+        return res
+
+    def deposit_index_info(self) -> dict:
+        """The pubkey index ``process_deposits`` keeps (pe_profile_deposit_index): slots (0 = none), keys, build_ms."""
+        slots, keys, ms = C.c_uint32(0), C.c_uint64(0), C.c_float(0)
+        self._check(self._lib.pe_profile_deposit_index(self._h, C.addressof(slots), C.addressof(keys), C.addressof(ms)))
+        return {"slots": int(slots.value), "keys": int(keys.value), "build_ms": float(ms.value)}
 
     def g1_sum(self, offsets, index=None, points96=None) -> np.ndarray:
         off = np.ascontiguousarray(offsets, dtype=np.uint32)

@@ -694,6 +694,62 @@ def process_slashings(state, *, proportional_slashing_multiplier: int = 3, epoch
     state.balances[:] = [int(x) for x in e.state_get_balances()[0]]
 
 
+# ----------------------------------------------------------------------------- deposits
+def process_deposits(state, deposits, message_points, *, check_proofs: bool = True, make_validator: Optional[Callable] = None,
+                     **params) -> np.ndarray:
+    """process_deposit (pe:139-175) for ``deposits`` in order, on the GPU (pe_process_deposits): Merkle proofs against
+    ``state.eth1_data.deposit_root`` at ``state.eth1_deposit_index`` (check_proofs False: genesis), the pubkey lookup in a
+    device-side index, proofs of possession for new pubkeys, top-ups and appended validators.  ``state`` must have been bound
+    with ``bind_state``.  message_points[i]: hash_to_curve(compute_signing_root(DepositMessage_i, domain)) as a 192-byte uncompressed
+    G2 point -- ``Engine.deposit_signing_roots`` gives the roots; hash_to_curve is the caller's.
+    make_validator(**fields): how a Validator of the caller's state type is made (default: a SimpleNamespace).
+    A failing proof raises AssertionError, as the reference does, with the state untouched.  -> the statuses (DEP_*).
+    Every call moves the registry up (as process_registry_updates does); the path without any transfer is
+    ``Engine.process_deposits`` over arrays that stay resident.  Keywords replace fields of pe_deposit_params."""
+    from types import SimpleNamespace
+
+    b = _binding(state)
+    assert b is not None, "process_deposits: bind_state(engine, state, ...) first"
+    deposits = list(deposits)
+    vals, n, e = state.validators, len(state.validators), b.engine
+    e.registry_set_epochs(_u64_of((v.activation_epoch for v in vals), n), _u64_of((v.exit_epoch for v in vals), n))
+    b.epochs_resident = True
+    scores = getattr(state, "inactivity_scores", None)
+    e.state_set_balances(_u64_of(state.balances, n), None if scores is None else _u64_of(scores, n),
+                         _u64_of((v.withdrawable_epoch for v in vals), n))
+    e.registry_set_static(np.frombuffer(b"".join(bytes(v.pubkey) for v in vals), dtype=np.uint8).reshape(n, 48),
+                          np.frombuffer(b"".join(bytes(v.withdrawal_credentials) for v in vals), dtype=np.uint8).reshape(n, 32),
+                          _u64_of((v.activation_eligibility_epoch for v in vals), n))
+    rows = [(d.data.pubkey, d.data.withdrawal_credentials, d.data.amount, d.data.signature) for d in deposits]
+    mp = np.frombuffer(b"".join(bytes(m) for m in message_points), dtype=np.uint8)
+    proofs = None
+    if check_proofs:
+        proofs = np.frombuffer(b"".join(b"".join(bytes(x) for x in d.proof) for d in deposits), dtype=np.uint8)
+    res = e.process_deposits(rows, mp, proofs, int(state.eth1_deposit_index),
+                             bytes(state.eth1_data.deposit_root) if check_proofs else None, params)
+    assert res["n_bad_proof"] == 0, "process_deposit: is_valid_merkle_branch failed (pe:141)"
+    state.eth1_deposit_index += len(deposits)
+    p = e.deposit_params(**params)
+    make = make_validator or (lambda **kw: SimpleNamespace(**kw))
+    for d, st, idx in zip(deposits, res["status"], res["index"]):
+        amount = int(d.data.amount)
+        if st == _abi.PE_DEP_APPENDED:
+            far = int(p.far_future_epoch)
+            eff = min(amount - amount % int(p.effective_balance_increment), int(p.max_effective_balance))
+            state.validators.append(make(pubkey=d.data.pubkey, withdrawal_credentials=d.data.withdrawal_credentials,
+                                         effective_balance=eff, slashed=False, activation_eligibility_epoch=far,
+                                         activation_epoch=far, exit_epoch=far, withdrawable_epoch=far))
+            state.balances.append(amount)
+            state.previous_epoch_participation.append(0)
+            state.current_epoch_participation.append(0)
+            if scores is not None:
+                scores.append(0)
+        elif st == _abi.PE_DEP_TOPUP:
+            state.balances[int(idx)] += amount
+    state._last_deposit_stats = {k: v for k, v in res.items() if k not in ("status", "index")}
+    return res["status"]
+
+
 # ----------------------------------------------------------------------------- the active set and what is counted from it
 FAR_FUTURE_EPOCH = 2**64 - 1
 # the constants pe:461-468 and pe:1225-1287 name, mainnet values; pass `preset=` to replace any of them
