@@ -515,7 +515,6 @@ void pe_engine_destroy(pe_engine* h)
     h->d_shuffle_scratch.release();
     h->d_sum_groups.release();
     h->d_sum_lane.release();
-    h->d_points30.release();
     slasher_release(h);
     if (h->comm && rccl().ok) (void)rccl().CommDestroy(h->comm);
     if (h->comm_g1 && rccl().ok) (void)rccl().CommDestroy(h->comm_g1);
@@ -544,14 +543,12 @@ void pe_engine_destroy(pe_engine* h)
         if (a.ev_leg) (void)hipEventDestroy(a.ev_leg);
         if (a.ev_aux) (void)hipEventDestroy(a.ev_aux);
     }
-    for (DevBuf* b : {&h->d_points, &h->d_balance, &h->d_flags, &h->d_incr, &h->d_sbalance, &h->d_sflags, &h->d_vote_key, &h->d_vote_block, &h->d_vote_slot,
-                      &h->d_part_cur, &h->d_part_prev, &h->d_tsize, &h->d_tparent, &h->d_trank, &h->d_tleaf,
+    reg_release(h);  // the per-validator columns (reg_columns.h)
+    for (DevBuf* b : {&h->d_tsize, &h->d_tparent, &h->d_trank, &h->d_tleaf,
                       &h->d_tpos, &h->d_tidx, &h->d_direct, &h->d_weights, &h->d_totals, &h->d_head,
                       &h->d_broot_tab, &h->d_broots, &h->d_bslot_pos,
                       &h->d_partials, &h->d_lane_partials, &h->d_out96, &h->d_tmp_points, &h->d_tmp_be, &h->d_tmp_points30,
-                      &h->d_activation_epoch, &h->d_exit_epoch, &h->d_active, &h->d_active_wg, &h->d_registry_wg,
-                      &h->d_rbalance, &h->d_inactivity, &h->d_withdrawable,
-                      &h->d_pubkey_leaf, &h->d_withdrawal_credentials, &h->d_activation_eligibility, &h->d_ssz_zero,
+                      &h->d_active, &h->d_active_wg, &h->d_registry_wg, &h->d_ssz_zero,
                       &h->d_ssz_validator_roots, &h->d_ssz_level[0], &h->d_ssz_level[1], &h->d_ssz_chunks, &h->d_bls, &h->d_batch, &h->d_verify,
                       &h->d_dep_index, &h->d_deposit})
         b->release();

@@ -7,7 +7,7 @@
 //                             pe_g2_subgroup_check and pairing_run over (pk, H(m)), (-g1, sig): existing code, called --,
 //                             k_deposit_resolve (duplicates inside the batch, statuses, new indices), registry_grow and
 //                             k_deposit_apply
-//   registry_grow             the resident per-validator arrays extended with their contents kept
+//   registry_grow             the resident per-validator columns (reg_columns.h) extended with their contents kept
 // The rules per deposit are deposit_row.h.  Synchronous, one GPU.
 #include "engine_internal.h"
 #include "deposit_row.h"
@@ -26,12 +26,6 @@ static_assert(DEPOSIT_NONE == NONE32, "deposit_row.h: its empty slot is the engi
 namespace posevo {
 
 namespace {
-
-void bytes_to_words(const uint8_t b[32], uint32_t w[8])
-{
-    for (int k = 0; k < 8; ++k)
-        w[k] = ((uint32_t)b[4 * k] << 24) | ((uint32_t)b[4 * k + 1] << 16) | ((uint32_t)b[4 * k + 2] << 8) | b[4 * k + 3];
-}
 
 // The pubkey index covers the registry and leaves room for n_more keys: built where there is none, rebuilt larger where a
 // call outgrows it, otherwise extended by the validators appended since (none, unless an earlier call failed half-way).
@@ -107,25 +101,10 @@ int registry_grow(pe_engine* h, uint64_t n_new)
     if (n_new <= n_old) return PE_OK;
     if (n_new >= 0xFFFFFFFFull) return fail(h, PE_ERR_CAPACITY, "validator index must fit 32 bits");
     committee_sums_drop(h);  // sums over a registry of the old size; a build in flight has read the points before they move
-    uint64_t cap = std::max(h->reg_capacity, n_old);
-    if (n_new > h->reg_capacity) cap = std::max(n_new, 2 * cap);
-    cap = std::min<uint64_t>((cap + 3) & ~uint64_t(3), 0x100000000ull);
-    struct Column { DevBuf* buf; size_t elem; bool held; int fill; };  // fill: the byte the new rows take, -1 = the caller writes them
-    const Column columns[] = {
-        {&h->d_sbalance, 8, true, -1},  {&h->d_sflags, 1, true, -1},       {&h->d_incr, 2, true, -1},
-        {&h->d_activation_epoch, 8, true, -1}, {&h->d_exit_epoch, 8, true, -1}, {&h->d_activation_eligibility, 8, true, -1},
-        {&h->d_withdrawable, 8, true, -1}, {&h->d_pubkey_leaf, 32, true, -1}, {&h->d_withdrawal_credentials, 32, true, -1},
-        {&h->d_rbalance, 8, true, 0},   {&h->d_inactivity, 8, true, 0},    {&h->d_part_cur, 1, true, 0},
-        {&h->d_part_prev, 1, true, 0},  {&h->d_balance, 8, true, 0},       {&h->d_flags, 1, true, 0},
-        {&h->d_vote_key, 8, true, 0},   {&h->d_vote_block, 4, true, 0xFF}, {&h->d_vote_slot, 4, h->cfg.vote_expiry_slots != 0, 0},
-        {&h->d_points, 4 * G1_ROW_WORDS, h->have_points, -1}, {&h->d_points30, 4 * G1_ROW_WORDS, h->have_points && h->points30_valid, -1},
-    };
-    for (const Column& c : columns)
-        if (c.held) HIP_TRY(h, c.buf->ensure(std::max<size_t>(64, c.elem * cap), /*keep=*/true, h->stream));
+    const uint64_t cap = reg_grown_capacity(h->reg_capacity, n_old, n_new);
+    HIP_TRY(h, reg_ensure(h, reg_held(h), cap, /*keep=*/true));
     h->reg_capacity = cap;
-    for (const Column& c : columns)
-        if (c.held && c.fill >= 0)
-            HIP_TRY(h, hipMemsetAsync(c.buf->as<uint8_t>() + c.elem * n_old, c.fill, c.elem * (n_new - n_old), h->stream));
+    HIP_TRY(h, reg_fill(h, reg_held(h), n_old, n_new));
     if (h->d_totals.p) HIP_TRY(h, hipMemsetAsync(h->d_totals.p, 0, h->d_totals.cap, h->stream));  // k_votes' grid changes with n
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->h_flags.resize(n_new, 0);
@@ -171,7 +150,7 @@ int pe_deposit_signing_roots(pe_engine* h, const pe_deposit_data* deposits, uint
     DepositLeavesArgs a{};
     a.rows = w(r_rows);
     a.n = n;
-    bytes_to_words(domain, a.domain);
+    be32_words(domain, a.domain);
     a.leaf = w(r_leaf);
     a.proof_ok = w(r_ok);
     a.signing_roots = w(r_roots);
@@ -229,7 +208,7 @@ int pe_process_deposits(pe_engine* h, const pe_deposit_data* deposits, uint32_t 
     la.n = n;
     la.proofs = proofs ? w(r_proofs) : nullptr;
     la.index0 = eth1_deposit_index;
-    if (proofs) bytes_to_words(deposit_root, la.root);
+    if (proofs) be32_words(deposit_root, la.root);
     la.leaf = w(r_leaf);
     la.proof_ok = w(r_ok);
     launch_deposit_leaves(h->stream, la);

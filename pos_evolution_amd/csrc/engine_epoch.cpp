@@ -46,9 +46,7 @@ int materialise_state_view(pe_engine* h)
 {
     if (h->state_view_set) return PE_OK;
     const uint64_t n = h->n_val;
-    const size_t n4 = (n + 3) & ~size_t(3);
-    HIP_TRY(h, h->d_sbalance.ensure(std::max<size_t>(64, n4 * 8)));
-    HIP_TRY(h, h->d_sflags.ensure(std::max<size_t>(64, n4)));
+    HIP_TRY(h, reg_ensure(h, REG_VIEW, n, /*keep=*/false));  // overwritten below
     if (n) {
         HIP_TRY(h, hipMemcpyAsync(h->d_sbalance.p, h->d_balance.p, 8 * n, hipMemcpyDeviceToDevice, h->stream));
         launch_state_view_from_registry(h->stream, h->d_flags.as<uint8_t>(), h->d_balance.as<uint64_t>(),
@@ -108,16 +106,9 @@ int pe_state_set_validators(pe_engine* h, uint64_t n, const uint64_t* effective_
     if (!h || (n && (!effective_balance || !flags))) return PE_ERR_INVALID_ARG;
     if (n != h->n_val) return fail(h, PE_ERR_INVALID_ARG, "pe_state_set_validators: n differs from the registry size");
     PE_TRY(enter(h));
-    std::vector<uint16_t> incr(n);
-    const uint64_t inc = h->cfg.effective_balance_increment;
-    for (uint64_t i = 0; i < n; ++i) {
-        const uint64_t q = effective_balance[i] / inc;
-        if (q > 0xFFFF) return fail(h, PE_ERR_INVALID_ARG, "effective_balance / increment exceeds 65535");
-        incr[i] = (uint16_t)q;
-    }
-    const size_t n4 = (n + 3) & ~size_t(3);
-    HIP_TRY(h, h->d_sbalance.ensure(std::max<size_t>(64, n4 * 8)));
-    HIP_TRY(h, h->d_sflags.ensure(std::max<size_t>(64, n4)));
+    std::vector<uint16_t> incr;
+    PE_TRY(balance_increments(h, effective_balance, n, incr));
+    HIP_TRY(h, reg_ensure(h, REG_VIEW, n, /*keep=*/false));  // overwritten below
     HIP_TRY(h, hipMemcpyAsync(h->d_sbalance.p, effective_balance, n * 8, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->d_sflags.p, flags, n, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->d_incr.p, incr.data(), n * 2, hipMemcpyHostToDevice, h->stream));
@@ -170,8 +161,7 @@ int pe_registry_set_epochs(pe_engine* h, uint64_t n, const uint64_t* activation_
     if (!h || (n && (!activation_epoch || !exit_epoch))) return PE_ERR_INVALID_ARG;
     PE_TRY(enter(h));
     if (n != h->n_val) return fail(h, PE_ERR_INVALID_ARG, "pe_registry_set_epochs: n differs from the registry size");
-    HIP_TRY(h, h->d_activation_epoch.ensure(std::max<size_t>(64, 8 * n)));
-    HIP_TRY(h, h->d_exit_epoch.ensure(std::max<size_t>(64, 8 * n)));
+    HIP_TRY(h, reg_ensure(h, REG_EPOCHS, n, /*keep=*/false));
     if (n) {
         HIP_TRY(h, hipMemcpyAsync(h->d_activation_epoch.p, activation_epoch, 8 * n, hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipMemcpyAsync(h->d_exit_epoch.p, exit_epoch, 8 * n, hipMemcpyHostToDevice, h->stream));
@@ -290,10 +280,7 @@ int pe_compute_proposers(pe_engine* h, const uint8_t* seeds32, uint32_t n_seeds,
     const size_t off_seed = st.alloc(32ull * n_seeds);
     const size_t off_idx = st.alloc(staged ? 4ull * n_active + 4 : 4);
     uint32_t* sw = st.host<uint32_t>(off_seed);
-    for (uint64_t i = 0; i < 8ull * n_seeds; ++i) {  // the kernels take a seed as 8 big-endian words
-        const uint8_t* b = seeds32 + 4 * i;
-        sw[i] = ((uint32_t)b[0] << 24) | ((uint32_t)b[1] << 16) | ((uint32_t)b[2] << 8) | b[3];
-    }
+    for (uint32_t i = 0; i < n_seeds; ++i) be32_words(seeds32 + 32ull * i, sw + 8ull * i);
     if (staged) memcpy(st.host<uint32_t>(off_idx), active_indices, 4ull * n_active);
     OutBlock ob(h);
     const size_t off_prop = ob.alloc(4ull * n_seeds);
@@ -317,13 +304,7 @@ int pe_state_set_balances(pe_engine* h, uint64_t n, const uint64_t* balances, co
     if (!h || (n && !balances)) return PE_ERR_INVALID_ARG;
     PE_TRY(enter(h));
     if (n != h->n_val) return fail(h, PE_ERR_INVALID_ARG, "pe_state_set_balances: n differs from the registry size");
-    const size_t bytes = std::max<size_t>(64, 8 * n);
-    if (h->d_rbalance.cap < bytes || h->d_inactivity.cap < bytes || h->d_withdrawable.cap < bytes) {
-        h->balances_set = false;  // the arrays are re-allocated: what they held is gone whether or not all three succeed
-        HIP_TRY(h, h->d_rbalance.ensure(bytes));
-        HIP_TRY(h, h->d_inactivity.ensure(bytes));
-        HIP_TRY(h, h->d_withdrawable.ensure(bytes));
-    }
+    HIP_TRY(h, reg_ensure(h, REG_BALANCES, n, /*keep=*/false, &h->balances_set));
     if (n) {
         HIP_TRY(h, hipMemcpyAsync(h->d_rbalance.p, balances, 8 * n, hipMemcpyHostToDevice, h->stream));
         if (inactivity_scores)

@@ -21,7 +21,7 @@ void g1_stream_guard(pe_engine* h, hipStream_t s)
 // current arena, copying the aggregate pubkeys out before k_g1_finish had written them.)
 int build_points30(pe_engine* h, uint64_t n)
 {
-    HIP_TRY(h, h->d_points30.ensure(std::max<size_t>(128, 4ull * G1_ROW_WORDS * n)));
+    HIP_TRY(h, reg_ensure(h, REG_POINTS30, n, /*keep=*/false));
     launch_g1_table_s30(h->stream, h->d_points.as<uint32_t>(), h->d_points30.as<uint32_t>(), n);
     HIP_TRY(h, hipGetLastError());
     h->points30_valid = true;
@@ -467,7 +467,7 @@ int pe_set_pubkeys_compressed(pe_engine* h, uint64_t n, const uint8_t* pubkeys48
     if (n != h->n_val) return fail(h, PE_ERR_INVALID_ARG, "pe_set_pubkeys_compressed: n differs from the registry size");
     PE_TRY(enter(h));
     if (n == 0) return PE_OK;
-    HIP_TRY(h, h->d_points.ensure(4ull * G1_ROW_WORDS * n));
+    HIP_TRY(h, reg_ensure(h, REG_POINTS, n, /*keep=*/false));
     h->have_points = false;
     h->points30_valid = false;
     committee_sums_drop(h);

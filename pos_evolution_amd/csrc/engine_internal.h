@@ -17,7 +17,7 @@
 //                      effective-balance hysteresis
 //   engine_deposit.cpp process_deposit over the resident registry: the pubkey index, proofs, verdicts of new keys, registry_grow
 // What host and device share of an attestation row: where its bits and its committee lie (att_row.h) and which status it
-// gets (att_rules.h).
+// gets (att_rules.h).  The per-validator device arrays are one table (reg_columns.h), sized, filled and released through it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -45,6 +45,7 @@
 #include "att_rules.h"
 #include "carve.h"
 #include "kernels.h"
+#include "reg_columns.h"
 
 namespace posevo {
 
@@ -317,7 +318,8 @@ struct pe_engine {
     uint64_t dep_index_keys = 0;
     float dep_index_build_ms = 0;  // pe_profile_deposit_index: the last full build, launch to completion
     DevBuf d_deposit;              // one call's workspace: the Layout of pe_process_deposits
-    uint64_t reg_capacity = 0;     // validators every resident per-validator array has room for (registry_grow doubles it)
+    uint64_t reg_capacity = 0;     // validators registry_grow last sized every held column for (it doubles it: reg_grown_capacity);
+                                   // the setters size a column for the registry alone, and no column ever shrinks
     // ---- pe_verify_resident (engine_resident_verify.cpp) ----
     // which aggregate the arena's d_res_points belong to: valid while that is still the handle's last aggregate of either kind
     struct ResidentVerify {
@@ -646,6 +648,52 @@ struct ProfScope {
     }
 };
 
+// ------------------------------------------------------------------ the per-validator columns (reg_columns.h)
+// The table's rows as members of the handle, and the four things a call site does with a group of columns.  `groups` is a set
+// of RegGroup bits.  A column is sized here and nowhere else: reg_column_bytes of the validators it is to hold.
+static_assert(REG_POINT_BYTES == 4 * G1_ROW_WORDS, "reg_columns.h: a row of the pubkey table is kernels.h' G1_ROW_WORDS words");
+#define REG_COLUMN_MEMBER(member, elem, group, fill) &pe_engine::member,
+constexpr DevBuf pe_engine::* REG_MEMBER[REG_N_COLUMNS] = {REG_COLUMNS(REG_COLUMN_MEMBER)};
+#undef REG_COLUMN_MEMBER
+// The groups this handle holds: what registry_grow extends and what takes a fill.  The latest messages' slots exist in the
+// vote-expiry variant only, the pubkey table where keys are loaded, its S30 form where build_points30 has run.
+inline uint32_t reg_held(const pe_engine* h)
+{
+    return REG_ALL_GROUPS & ~(h->cfg.vote_expiry_slots ? 0u : REG_VOTE_SLOT) & ~(h->have_points ? 0u : REG_POINTS) &
+           ~(h->have_points && h->points30_valid ? 0u : REG_POINTS30);
+}
+// Room for n validators in every column of `groups`.  keep: a column that moves takes its contents along (on the engine's
+// stream, waited for).  set_flag: the groups' "set" flag, cleared before the first re-allocation -- what the columns held is gone
+// whether or not every allocation succeeds; it stays as it is where every column is large enough already.
+inline hipError_t reg_ensure(pe_engine* h, uint32_t groups, uint64_t n, bool keep, bool* set_flag = nullptr)
+{
+    for (size_t c = 0; c < REG_N_COLUMNS; ++c) {
+        if (!(REG_COLUMN[c].group & groups)) continue;
+        DevBuf& b = h->*REG_MEMBER[c];
+        const size_t bytes = reg_column_bytes(REG_COLUMN[c].elem, n);
+        if (set_flag && b.cap < bytes) *set_flag = false;
+        const hipError_t e = b.ensure(bytes, keep, h->stream);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+// Rows [row0, reg_rows(n)) of every column of `groups` that has one take the table's fill byte, on the engine's stream.
+inline hipError_t reg_fill(pe_engine* h, uint32_t groups, uint64_t row0, uint64_t n)
+{
+    for (size_t c = 0; c < REG_N_COLUMNS; ++c) {
+        const RegColumn& col = REG_COLUMN[c];
+        if (!(col.group & groups) || col.fill < 0 || reg_rows(n) <= row0) continue;
+        const hipError_t e = hipMemsetAsync((h->*REG_MEMBER[c]).as<uint8_t>() + col.elem * row0, col.fill,
+                                            col.elem * (reg_rows(n) - row0), h->stream);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+inline void reg_release(pe_engine* h)
+{
+    for (size_t c = 0; c < REG_N_COLUMNS; ++c) (h->*REG_MEMBER[c]).release();
+}
+
 // ------------------------------------------------------------------ completion of batch calls (engine_core.cpp)
 int run_deferred(pe_engine* h);
 int complete_arena(pe_engine* h, int ai);
@@ -728,6 +776,12 @@ inline uint32_t get_ancestor(const pe_engine* h, uint32_t idx, uint64_t slot)
     while (h->blocks[idx].slot > slot && h->blocks[idx].parent != NONE32) idx = h->blocks[idx].parent;
     return idx;
 }
+// 32 bytes as the 8 big-endian words the kernels take a seed, a root or a domain as
+inline void be32_words(const uint8_t b[32], uint32_t w[8])
+{
+    for (int k = 0; k < 8; ++k)
+        w[k] = ((uint32_t)b[4 * k] << 24) | ((uint32_t)b[4 * k + 1] << 16) | ((uint32_t)b[4 * k + 2] << 8) | b[4 * k + 3];
+}
 inline uint64_t isqrt64(uint64_t n)
 {
     uint64_t x = n, y = (x + 1) / 2;
@@ -742,7 +796,8 @@ int insert_block(pe_engine* h, const Root& root, uint32_t parent, uint64_t slot,
 CommitteeTable* find_table(pe_engine* h, uint64_t epoch);
 int run_tree(pe_engine* h, uint64_t* d_direct, const VoteTotals* d_totals, int clear_direct, uint32_t* head_out,
              uint32_t* async_word = nullptr);
-int ensure_validator_arrays(pe_engine* h, uint64_t n);
+// bal[i] / effective_balance_increment of n validators as the 16-bit increments the kernels weigh with; refused beyond 65535
+int balance_increments(pe_engine* h, const uint64_t* bal, uint64_t n, std::vector<uint16_t>& out);
 int upload_balances(pe_engine* h, uint64_t n, const uint64_t* bal, const uint8_t* flags);
 // the active set of a shuffle: NULL = validators 0 .. n_active - 1, else distinct indices into the registry
 // ... or PE_ACTIVE_RESIDENT = the list pe_active_set left on the device (n_active must be its length)
@@ -761,10 +816,10 @@ void resident_balances_drop(pe_engine* h);
 void registry_static_drop(pe_engine* h);
 // a working-state view that still mirrors the registry becomes a view of its own, flags included (engine_epoch.cpp)
 int materialise_state_view(pe_engine* h);
-// Every resident per-validator array gets room for n_new validators with its contents kept (capacity doubling), the rows
-// [n_val, n_new) take the values of a validator nobody has written yet (zero balances, scores, participation and justified
-// data, no latest message) and n_val becomes n_new; what is derived from n -- the resident active list, the committee sums --
-// is dropped.  The caller writes the rows' other columns (engine_deposit.cpp).
+// Every column the handle holds (reg_columns.h) gets room for n_new validators with its contents kept (capacity doubling), the
+// rows [n_val, reg_rows(n_new)) take the table's fill -- a validator nobody has written yet: zero balances, scores, participation
+// and justified data, no latest message -- and n_val becomes n_new; what is derived from n -- the resident active list, the
+// committee sums -- is dropped.  The caller writes the rows' other columns (engine_deposit.cpp).
 int registry_grow(pe_engine* h, uint64_t n_new);
 
 // Re-pack one attestation's bits into 32-bit words (zero padded, masked to n_use bits); returns popcount.

@@ -128,14 +128,8 @@ int pe_registry_set_static(pe_engine* h, uint64_t n, const uint8_t* pubkeys48, c
     if (!h || (n && (!pubkeys48 || !withdrawal_credentials32 || !activation_eligibility_epoch))) return PE_ERR_INVALID_ARG;
     PE_TRY(enter(h));
     if (n != h->n_val) return fail(h, PE_ERR_INVALID_ARG, "pe_registry_set_static: n differs from the registry size");
-    const size_t b32 = std::max<size_t>(64, 32 * n), b8 = std::max<size_t>(64, 8 * n);
     h->dep_index_slots = 0;  // the leaves are replaced: the pubkey index over the old ones goes with them
-    if (h->d_pubkey_leaf.cap < b32 || h->d_withdrawal_credentials.cap < b32 || h->d_activation_eligibility.cap < b8) {
-        h->static_set = false;  // re-allocated: what they held is gone whether or not all three succeed
-        HIP_TRY(h, h->d_pubkey_leaf.ensure(b32));
-        HIP_TRY(h, h->d_withdrawal_credentials.ensure(b32));
-        HIP_TRY(h, h->d_activation_eligibility.ensure(b8));
-    }
+    HIP_TRY(h, reg_ensure(h, REG_STATIC, n, /*keep=*/false, &h->static_set));
     if (n) {
         h->static_set = false;
         HIP_TRY(h, hipMemcpyAsync(h->d_withdrawal_credentials.p, withdrawal_credentials32, 32 * n, hipMemcpyHostToDevice, h->stream));

@@ -219,26 +219,26 @@ uint32_t pack_bits(const uint8_t* src, uint32_t n_use, uint32_t* dst_words)
     return cnt;
 }
 
-int ensure_validator_arrays(pe_engine* h, uint64_t n)
+int balance_increments(pe_engine* h, const uint64_t* bal, uint64_t n, std::vector<uint16_t>& out)
 {
-    const size_t n4 = (n + 3) & ~size_t(3);
-    HIP_TRY(h, h->d_balance.ensure(std::max<size_t>(64, n4 * 8)));
-    HIP_TRY(h, h->d_flags.ensure(std::max<size_t>(64, n4)));
-    HIP_TRY(h, h->d_incr.ensure(std::max<size_t>(64, n4 * 2)));
+    out.resize(n);
+    const uint64_t inc = h->cfg.effective_balance_increment;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t q = bal[i] / inc;
+        if (q > 0xFFFF) return fail(h, PE_ERR_INVALID_ARG, "effective_balance / increment exceeds 65535");
+        out[i] = (uint16_t)q;
+    }
     return PE_OK;
 }
 
 int upload_balances(pe_engine* h, uint64_t n, const uint64_t* bal, const uint8_t* flags)
 {
-    std::vector<uint16_t> incr(n);
-    const uint64_t inc = h->cfg.effective_balance_increment;
-    for (uint64_t i = 0; i < n; ++i) {
-        const uint64_t q = bal[i] / inc;
-        if (q > 0xFFFF) return fail(h, PE_ERR_INVALID_ARG, "effective_balance / increment exceeds 65535");
-        incr[i] = (uint16_t)q;
-    }
-    int rc = ensure_validator_arrays(h, n);
-    if (rc) return rc;
+    std::vector<uint16_t> incr;
+    PE_TRY(balance_increments(h, bal, n, incr));
+    HIP_TRY(h, reg_ensure(h, REG_JUSTIFIED, n, /*keep=*/false));  // overwritten below
+    // the view: overwritten below while it mirrors the registry; one of its own keeps its rows and is sized for the registry
+    // (pe_ffg_balances and the flag passes read n_val rows of it)
+    HIP_TRY(h, reg_ensure(h, REG_VIEW, n, /*keep=*/h->state_view_set));
     // keep equivocation marks across balance refreshes (equivocating_indices only grows, pe:1459-1461)
     std::vector<uint8_t> f(n);
     for (uint64_t i = 0; i < n; ++i) {
@@ -249,9 +249,6 @@ int upload_balances(pe_engine* h, uint64_t n, const uint64_t* bal, const uint8_t
     HIP_TRY(h, hipMemcpyAsync(h->d_balance.p, bal, n * 8, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->d_flags.p, f.data(), n, hipMemcpyHostToDevice, h->stream));
     if (!h->state_view_set) {  // the working state mirrors the registry until pe_state_set_validators says otherwise
-        const size_t n4 = (n + 3) & ~size_t(3);
-        HIP_TRY(h, h->d_sbalance.ensure(std::max<size_t>(64, n4 * 8)));
-        HIP_TRY(h, h->d_sflags.ensure(std::max<size_t>(64, n4)));
         std::vector<uint8_t> sf(n);
         for (uint64_t i = 0; i < n; ++i)  // active now => also counted as active in the previous epoch
             sf[i] = (uint8_t)((flags[i] & (PE_VAL_ACTIVE | PE_VAL_SLASHED)) | ((flags[i] & PE_VAL_ACTIVE) ? PE_VAL_ACTIVE_PREV : 0));
@@ -360,9 +357,7 @@ int pe_store_init(pe_engine* h, uint64_t genesis_time, uint64_t anchor_slot, con
     h->rr.valid = false;
     PE_TRY(slasher_reset(h));  // what the validators of the previous store attested says nothing about this one
     if (h->n_val) {
-        const size_t n4 = (h->n_val + 3) & ~size_t(3);
-        HIP_TRY(h, hipMemsetAsync(h->d_part_cur.p, 0, n4, h->stream));
-        HIP_TRY(h, hipMemsetAsync(h->d_part_prev.p, 0, n4, h->stream));
+        HIP_TRY(h, reg_fill(h, REG_PARTICIPATION, 0, h->n_val));
         // the working state mirrors the registry again until pe_state_set_validators says otherwise
         HIP_TRY(h, hipMemcpyAsync(h->d_sbalance.p, h->d_balance.p, 8 * h->n_val, hipMemcpyDeviceToDevice, h->stream));
         launch_state_view_from_registry(h->stream, h->d_flags.as<uint8_t>(), h->d_balance.as<uint64_t>(),
@@ -383,9 +378,7 @@ int pe_store_init(pe_engine* h, uint64_t genesis_time, uint64_t anchor_slot, con
     for (auto& f : h->h_flags) f &= (uint8_t)~PE_VAL_EQUIVOCATING;        // equivocating_indices = set()
     if (h->n_val) {
         HIP_TRY(h, hipMemcpyAsync(h->d_flags.p, h->h_flags.data(), h->n_val, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemsetAsync(h->d_vote_key.p, 0, h->n_val * 8, h->stream));       // latest_messages = {}
-        HIP_TRY(h, hipMemsetAsync(h->d_vote_block.p, 0xFF, h->n_val * 4, h->stream));
-        if (h->cfg.vote_expiry_slots) HIP_TRY(h, hipMemsetAsync(h->d_vote_slot.p, 0, h->n_val * 4, h->stream));
+        HIP_TRY(h, reg_fill(h, reg_held(h) & (REG_VOTES | REG_VOTE_SLOT), 0, h->n_val));  // latest_messages = {}
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
     h->initialised = true;
@@ -401,22 +394,11 @@ int pe_set_validators(pe_engine* h, uint64_t n, const uint8_t* pubkeys96, const 
     const uint64_t old_n = h->n_val;
     int rc = upload_balances(h, n, effective_balance, flags);
     if (rc) return rc;
-    const size_t n4 = (n + 3) & ~size_t(3);
-    HIP_TRY(h, h->d_vote_key.ensure(std::max<size_t>(64, n4 * 8), true, h->stream));
-    HIP_TRY(h, h->d_vote_block.ensure(std::max<size_t>(64, n4 * 4), true, h->stream));
-    if (h->cfg.vote_expiry_slots) HIP_TRY(h, h->d_vote_slot.ensure(std::max<size_t>(64, n4 * 4), true, h->stream));
-    HIP_TRY(h, h->d_part_cur.ensure(std::max<size_t>(64, n4), true, h->stream));
-    HIP_TRY(h, h->d_part_prev.ensure(std::max<size_t>(64, n4), true, h->stream));
-    if (n > old_n) {  // new validators: no latest message, no participation
-        HIP_TRY(h, hipMemsetAsync(h->d_vote_key.as<uint64_t>() + old_n, 0, (n4 - old_n) * 8, h->stream));
-        HIP_TRY(h, hipMemsetAsync(h->d_vote_block.as<uint32_t>() + old_n, 0xFF, (n4 - old_n) * 4, h->stream));
-        if (h->cfg.vote_expiry_slots)
-            HIP_TRY(h, hipMemsetAsync(h->d_vote_slot.as<uint32_t>() + old_n, 0, (n4 - old_n) * 4, h->stream));
-        HIP_TRY(h, hipMemsetAsync(h->d_part_cur.as<uint8_t>() + old_n, 0, n4 - old_n, h->stream));
-        HIP_TRY(h, hipMemsetAsync(h->d_part_prev.as<uint8_t>() + old_n, 0, n4 - old_n, h->stream));
-    }
+    const uint32_t kept = reg_held(h) & (REG_VOTES | REG_VOTE_SLOT | REG_PARTICIPATION);
+    HIP_TRY(h, reg_ensure(h, kept, n, /*keep=*/true));
+    if (n > old_n) HIP_TRY(h, reg_fill(h, kept, old_n, n));  // new validators: no latest message, no participation
     if (pubkeys96 && n) {
-        HIP_TRY(h, h->d_points.ensure(4ull * G1_ROW_WORDS * n));
+        HIP_TRY(h, reg_ensure(h, REG_POINTS, n, /*keep=*/false));
         h->points30_valid = false;
         committee_sums_drop(h);  // sums over the old points (a build in flight is waited for); the next table build makes new ones
         // convert in chunks through a bounded device staging buffer
@@ -615,6 +597,19 @@ int pe_on_attester_slashing(pe_engine* h, const pe_attestation* d1, const uint64
     return pe_mark_equivocating(h, inter.data(), inter.size());  // pe:1459-1461
 }
 
+// A table's device arrays for n_members members in n_committees committees; inverse: the validator -> (committee, position)
+// map of a partition as well, over the registry as it is now.
+static hipError_t table_ensure(pe_engine* h, CommitteeTable* t, uint64_t n_members, uint32_t n_committees, bool inverse)
+{
+    hipError_t e = t->d_members.ensure(std::max<size_t>(64, 4ull * n_members));
+    if (e == hipSuccess) e = t->d_offsets.ensure(4ull * (n_committees + 1));
+    if (e == hipSuccess && inverse) e = t->d_inv_comm.ensure(4ull * h->n_val);
+    if (e == hipSuccess && inverse) e = t->d_inv_pos.ensure(4ull * h->n_val);
+    return e;
+}
+// the swap-or-not shuffle's scratch: per round the source hashes of nb blocks of 256 positions (8 words each) | the pivots
+static size_t shuffle_scratch_bytes(uint32_t nb, uint32_t rounds) { return std::max<size_t>(64, 32ull * nb * rounds + 4ull * rounds + 64); }
+
 int pe_set_committees(pe_engine* h, uint64_t epoch, uint32_t n_committees, const uint32_t* offsets,
                       const uint32_t* members)
 {
@@ -655,13 +650,10 @@ int pe_set_committees(pe_engine* h, uint64_t epoch, uint32_t n_committees, const
     }
     t->sums_valid = t->sums_wanted = false;
     if (t->ev_sums) HIP_TRY(h, hipStreamWaitEvent(h->stream, t->ev_sums, 0));  // an earlier build still reads the arrays rewritten below
-    HIP_TRY(h, t->d_members.ensure(std::max<size_t>(64, 4ull * total)));
-    HIP_TRY(h, t->d_offsets.ensure(4ull * (n_committees + 1)));
+    HIP_TRY(h, table_ensure(h, t, total, n_committees, partition && h->n_val));
     HIP_TRY(h, hipMemcpyAsync(t->d_members.p, members, 4ull * total, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(t->d_offsets.p, offsets, 4ull * (n_committees + 1), hipMemcpyHostToDevice, h->stream));
     if (partition && h->n_val) {
-        HIP_TRY(h, t->d_inv_comm.ensure(4ull * h->n_val));
-        HIP_TRY(h, t->d_inv_pos.ensure(4ull * h->n_val));
         launch_invert_committees(h->stream, t->d_members.as<uint32_t>(), t->d_offsets.as<uint32_t>(), n_committees,
                                  t->d_inv_comm.as<uint32_t>(), t->d_inv_pos.as<uint32_t>(), h->n_val);
         HIP_TRY(h, hipGetLastError());
@@ -769,6 +761,7 @@ static int compute_committees_impl(pe_engine* h, uint64_t epoch, const uint8_t s
     t->sums_valid = t->sums_wanted = false;
     if (!asynchronous && t->ev_sums) HIP_TRY(h, hipStreamWaitEvent(h->stream, t->ev_sums, 0));
     const uint32_t nb = (n_active + 255) / 256;
+    HIP_TRY(h, table_ensure(h, t, n_active, n_committees, h->n_val != 0));
     if (asynchronous) {
         // Nothing of this call touches the pipelines' arenas or the engine's stream: the table carries its own small
         // staging pair (seed | offsets | active indices), the shuffle has its own stream and scratch, and the table's
@@ -784,17 +777,10 @@ static int compute_committees_impl(pe_engine* h, uint64_t epoch, const uint8_t s
         HIP_TRY(h, t->d_stage.ensure(bytes));
         uint8_t* hs = t->h_stage.as<uint8_t>();
         uint32_t* sw = reinterpret_cast<uint32_t*>(hs + o_seed);
-        for (int i = 0; i < 8; ++i)
-            sw[i] = ((uint32_t)seed[4 * i] << 24) | ((uint32_t)seed[4 * i + 1] << 16) | ((uint32_t)seed[4 * i + 2] << 8) | seed[4 * i + 3];
+        be32_words(seed, sw);
         memcpy(hs + o_offs, offsets.data(), 4ull * (n_committees + 1));
         if (staged && n_active) memcpy(hs + o_idx, active_indices, 4ull * n_active);
-        HIP_TRY(h, t->d_members.ensure(std::max<size_t>(64, 4ull * n_active)));
-        HIP_TRY(h, t->d_offsets.ensure(4ull * (n_committees + 1)));
-        HIP_TRY(h, h->d_shuffle_scratch.ensure(std::max<size_t>(64, 32ull * nb * shuffle_round_count + 4ull * shuffle_round_count + 64)));
-        if (h->n_val) {
-            HIP_TRY(h, t->d_inv_comm.ensure(4ull * h->n_val));
-            HIP_TRY(h, t->d_inv_pos.ensure(4ull * h->n_val));
-        }
+        HIP_TRY(h, h->d_shuffle_scratch.ensure(shuffle_scratch_bytes(nb, shuffle_round_count)));
         hipStream_t ps = h->prep_stream;
         // the sums' build of the table this slot held reads the arrays the shuffle is about to rewrite, on its own stream
         if (t->ev_sums) HIP_TRY(h, hipStreamWaitEvent(ps, t->ev_sums, 0));
@@ -836,13 +822,10 @@ static int compute_committees_impl(pe_engine* h, uint64_t epoch, const uint8_t s
     const size_t off_idx = st.alloc(staged ? 4ull * n_active + 4 : 4);
     const size_t off_offs = st.alloc(4ull * (n_committees + 1));
     uint32_t* sw = st.host<uint32_t>(off_seed);
-    for (int i = 0; i < 8; ++i)
-        sw[i] = ((uint32_t)seed[4 * i] << 24) | ((uint32_t)seed[4 * i + 1] << 16) | ((uint32_t)seed[4 * i + 2] << 8) | seed[4 * i + 3];
+    be32_words(seed, sw);
     if (staged && n_active) memcpy(st.host<uint32_t>(off_idx), active_indices, 4ull * n_active);
     memcpy(st.host<uint32_t>(off_offs), offsets.data(), 4ull * (n_committees + 1));
-    HIP_TRY(h, t->d_members.ensure(std::max<size_t>(64, 4ull * n_active)));
-    HIP_TRY(h, t->d_offsets.ensure(4ull * (n_committees + 1)));
-    HIP_TRY(h, h->d_tmp_be.ensure(std::max<size_t>(64, 32ull * nb * shuffle_round_count + 4ull * shuffle_round_count + 64)));
+    HIP_TRY(h, h->d_tmp_be.ensure(shuffle_scratch_bytes(nb, shuffle_round_count)));
     HIP_TRY(h, st.upload());
     hipStream_t cs = h->stream;
     uint32_t* d_source = h->d_tmp_be.as<uint32_t>();
@@ -851,12 +834,9 @@ static int compute_committees_impl(pe_engine* h, uint64_t epoch, const uint8_t s
                    active_list_dev(h, active_indices, st.dev<uint32_t>(off_idx)), t->d_members.as<uint32_t>());
     HIP_TRY(h, hipMemcpyAsync(t->d_offsets.p, st.dev<uint32_t>(off_offs), 4ull * (n_committees + 1),
                               hipMemcpyDeviceToDevice, cs));
-    if (h->n_val) {
-        HIP_TRY(h, t->d_inv_comm.ensure(4ull * h->n_val));
-        HIP_TRY(h, t->d_inv_pos.ensure(4ull * h->n_val));
+    if (h->n_val)
         launch_invert_committees(cs, t->d_members.as<uint32_t>(), t->d_offsets.as<uint32_t>(), n_committees,
                                  t->d_inv_comm.as<uint32_t>(), t->d_inv_pos.as<uint32_t>(), h->n_val);
-    }
     HIP_TRY(h, hipGetLastError());
     lap.mark("comm.2_launch");
     // the table stays on the device; the members come back only on request, through the pinned block (a pageable
