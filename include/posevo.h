@@ -708,8 +708,8 @@ typedef struct pe_deposit_stats {
     uint64_t n_validators;             /* pe_num_validators(h) after the call */
 } pe_deposit_stats;
 /* out_roots32[32 i ..] = compute_signing_root(DepositMessage(deposit i), domain) (pe:157-163), hashed on the device:
- * H(hash_tree_root(DepositMessage) || domain).  hash_to_curve of these is the caller's, as for every BLS call here; its
- * results are pe_process_deposits' message_points192.  Synchronous; needs no registry. */
+ * H(hash_tree_root(DepositMessage) || domain).  pe_hash_to_g2 of these (tag: Ethereum's signature DST) gives
+ * pe_process_deposits' message_points192.  Synchronous; needs no registry. */
 int pe_deposit_signing_roots(pe_engine* h, const pe_deposit_data* deposits, uint32_t n, const uint8_t domain[32],
                              uint8_t* out_roots32);
 /* process_deposit for n deposits, with the reference's semantics applied sequentially in batch order: a deposit's pubkey is
@@ -936,8 +936,8 @@ int pe_g2_subgroup_check(pe_engine* h, const uint8_t* points192, uint64_t n, int
  * an empty group gives 1 (the empty product); infinity on either side contributes 1.
  * Subgroup membership is the caller's: pe_g1_key_validate / pe_g2_subgroup_check.
  * Synchronous (completes open pipelines first); one GPU: PE_ERR_STATE on a handle with pe_dist_init* active.
- * offsets not monotone or past n_pairs: PE_ERR_INVALID_ARG.  Not computed here: hash_to_curve (the caller supplies the
- * message point H(m) in G2).  One final exponentiation per group; pe_batch_verify below pays one per call. */
+ * offsets not monotone or past n_pairs: PE_ERR_INVALID_ARG.  Not computed here: hash_to_curve (pe_hash_to_g2 makes the
+ * message point H(m) in G2; these calls take it).  One final exponentiation per group; pe_batch_verify below pays one per call. */
 #define PE_BLS_VALID 1
 #define PE_BLS_INVALID 0
 #define PE_BLS_BAD_POINT 2
@@ -981,7 +981,7 @@ int pe_batch_fast_aggregate_verify(pe_engine* h, const uint32_t* index, const ui
  *   index          host; member j's signature is signatures96[index[j]]; NULL: member j's is signatures96[j]
  *   signer         host; member j's validator index: its pubkey is the registry's (taken as KeyValidated)
  *   offsets        host; group g = members [offsets[g], offsets[g+1])
- *   message_points192   H(m_g), one 192-byte G2 point per group (hash_to_curve is the caller's)
+ *   message_points192   H(m_g), one 192-byte G2 point per group (pe_hash_to_g2 makes them)
  *   scalars        host; one non-zero 64-bit r_j per member, or NULL: drawn from getrandom.  NULL is the production mode.
  *                  Caller-supplied scalars MUST BE UNPREDICTABLE to the signers, exactly as for pe_batch_verify: with r_a = r_b
  *                  known, sig_a + D and sig_b - D both pass.  With secret scalars a wrong 1 has probability <= 2^-64 per group.
@@ -1005,7 +1005,7 @@ int pe_verify_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t n, 
  * key and the signature that aggregate left in device memory -- no wait for out_aggpk96 / out_signatures96, no second
  * decompression, no upload of points the device already holds.
  *   message_points192   n_points message points H(m), 192-byte G2 wire form; host memory, or device memory (read in place when
- *                       16-byte aligned, copied otherwise).  hash_to_curve is the caller's.
+ *                       16-byte aligned, copied otherwise).  pe_hash_to_g2 writes them there.
  *   point_of_row        host memory, one entry per INPUT row of that aggregate: the group a row went into takes the point of
  *                       its first row (pe_attestation order of appearance).  NULL: group g takes message_points192[g].
  *   flags               PE_VERIFY_APPLY: on the device, sig_valid of every group decided by rows 2-4 below becomes
@@ -1029,6 +1029,33 @@ int pe_verify_signatures(pe_engine* h, const uint8_t* signatures96, uint64_t n, 
 #define PE_VERIFY_APPLY  0x1u
 int pe_verify_resident(pe_engine* h, const uint8_t* message_points192, uint32_t n_points, const uint32_t* point_of_row,
                        uint32_t flags, uint32_t cap, int32_t* verdict);
+
+/* ---- hash_to_curve: the message points H(m) from messages (RFC 9380) -------- */
+/* Suite BLS12381G2_XMD:SHA-256_SSWU_RO_: hash_to_field by expand_message_xmd over SHA-256, the simplified SWU map onto the
+ * isogenous curve, the 3-isogeny to the twist, the sum of the two mapped points, clear_cofactor.  What comes out is the 192-byte
+ * G2 wire form (x.c1 | x.c0 | y.c1 | y.c0) that pe_fast_aggregate_verify, pe_batch_verify, pe_verify_signatures,
+ * pe_verify_resident and pe_process_deposits take as message points.
+ *   msgs      n messages of msg_len bytes each, back to back; 0 <= msg_len <= 255.  Host memory, or device memory (read in
+ *             place when 16-byte aligned, copied otherwise).  NULL is allowed for msg_len == 0.
+ *   dst       the domain separation tag, host memory, 1 <= dst_len <= 255 (Ethereum's signatures:
+ *             "BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_")
+ *   out192    n x 192 bytes.  Host memory, or device memory as pe_verify_resident accepts its message points (written in
+ *             place when 16-byte aligned, through a copy otherwise): signing roots -> H(m) -> verdict then never cross to
+ *             the host.
+ *   status    nullable, host memory, one per message: 0, or 1 where H(m) is the identity (out192: 0x40 and zeros) -- no known
+ *             message gives it; the verification calls refuse an identity message point.
+ * Synchronous, one GPU.  PE_ERR_STATE under pe_dist_init* and inside a pipeline (between pe_pipeline_begin* and its end);
+ * PE_ERR_INVALID_ARG for dst_len outside 1 .. 255, msg_len above 255 or a missing array; PE_ERR_CAPACITY above 2^24 messages.
+ * n == 0 returns PE_OK.  An error writes nothing. */
+int pe_hash_to_g2(pe_engine* h, const uint8_t* msgs, uint32_t n, uint32_t msg_len, const uint8_t* dst, uint32_t dst_len,
+                  uint8_t* out192, int32_t* status);
+/* The same from field elements -- the RFC's own seam behind hash_to_field: out192[i] = clear_cofactor(map_to_curve(u0_i) +
+ * map_to_curve(u1_i)).
+ *   u_be      host memory, n x 192 bytes: u0.c0 | u0.c1 | u1.c0 | u1.c1 (c0 + c1 i), each a 48-byte big-endian integer below p
+ *   out192    as pe_hash_to_g2's
+ * u = 0 takes the map's exceptional case, u1 = u0 the doubling, u1 = -u0 gives the identity.  Errors as pe_hash_to_g2;
+ * PE_ERR_INVALID_ARG also for a word that is not below p. */
+int pe_map_to_g2(pe_engine* h, const uint8_t* u_be, uint32_t n, uint8_t* out192);
 
 /* ---- multi-GPU exchange (validator-range shards) ----------- */
 /* Each rank owns a contiguous validator range and the whole (small) block table.

@@ -26,6 +26,7 @@ PE_SIG_STATUS_IDENTITY = 4  # pe_verify_signatures: the signature is the point a
 PE_BLS_INVALID, PE_BLS_VALID, PE_BLS_BAD_POINT, PE_BLS_UNDECIDED = 0, 1, 2, 3
 PE_VERIFY_APPLY = 0x1  # pe_verify_resident: AND the verdict into the group's sig_valid on the device
 PE_VERIFY_RESIDENT_STATS = 11
+ETH2_DST = b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"  # pe_hash_to_g2: the domain separation tag of Ethereum's signatures
 NONE32 = 0xFFFFFFFF
 
 PE_VAL_ACTIVE, PE_VAL_SLASHED, PE_VAL_EQUIVOCATING, PE_VAL_ACTIVE_PREV = 0x01, 0x02, 0x04, 0x08
@@ -252,6 +253,8 @@ SIGNATURES = {
     "pe_deposit_signing_roots": (C.c_int, [_H, _u8p, C.c_uint32, _u8p, _u8p]),
     "pe_process_deposits": (C.c_int, [_H, _u8p, C.c_uint32, _u8p, C.c_uint64, _u8p, _u8p, _P(pe_deposit_params), _i32p, _u32p,
                                       _P(pe_deposit_stats)]),
+    "pe_hash_to_g2": (C.c_int, [_H, _u8p, C.c_uint32, C.c_uint32, _u8p, C.c_uint32, _u8p, _i32p]),
+    "pe_map_to_g2": (C.c_int, [_H, _u8p, C.c_uint32, _u8p]),
     "pe_g1_sum": (C.c_int, [_H, _u8p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u8p]),
     "pe_prune": (C.c_int, [_H, C.c_void_p]),
     "pe_set_block_checkpoints": (C.c_int, [_H, C.c_uint32, C.c_uint64, _u8p, C.c_uint64, _u8p]),

@@ -1,7 +1,7 @@
 // engine_bls.cpp -- the pairing-product check and FastAggregateVerify on the device.
 //   pe_pairing_check          per group: prod e(P_j, Q_j) == 1
 //   pe_fast_aggregate_verify  per group: e(sum of the group's registry pubkeys, H(m)) e(-g1, signature) == 1; the sum goes the
-//                             route of pe_g1_sum, H(m) is the caller's (hash_to_curve is out of scope)
+//                             route of pe_g1_sum, H(m) comes in as a point (pe_hash_to_g2 makes it: engine_h2c.cpp)
 //   pe_profile_pairing_gt     the value the verdict compares with 1, for the parity tests
 // (pe_batch_verify, which decides many aggregates with one final exponentiation and falls back on pairing_run: engine_batch.cpp)
 // Both verdict calls are synchronous and complete open pipelines first (enter); one GPU: PE_ERR_STATE under pe_dist_init*.

@@ -73,4 +73,51 @@ __device__ __forceinline__ bool fp_sqrt(fp& r, const fp& a)
     return fp_eq(t, a);
 }
 
+// A square root of a = a0 + a1 u in Fp2 = Fp[u]/(u^2 + 1), BOTH components in one lane (the G2 decompression's lane per point;
+// the hash-to-curve map, whose lane pair tries its two candidates at once).  y0, y1 and st come in as zero; st stays 0 iff a is a
+// square, then (y0 + y1 u)^2 == a; otherwise it becomes 2 ("not on the curve", the decompression's status).
+// The "complex method" (p = 3 mod 4): s = sqrt(norm) in Fp, d = (a0 + s)/2, w = d^((p-3)/4):
+// y = d w + (a1 w / 2) u if d is a residue, -(a1 w / 2) + (d w) u otherwise -- two windowed Fp exponentiations, no inversion, no
+// second attempt.  Which of the two roots comes out is the caller's to settle.
+__device__ __forceinline__ void f2_sqrt_lane(fp& y0, fp& y1, int32_t& st, const fp& a0, const fp& a1)
+{
+    if (fp_is_zero(a1)) {  // a in Fp: t = a0^((p+1)/4) squares to a0 (y = t) or to -a0 (y = u t: -1 is a non-residue)
+        fp t, c;
+        fp_sqrt_candidate(t, a0);
+        fp_sqr(c, t);
+        if (fp_eq(c, a0)) y0 = t;
+        else y1 = t;
+    } else {
+        fp n, t, s, d, w, v, c;
+        fp_sqr(n, a0);
+        fp_sqr(t, a1);
+        fp_add(n, n, t);
+        if (!fp_sqrt(s, n)) st = 2;  // the norm of a square is a square in Fp
+        else {
+            // exactly one of d = (a0 + s)/2 and d' = (a0 - s)/2 = -a1^2 / (4 d) is a square.  ONE exponentiation serves both
+            // cases and the division: w = d^((p-3)/4), t = d w, v = a1 w / 2.
+            //   d a residue:  t^2 = d, w = 1/t:        y = t + v u       (y0^2 - y1^2 = d - a1^2/(4d) = a0, 2 y0 y1 = a1)
+            //   otherwise:    t^2 = -d, w^2 = -1/d:    y = -v + t u      (v^2 + d = d' + d = a0, -2 v t = -a1 d w^2 = a1)
+            fp_add(d, a0, s);
+            fp_half(d, d);
+            fp_pow_pm3d4(w, d);
+            fp_mul(t, d, w);
+            fp_mul(v, a1, w);
+            fp_half(v, v);
+            fp_sqr(c, t);
+            if (fp_eq(c, d)) { y0 = t; y1 = v; }
+            else { fp_neg(y0, v); y1 = t; }
+        }
+    }
+    if (st == 0) {  // belt and braces: y^2 == a
+        fp t0, t1, t2;
+        fp_sqr(t0, y0);
+        fp_sqr(t1, y1);
+        fp_sub(t0, t0, t1);
+        fp_mul(t2, y0, y1);
+        fp_dbl(t2, t2);
+        if (!fp_eq(t0, a0) || !fp_eq(t2, a1)) st = 2;
+    }
+}
+
 }  // namespace posevo

@@ -61,9 +61,8 @@ void launch_g2_convert(hipStream_t s, const uint8_t* be192, uint32_t* mont48, ui
 // ---------------------------------------------------------------- decompress
 // BLSSignature wire format (pe:37, pe:717): 96 bytes = x.c1 | x.c0 big-endian, flag bits in the leading byte (bit 7
 // compressed, bit 6 infinity, bit 5 "y is the lexicographically larger root", compared on (c1, c0)).
-// One lane per point.  y = sqrt(x^3 + 4(1+u)) in Fp2 by the "complex method" (p = 3 mod 4): s = sqrt(norm) in Fp,
-// d = (a0 + s)/2, w = d^((p-3)/4): y = d w + (a1 w / 2) u if d is a residue, -(a1 w / 2) + (d w) u otherwise -- two windowed
-// Fp exponentiations (fp_sqrt.h), no inversion, no second attempt: ~1000 Montgomery products per point.  status: 0 ok, 1 malformed encoding, 2 not on the curve.
+// One lane per point.  y = sqrt(x^3 + 4(1+u)) in Fp2 by f2_sqrt_lane (fp_sqrt.h: the "complex method", two windowed Fp
+// exponentiations, no inversion, no second attempt: ~1000 Montgomery products per point).  status: 0 ok, 1 malformed encoding, 2 not on the curve.
 __device__ __forceinline__ void g2_decompress_one(const uint64_t i, const uint8_t* __restrict__ in96, uint32_t* __restrict__ out_mont48,
                                                   uint8_t* __restrict__ out_be192, int32_t* __restrict__ status)
 {
@@ -108,43 +107,7 @@ __device__ __forceinline__ void g2_decompress_one(const uint64_t i, const uint8_
             fp_add(a0, a0, four);
             fp_add(a1, a1, four);
         }
-        if (fp_is_zero(a1)) {  // a in Fp: t = a0^((p+1)/4) squares to a0 (y = t) or to -a0 (y = u t: -1 is a non-residue)
-            fp t, c;
-            fp_sqrt_candidate(t, a0);
-            fp_sqr(c, t);
-            if (fp_eq(c, a0)) y0 = t;
-            else y1 = t;
-        } else {
-            fp n, t, s, d, w, v, c;
-            fp_sqr(n, a0);
-            fp_sqr(t, a1);
-            fp_add(n, n, t);
-            if (!fp_sqrt(s, n)) st = 2;  // the norm of a square is a square in Fp
-            else {
-                // exactly one of d = (a0 + s)/2 and d' = (a0 - s)/2 = -a1^2 / (4 d) is a square.  ONE exponentiation serves both
-                // cases and the division: w = d^((p-3)/4), t = d w, v = a1 w / 2.
-                //   d a residue:  t^2 = d, w = 1/t:        y = t + v u       (y0^2 - y1^2 = d - a1^2/(4d) = a0, 2 y0 y1 = a1)
-                //   otherwise:    t^2 = -d, w^2 = -1/d:    y = -v + t u      (v^2 + d = d' + d = a0, -2 v t = -a1 d w^2 = a1)
-                fp_add(d, a0, s);
-                fp_half(d, d);
-                fp_pow_pm3d4(w, d);
-                fp_mul(t, d, w);
-                fp_mul(v, a1, w);
-                fp_half(v, v);
-                fp_sqr(c, t);
-                if (fp_eq(c, d)) { y0 = t; y1 = v; }
-                else { fp_neg(y0, v); y1 = t; }
-            }
-        }
-        if (st == 0) {  // belt and braces: y^2 == a
-            fp t0, t1, t2;
-            fp_sqr(t0, y0);
-            fp_sqr(t1, y1);
-            fp_sub(t0, t0, t1);
-            fp_mul(t2, y0, y1);
-            fp_dbl(t2, t2);
-            if (!fp_eq(t0, a0) || !fp_eq(t2, a1)) st = 2;
-        }
+        f2_sqrt_lane(y0, y1, st, a0, a1);
         if (st == 0) {
             const bool larger = fp_is_zero(y1) ? fp_is_larger_half(y0) : fp_is_larger_half(y1);
             if (larger != sign_flag) {

@@ -794,4 +794,16 @@ struct DepositApplyArgs {
 };
 void launch_deposit_apply(hipStream_t s, const DepositApplyArgs& a);
 
+// ---- hash_to_curve for G2 (h2c_kernels.hip; RFC 9380, BLS12381G2_XMD:SHA-256_SSWU_RO_)
+constexpr int H2C_POINT_WORDS = 96;  // an XYZZ point over Fp2 between k_h2c_map and k_h2c_finish (g2.h: G2X_WORDS)
+// n messages of msg_len bytes back to back -> (u0, u1): 48 Montgomery words a message (u0.c0 | u0.c1 | u1.c0 | u1.c1)
+void launch_h2c_expand(hipStream_t s, const uint8_t* msgs, uint32_t n, uint32_t msg_len, const uint8_t* dst, uint32_t dst_len,
+                       uint32_t* u_mont);
+// n_words canonical 48-byte big-endian values -> Montgomery words (the same rows, from pe_map_to_g2's bytes)
+void launch_h2c_load_u(hipStream_t s, const uint8_t* be48, uint32_t n_words, uint32_t* u_mont);
+// n_u values of Fp2 (24 words) -> n_u points of E2 as XYZZ (H2C_POINT_WORDS words): simplified SWU, then the 3-isogeny
+void launch_h2c_map(hipStream_t s, const uint32_t* u_mont, uint32_t n_u, uint32_t* out_xyzz);
+// message i: points 2 i and 2 i + 1 added, the cofactor cleared, 192 wire bytes; status (nullable): 1 where H is the identity
+void launch_h2c_finish(hipStream_t s, const uint32_t* pts_xyzz, uint32_t n, uint8_t* out_be192, int32_t* status);
+
 }  // namespace posevo

@@ -1,7 +1,8 @@
-// sha256.h -- SHA-256 for the two message shapes the engine hashes, one text for the gfx950 kernels, the host side of the
+// sha256.h -- SHA-256 for the message shapes the engine hashes, one text for the gfx950 kernels, the host side of the
 // library and a plain host compiler (tests/native/sha256_host.cpp):
 //   sha256_one_block   a message of at most 55 bytes, given as its one padded block (the shuffle's and the sampler's hashes)
 //   sha256_64          a message of exactly 64 bytes: a Merkle node H(left || right) of SSZ (ssz_kernels.hip, engine_ssz.cpp)
+//   sha256_compress    one compression over a running state: messages of any length (h2c_kernels.hip)
 // Words are SHA's big-endian words throughout: word i of a message is bytes 4i .. 4i + 3 read big-endian, word i of a digest
 // is written back the same way.
 #pragma once
@@ -132,6 +133,32 @@ PE_HD void sha256_64(const uint32_t in[16], uint32_t out[8])
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) out[i] = s[i] + mid[i];
+}
+// One compression of a message of any length: s (the IV to begin with) takes the block w, 16 big-endian words, which the
+// rolling schedule overwrites.  Padding is the caller's (hash_to_field's expander, h2c_kernels.hip).
+PE_HD void sha256_compress(uint32_t (&s)[8], uint32_t (&w)[16])
+{
+    uint32_t in[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) in[i] = s[i];
+#pragma unroll
+    for (int base = 0; base < 64; base += 8) {
+        if (base >= 16) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int i = base + j;
+                const uint32_t x15 = w[(i - 15) & 15], x2 = w[(i - 2) & 15];
+                const uint32_t s0 = rotr(x15, 7) ^ rotr(x15, 18) ^ (x15 >> 3);
+                const uint32_t s1 = rotr(x2, 17) ^ rotr(x2, 19) ^ (x2 >> 10);
+                w[i & 15] = w[i & 15] + s0 + w[(i - 7) & 15] + s1;
+            }
+        }
+#define PE_SHA_KW(j) (SHA_K[base + (j)] + w[(base + (j)) & 15])
+        PE_SHA_ROUNDS8(s, PE_SHA_KW);
+#undef PE_SHA_KW
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s[i] += in[i];
 }
 #undef PE_SHA_ROUNDS8
 #undef PE_SHA_ROUND

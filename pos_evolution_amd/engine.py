@@ -834,6 +834,48 @@ class Engine:
             _ptr(out, C.c_uint8) if aggregates else None))
         return verdict[:members], status[:members], group[:n_groups], (out[:n_groups] if aggregates else None)
 
+    def hash_to_g2(self, messages, dst: bytes = _abi.ETH2_DST, out: Optional[DeviceArena] = None, want_status: bool = False):
+        """pe_hash_to_g2: the message points H(m) of ``messages`` under the tag ``dst`` -- hash_to_curve of RFC 9380, suite
+        BLS12381G2_XMD:SHA-256_SSWU_RO_ -- as every BLS call of the engine takes them: (n, 192) uint8, G2 wire form.
+        messages: n byte strings of ONE length (0 .. 255), an (n, msg_len) uint8 array, or ``(DeviceArena, msg_len)`` for
+        messages that lie in device memory.  ``out``: a DeviceArena of n * 192 bytes -- the points are written there and never
+        cross to the host (``verify_resident`` reads them in place); the arena is returned.  ``want_status``: also int32 (n,),
+        1 where H(m) is the identity (no message anybody has seen)."""
+        if isinstance(messages, tuple) and messages[0].__class__ is DeviceArena:
+            arena, msg_len = messages[0], int(messages[1])
+            n = arena.size // msg_len if msg_len else 0
+            msg_ptr = arena.ptr
+        else:
+            if isinstance(messages, np.ndarray):
+                m = np.ascontiguousarray(messages, dtype=np.uint8)
+                m = m.reshape(len(m), -1) if m.ndim != 2 else m
+            else:
+                rows = [bytes(x) for x in messages]
+                if len({len(x) for x in rows}) > 1:
+                    raise ValueError("hash_to_g2: the messages of one call have one length")
+                m = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), len(rows[0]) if rows else 0)
+            n, msg_len = m.shape
+            msg_ptr = m.ctypes.data if m.size else None
+        dst_arr = np.frombuffer(bytes(dst), dtype=np.uint8)
+        if out is not None and out.size < 192 * n:
+            raise ValueError("hash_to_g2: the output arena is smaller than n * 192 bytes")
+        pts = None if out is not None else np.zeros((max(n, 1), 192), dtype=np.uint8)
+        status = np.zeros(max(n, 1), dtype=np.int32) if want_status else None
+        self._check(self._lib.pe_hash_to_g2(self._h, C.c_void_p(msg_ptr), n, msg_len, _ptr(dst_arr) if dst_arr.size else None,
+                                            dst_arr.size, C.c_void_p(out.ptr) if out is not None else _ptr(pts),
+                                            _ptr(status) if want_status else None))
+        res = out if out is not None else pts[:n]
+        return (res, status[:n]) if want_status else res
+
+    def map_to_g2(self, u) -> np.ndarray:
+        """pe_map_to_g2: n x (u0, u1) -> (n, 192) uint8 points of G2: map_to_curve of both, their sum, clear_cofactor (RFC 9380's
+        steps behind hash_to_field).  u: (n, 192) uint8 -- u0.c0 | u0.c1 | u1.c0 | u1.c1, 48-byte big-endian words below p."""
+        ub = np.ascontiguousarray(u, dtype=np.uint8).reshape(-1, 192)
+        n = len(ub)
+        pts = np.zeros((max(n, 1), 192), dtype=np.uint8)
+        self._check(self._lib.pe_map_to_g2(self._h, _ptr(ub) if n else None, n, _ptr(pts)))
+        return pts[:n]
+
     def verify_resident(self, message_points192, point_of_row=None, apply: bool = True, cap: Optional[int] = None) -> np.ndarray:
         """pe_verify_resident: int32[n_groups], one verdict per group of the last ``aggregate_signed`` over DeviceRows with
         ``want_aggregate_pubkeys=True``, from the aggregate keys and signatures that call left in device memory: 1 valid,

@@ -343,10 +343,20 @@ def get_indexed_attestation(store: Store, attestation):
     return [int(i) for i in indices], attestation.data, getattr(attestation, "signature", None)
 
 
+ETH2_DST = b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"
+
+
+def hash_to_curve_g2(engine: Engine, signing_roots: Sequence[bytes], dst: bytes = ETH2_DST) -> np.ndarray:
+    """hash_to_curve(signing_root, DST) of every root, on the GPU (pe_hash_to_g2): (n, 192) uint8 message points, what
+    fast_aggregate_verify, batch_fast_aggregate_verify, verify_attestation_signatures, verify_resident_attestations and
+    process_deposits take as ``message_point(s)``."""
+    return engine.hash_to_g2([bytes(r) for r in signing_roots], dst)
+
+
 def fast_aggregate_verify(store: Store, indices: Sequence[int], message_point, signature) -> bool:
     """bls.FastAggregateVerify(pubkeys of ``indices``, message, signature) -- the check is_valid_indexed_attestation ends with
     (pe:1456) -- computed on the GPU: the registry pubkeys are summed and e(sum, H(m)) == e(g1, signature) is decided by the
-    pairing-product kernels.  ``message_point`` is H(m) as a 192-byte uncompressed G2 point (hash_to_curve is the caller's),
+    pairing-product kernels.  ``message_point`` is H(m) as a 192-byte uncompressed G2 point (hash_to_curve_g2 makes them),
     ``signature`` the 192-byte uncompressed aggregate signature.  Returns the computed boolean; it may be passed as
     ``signature_valid`` wherever the verdict is injected today (attestations, IndexedAttestation).  An empty index list, an
     identity signature and a point off its curve give False.  Subgroup membership is checked by Engine.g2_subgroup_check /
@@ -375,7 +385,7 @@ def batch_fast_aggregate_verify(store: Store, index_lists: Sequence[Sequence[int
 def verify_attestation_signatures(store: Store, signers: Sequence[Sequence[int]], message_points, signatures) -> list:
     """One boolean per UNAGGREGATED attestation: ``signers[g]`` are the validators whose single-signer attestations carry the
     same AttestationData (one committee's votes), ``message_points[g]`` is H(m) of that data as a 192-byte uncompressed G2 point
-    (hash_to_curve is the caller's) and ``signatures[g]`` their 96-byte compressed BLSSignatures, in the order of ``signers[g]``.
+    (hash_to_curve_g2 makes them) and ``signatures[g]`` their 96-byte compressed BLSSignatures, in the order of ``signers[g]``.
     Engine.verify_signatures decides each group with one pairing check over sums weighted by scalars the engine draws itself,
     and finds the invalid members of a group that fails.  Returns a list of lists of booleans, shaped like ``signers``; each may
     be passed as ``signature_valid`` wherever the verdict is injected today.  A valid aggregate says nothing about its members
@@ -394,7 +404,7 @@ def verify_resident_attestations(store: Store, message_points, point_of_row=None
     ``aggregate_signed`` over DeviceRows formed (with ``want_aggregate_pubkeys=True``), computed where the aggregate keys and
     signatures lie; the verdicts take the place of the injected ``signature_valid``: ``on_attestation_batch`` /
     ``process_attestation_batch`` with ``(ROWS_RESIDENT, RESIDENT)`` afterwards reject every group that did not verify with
-    PE_ATT_BAD_SIGNATURE.  ``message_points``: H(m) as 192-byte uncompressed G2 points (hash_to_curve is the caller's), one per
+    PE_ATT_BAD_SIGNATURE.  ``message_points``: H(m) as 192-byte uncompressed G2 points (hash_to_curve_g2 makes them), one per
     group in group order, or -- with ``point_of_row`` (one index per input row) -- in any order, named by row.  Returns one
     entry per group: True / False, or None for a group without a committee (the handlers reject it for that reason)."""
     msg = np.frombuffer(b"".join(bytes(m) for m in message_points), dtype=np.uint8)
@@ -701,7 +711,7 @@ def process_deposits(state, deposits, message_points, *, check_proofs: bool = Tr
     ``state.eth1_data.deposit_root`` at ``state.eth1_deposit_index`` (check_proofs False: genesis), the pubkey lookup in a
     device-side index, proofs of possession for new pubkeys, top-ups and appended validators.  ``state`` must have been bound
     with ``bind_state``.  message_points[i]: hash_to_curve(compute_signing_root(DepositMessage_i, domain)) as a 192-byte uncompressed
-    G2 point -- ``Engine.deposit_signing_roots`` gives the roots; hash_to_curve is the caller's.
+    G2 point -- ``Engine.deposit_signing_roots`` gives the roots, hash_to_curve_g2 the points.
     make_validator(**fields): how a Validator of the caller's state type is made (default: a SimpleNamespace).
     A failing proof raises AssertionError, as the reference does, with the state untouched.  -> the statuses (DEP_*).
     Every call moves the registry up (as process_registry_updates does); the path without any transfer is
