@@ -1057,6 +1057,38 @@ int pe_hash_to_g2(pe_engine* h, const uint8_t* msgs, uint32_t n, uint32_t msg_le
  * PE_ERR_INVALID_ARG also for a word that is not below p. */
 int pe_map_to_g2(pe_engine* h, const uint8_t* u_be, uint32_t n, uint8_t* out192);
 
+/* ---- the message of an attestation's signature, from the attestation itself -------- */
+/* is_valid_indexed_attestation verifies over compute_signing_root(data, get_domain(state, DOMAIN_BEACON_ATTESTER,
+ * data.target.epoch)) = H(hash_tree_root(AttestationData) || domain).  The state's part of that is three values: */
+#define PE_ETH2_DST "BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"   /* Ethereum's signature tag, 43 bytes */
+typedef struct pe_attester_domains {      /* get_domain(state, DOMAIN_BEACON_ATTESTER, data.target.epoch) */
+    uint64_t fork_epoch;                  /* state.fork.epoch */
+    uint8_t  domain_previous[32];         /* compute_domain(type, fork.previous_version, genesis_validators_root) */
+    uint8_t  domain_current[32];          /* ... fork.current_version ...: taken where target.epoch >= fork_epoch */
+} pe_attester_domains;                    /* 72 bytes */
+
+/* out_roots32[i] = the signing root of rows[i], 32 bytes each, back to back as pe_hash_to_g2 takes its messages.  Of a row only
+ * the seven fields of AttestationData enter (slot, index, beacon_block_root, source, target): bits_offset, n_bits, flags and
+ * reserved0 do not.  Nine SHA-256 of 64 bytes per row, on the device.
+ *   rows, out_roots32   each host memory, or device memory (used in place when 16-byte aligned, through a copy otherwise)
+ * Needs no store and no registry.  Synchronous, one GPU.  PE_ERR_STATE under pe_dist_init* and inside a pipeline;
+ * PE_ERR_INVALID_ARG for a missing dom or array; PE_ERR_CAPACITY above 2^24 rows.  n == 0 returns PE_OK.  An error writes
+ * nothing. */
+int pe_attestation_signing_roots(pe_engine* h, const pe_attestation* rows, uint32_t n, const pe_attester_domains* dom,
+                                 uint8_t* out_roots32);
+
+/* pe_verify_resident with the messages taken from the groups themselves: group g is verified over the signing root of ITS
+ * OWN AttestationData (its first input row's; a group is formed by AttestationData equality) under dom, hashed to G2 with
+ * PE_ETH2_DST -- signing roots, (u0, u1), message points and pairings all on the call's stream in one workspace, nothing of
+ * the messages crossing to the host in between.  The caller names no message, so it cannot name the wrong one.
+ *   out_roots32   nullable, host memory, 32 x cap: the groups' signing roots in group order (entries past the groups read 0);
+ *                 also written for a group without a committee
+ * Preconditions, flags, cap, the verdict table (row 2 cannot occur: the points are the engine's own), the counters of the profile
+ * hook, the completion of open pipelines and the errors are pe_verify_resident's;
+ * PE_ERR_INVALID_ARG also for a NULL dom. */
+int pe_verify_resident_data(pe_engine* h, const pe_attester_domains* dom, uint32_t flags, uint32_t cap, int32_t* verdict,
+                            uint8_t* out_roots32);
+
 /* ---- multi-GPU exchange (validator-range shards) ----------- */
 /* Each rank owns a contiguous validator range and the whole (small) block table.
  * get_head splits at the one exchange point:

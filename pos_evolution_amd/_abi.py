@@ -155,6 +155,13 @@ class pe_deposit_stats(C.Structure):
                 ("n_validators", C.c_uint64)]
 
 
+class pe_attester_domains(C.Structure):
+    """struct pe_attester_domains (include/posevo.h): what get_domain(state, DOMAIN_BEACON_ATTESTER, epoch) reads, 72 bytes."""
+    _fields_ = [("fork_epoch", C.c_uint64), ("domain_previous", C.c_uint8 * 32), ("domain_current", C.c_uint8 * 32)]
+
+
+assert C.sizeof(pe_attester_domains) == 72
+
 PE_DEP_APPENDED, PE_DEP_TOPUP, PE_DEP_IGNORED_BAD_SIGNATURE, PE_DEP_BAD_PROOF = 0, 1, 2, 3
 PE_REWARDS_INACTIVITY, PE_REWARDS_DELTAS = 1, 2
 PE_ROOT_BALANCES, PE_ROOT_INACTIVITY, PE_ROOT_PART_PREV, PE_ROOT_PART_CUR, PE_ROOT_VALIDATORS = 1, 2, 4, 8, 16
@@ -255,6 +262,8 @@ SIGNATURES = {
                                       _P(pe_deposit_stats)]),
     "pe_hash_to_g2": (C.c_int, [_H, _u8p, C.c_uint32, C.c_uint32, _u8p, C.c_uint32, _u8p, _i32p]),
     "pe_map_to_g2": (C.c_int, [_H, _u8p, C.c_uint32, _u8p]),
+    "pe_attestation_signing_roots": (C.c_int, [_H, _attp, C.c_uint32, _P(pe_attester_domains), _u8p]),
+    "pe_verify_resident_data": (C.c_int, [_H, _P(pe_attester_domains), C.c_uint32, C.c_uint32, _i32p, _u8p]),
     "pe_g1_sum": (C.c_int, [_H, _u8p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u8p]),
     "pe_prune": (C.c_int, [_H, C.c_void_p]),
     "pe_set_block_checkpoints": (C.c_int, [_H, C.c_uint32, C.c_uint64, _u8p, C.c_uint64, _u8p]),

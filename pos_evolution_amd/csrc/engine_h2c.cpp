@@ -21,7 +21,7 @@ constexpr uint32_t H2C_MAX_N = 1u << 24;  // 768 bytes of workspace a message
 
 // what both calls share behind their own first kernel: (u0, u1) rows -> XYZZ points -> wire bytes
 struct H2cTail {
-    Region<uint32_t> u, pts;
+    Region<uint32_t> u, pts;  // h2c_work (carve.h): pe_verify_resident_data takes the same two behind its own first kernel
     Region<uint8_t> out;
     Region<int32_t> st;
     bool out_in_place = false;
@@ -32,8 +32,9 @@ H2cTail h2c_tail(Layout& L, uint32_t n, const uint8_t* out192, bool want_status)
     H2cTail t;
     t.out_kind = mem_kind(out192);
     t.out_in_place = reads_in_place(t.out_kind, out192);  // 16-byte aligned device memory: written where it lies
-    t.u = L.take<uint32_t>(48 * (size_t)n);
-    t.pts = L.take<uint32_t>((size_t)H2C_POINT_WORDS * 2 * n);
+    const H2cWork work = h2c_work(L, n, H2C_POINT_WORDS);
+    t.u = work.u;
+    t.pts = work.pts;
     t.out = L.take<uint8_t>(t.out_in_place ? 0 : 192 * (size_t)n);
     t.st = L.take<int32_t>(want_status ? n : 0);
     return t;

@@ -806,4 +806,13 @@ void launch_h2c_map(hipStream_t s, const uint32_t* u_mont, uint32_t n_u, uint32_
 // message i: points 2 i and 2 i + 1 added, the cofactor cleared, 192 wire bytes; status (nullable): 1 where H is the identity
 void launch_h2c_finish(hipStream_t s, const uint32_t* pts_xyzz, uint32_t n, uint8_t* out_be192, int32_t* status);
 
+// ---- attestation signing roots (att_signing_kernels.hip; the rule: att_signing_row.h)
+struct AttDomains;
+// out_roots32[i] = compute_signing_root(AttestationData of a row, get_domain(target.epoch)), 32 bytes each, back to back as
+// launch_h2c_expand reads its messages.  grp == nullptr: n roots, of rows 0 .. n - 1.  Else: one root per group of the
+// resident aggregate, of row grp[g].rep, for g < min(plan->n_groups, n) -- n is the host's upper bound and sizes the grid.
+// rows: n_rows rows of 144 bytes, 4-byte aligned; a rep beyond n_rows gives a zero root.
+void launch_att_signing_roots(hipStream_t s, const void* rows, uint32_t n_rows, const AttGroup* grp, const AttPlan* plan,
+                              uint32_t n, const AttDomains& dom, uint8_t* out_roots32);
+
 }  // namespace posevo

@@ -901,6 +901,53 @@ class Engine:
                                                  _abi.PE_VERIFY_APPLY if apply else 0, cap, _ptr(verdict, C.c_int32)))
         return verdict[:self._profile_verify_resident_stats()["groups"]]
 
+    @staticmethod
+    def _attester_domains(fork_epoch: int, domain_previous: bytes, domain_current: bytes) -> "_abi.pe_attester_domains":
+        if len(domain_previous) != 32 or len(domain_current) != 32:
+            raise ValueError("a domain is 32 bytes")
+        dom = _abi.pe_attester_domains()
+        dom.fork_epoch = int(fork_epoch)
+        dom.domain_previous[:] = bytes(domain_previous)
+        dom.domain_current[:] = bytes(domain_current)
+        return dom
+
+    def attestation_signing_roots(self, rows, fork_epoch: int, domain_previous: bytes, domain_current: bytes,
+                                  out: Optional[DeviceArena] = None):
+        """pe_attestation_signing_roots: (n, 32) uint8, compute_signing_root(AttestationData of row i, domain) -- the messages
+        attestation signatures are over, as ``hash_to_g2`` takes them -- with ``domain_current`` where the row's target epoch
+        is at or past ``fork_epoch`` and ``domain_previous`` before it (get_domain).  rows: a structured array of
+        pe_attestation (synth.ATT_DTYPE), a ctypes array of them, a list of AttRow, or DeviceRows.  ``out``: a DeviceArena of
+        n * 32 bytes -- the roots are written there and never cross to the host; the arena is returned."""
+        if rows.__class__ is DeviceRows:
+            n, row_ptr = rows.n, rows.ptr
+        else:
+            if not isinstance(rows, np.ndarray) and len(rows) and isinstance(rows[0], AttRow):
+                rows = pack_attestations(rows)[0]
+            n = len(rows)
+            row_ptr = (_att_ptr(rows) if isinstance(rows, np.ndarray) else C.addressof(rows)) if n else None
+        if out is not None and out.size < 32 * n:
+            raise ValueError("attestation_signing_roots: the output arena is smaller than n * 32 bytes")
+        dom = self._attester_domains(fork_epoch, domain_previous, domain_current)
+        roots = None if out is not None else np.zeros((max(n, 1), 32), dtype=np.uint8)
+        self._check(self._lib.pe_attestation_signing_roots(self._h, C.c_void_p(row_ptr), n, C.byref(dom),
+                                                           C.c_void_p(out.ptr) if out is not None else _ptr(roots)))
+        return out if out is not None else roots[:n]
+
+    def verify_resident_data(self, fork_epoch: int, domain_previous: bytes, domain_current: bytes, apply: bool = True,
+                             cap: Optional[int] = None, want_roots: bool = True):
+        """pe_verify_resident_data: ``verify_resident`` with every group's message taken from the group's own
+        AttestationData -- its signing root under get_domain(DOMAIN_BEACON_ATTESTER, target epoch), hashed to G2 under
+        Ethereum's tag -- all on the device.  Returns (int32[n_groups] verdicts as verify_resident's, (n_groups, 32) uint8
+        signing roots in group order, or None without ``want_roots``)."""
+        dom = self._attester_domains(fork_epoch, domain_previous, domain_current)
+        cap = self._signed_device_rows if cap is None else int(cap)
+        verdict = np.zeros(max(cap, 1), dtype=np.int32)
+        roots = np.zeros((max(cap, 1), 32), dtype=np.uint8) if want_roots else None
+        self._check(self._lib.pe_verify_resident_data(self._h, C.byref(dom), _abi.PE_VERIFY_APPLY if apply else 0, cap,
+                                                      _ptr(verdict, C.c_int32), _ptr(roots) if want_roots else None))
+        ng = self._profile_verify_resident_stats()["groups"]
+        return verdict[:ng], (roots[:ng] if want_roots else None)
+
     def _profile_verify_resident_stats(self) -> dict:
         """pe_profile_verify_resident_stats: how the last verify_resident decided its groups, by row of the rule table."""
         out = np.zeros(_abi.PE_VERIFY_RESIDENT_STATS, dtype=np.uint32)

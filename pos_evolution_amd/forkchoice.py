@@ -412,6 +412,72 @@ def verify_resident_attestations(store: Store, message_points, point_of_row=None
     return [None if int(v) == _abi.PE_BLS_UNDECIDED else int(v) == _abi.PE_BLS_VALID for v in verdict]
 
 
+# The message of an attestation's signature, as scalar logic: what the engine's k_att_signing_roots computes per row
+# (Engine.attestation_signing_roots) and what a caller needs once per fork to fill pe_attester_domains.  The reference names
+# compute_signing_root and get_domain and holds no text of them; these are the consensus specification's.
+DOMAIN_BEACON_ATTESTER = bytes([1, 0, 0, 0])
+GENESIS_FORK_VERSION = bytes(4)
+
+
+def _sha256(data: bytes) -> bytes:
+    import hashlib
+    return hashlib.sha256(data).digest()
+
+
+def _u64_chunk(v: int) -> bytes:
+    return int(v).to_bytes(8, "little") + bytes(24)
+
+
+def compute_fork_data_root(current_version: bytes, genesis_validators_root: bytes) -> bytes:
+    """hash_tree_root(ForkData(current_version, genesis_validators_root)): two chunks, one hash."""
+    assert len(current_version) == 4 and len(genesis_validators_root) == 32
+    return _sha256(bytes(current_version) + bytes(28) + bytes(genesis_validators_root))
+
+
+def compute_domain(domain_type: bytes, fork_version: Optional[bytes] = None, genesis_validators_root: Optional[bytes] = None) -> bytes:
+    """domain_type + compute_fork_data_root(fork_version, genesis_validators_root)[:28]"""
+    assert len(domain_type) == 4
+    fork_version = GENESIS_FORK_VERSION if fork_version is None else bytes(fork_version)
+    genesis_validators_root = ZERO_ROOT if genesis_validators_root is None else bytes(genesis_validators_root)
+    return bytes(domain_type) + compute_fork_data_root(fork_version, genesis_validators_root)[:28]
+
+
+def get_domain(state, domain_type: bytes, epoch: int) -> bytes:
+    """get_domain(state, domain_type, epoch): over ``state.fork.previous_version`` before ``state.fork.epoch``, over
+    ``state.fork.current_version`` from it on.  (The specification's default epoch, the state's current one, is the caller's
+    to pass: the signature of an attestation takes ``data.target.epoch``.)"""
+    fork = state.fork
+    version = fork.previous_version if int(epoch) < int(fork.epoch) else fork.current_version
+    return compute_domain(domain_type, bytes(version), bytes(state.genesis_validators_root))
+
+
+def _attestation_data_root(data) -> bytes:
+    cp = lambda c: _sha256(_u64_chunk(c.epoch) + bytes(c.root))
+    h01 = _sha256(_u64_chunk(data.slot) + _u64_chunk(data.index))
+    h23 = _sha256(bytes(data.beacon_block_root) + cp(data.source))
+    h45 = _sha256(cp(data.target) + ZERO_ROOT)
+    h67 = _sha256(bytes(64))
+    return _sha256(_sha256(h01 + h23) + _sha256(h45 + h67))
+
+
+def compute_signing_root(data, domain: bytes) -> bytes:
+    """compute_signing_root(AttestationData, domain) = hash_tree_root(SigningData(hash_tree_root(data), domain)): the 32 bytes
+    an attestation's signature is over.  ``data``: anything with AttestationData's fields."""
+    assert len(domain) == 32
+    return _sha256(_attestation_data_root(data) + bytes(domain))
+
+
+def verify_resident_attestation_data(store: Store, fork_epoch: int, domain_previous: bytes, domain_current: bytes) -> list:
+    """verify_resident_attestations with the messages taken from the aggregates themselves (pe_verify_resident_data): every
+    group of the engine's last ``aggregate_signed`` over DeviceRows is verified over compute_signing_root of ITS OWN
+    AttestationData under get_domain(state, DOMAIN_BEACON_ATTESTER, data.target.epoch) -- ``domain_previous`` before
+    ``fork_epoch``, ``domain_current`` from it on -- hashed to the curve and paired on the GPU, and the verdicts take the place of
+    the injected ``signature_valid`` as there.  Returns one entry per group: True / False, or None for a group without a
+    committee."""
+    verdict, _ = store.engine.verify_resident_data(fork_epoch, domain_previous, domain_current, apply=True)
+    return [None if int(v) == _abi.PE_BLS_UNDECIDED else int(v) == _abi.PE_BLS_VALID for v in verdict]
+
+
 def get_head(store: Store) -> bytes:
     """pe:1102-1116.  Raises (AssertionError) when the justified checkpoint has moved and the balances of its state
     have not been handed over (Store.ensure_justified_state)."""
