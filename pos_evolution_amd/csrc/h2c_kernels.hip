@@ -50,14 +50,10 @@ __device__ __forceinline__ void h2c_reduce(fp& r, const uint32_t (&hi)[8], const
         h.l[j] = hi[7 - j];
         l.l[j] = lo[7 - j];
     }
-    // (limbs the compiler knows to be zero must not reach the product's asm columns as constants: measured on gfx950, hipcc then
-    // forms a wrong product for a value whose upper four limbs are literal zeros; behind this barrier all twelve are registers)
+    // (the halves' upper four limbs reach the product as literal zeros: its accumulator operands are early-clobber for exactly this,
+    // tools/gen_fp_mul.py; tests/test_gpu_fp_device.py holds this very shape)
 #pragma unroll
-    for (int j = 0; j < 12; ++j) {
-        asm volatile("" : "+v"(h.l[j]));
-        asm volatile("" : "+v"(l.l[j]));
-        c.l[j] = H2C_2P256[j];
-    }
+    for (int j = 0; j < 12; ++j) c.l[j] = H2C_2P256[j];
     fp_to_mont(hm, h);
     fp_to_mont(lm, l);
     fp_mul(t, hm, c);

@@ -51,8 +51,11 @@ class Machine:
     def asm(self, stmt):
         body = "".join(re.findall(r'"((?:[^"\\]|\\.)*)"', stmt.split(":")[0]))
         ins = [s.strip() for s in body.replace("\\t", "").split("\\n") if s.strip()]
-        operands = re.findall(r'"[+=]?v"\(([^)]+)\)', stmt)
+        operands = re.findall(r'"[+=]?&?v"\(([^)]+)\)', stmt)
         assert operands[:2] == ["lo", "hi"] and stmt.rstrip().endswith('"vcc")')
+        # a statement of more than one MAC writes the accumulator before it has read every limb: both halves early-clobber, or the
+        # register allocator may hand a limb it knows to be zero the register of hi
+        assert re.search(r': "\+&v"\(lo\), "\+&v"\(hi\) :', stmt), stmt[-200:]
         vcc = 0
         for line in ins:
             op, args = line.split(None, 1)
