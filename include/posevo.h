@@ -1089,6 +1089,102 @@ int pe_attestation_signing_roots(pe_engine* h, const pe_attestation* rows, uint3
 int pe_verify_resident_data(pe_engine* h, const pe_attester_domains* dom, uint32_t flags, uint32_t cap, int32_t* verdict,
                             uint8_t* out_roots32);
 
+/* ---- sync committees (Altair): sampling, verification, rewards ------------- */
+/* The handle keeps two committees in device memory, the CURRENT one (whose members sign and are paid) and the NEXT one, each a
+ * list of `size` validator indices -- duplicates allowed -- with its aggregate pubkey: the compressed G1 sum of the members'
+ * registry pubkeys, a validator listed k times counted k times (eth_aggregate_pubkeys).
+ * Lifetime: both are dropped by pe_store_init, by a pe_set_validators that changes the registry's size or brings pubkeys, and
+ * by pe_set_pubkeys_compressed; they survive pe_process_deposits (indices stay valid as the registry grows). */
+#define PE_SYNC_COMMITTEE_MAX 512   /* SYNC_COMMITTEE_SIZE of mainnet; the minimal preset has 32 */
+#define PE_SYNC_MAX_BATCH 64        /* aggregates of one pe_process_sync_aggregate */
+#define PE_SYNC_CURRENT 0
+#define PE_SYNC_NEXT 1
+/* get_next_sync_committee: with total = n_active and i = 0, 1, ... the candidate
+ * active[compute_shuffled_index(i % total, total, seed)] is appended iff
+ * effective_balance * 255 >= max_effective_balance * hash(seed + uint64_le(i / 32))[i % 32] -- pe_compute_proposers' rule
+ * (pe:604-618), so member 0 and its i are what that call returns for the seed -- until `size` members are appended; a
+ * validator may be appended more than once, and is when n_active < size.  Sampled on the device (k_sync_sample, in batches
+ * of 16 384 candidates); the indices and the aggregate key STAY ON THE DEVICE as the handle's NEXT committee.
+ *   seed, active_indices / n_active / shuffle_round_count   as pe_compute_proposers: NULL = validators 0..n_active-1,
+ *       PE_ACTIVE_RESIDENT accepted, same validation; an empty active set is PE_ERR_INVALID_ARG
+ *   max_effective_balance   effective balances = the working-state view, as for the proposers
+ *   size            1 .. PE_SYNC_COMMITTEE_MAX (else PE_ERR_INVALID_ARG)
+ *   max_tries       candidates examined before giving up (0 = 2^20)
+ *   out_indices u32[size] (may be NULL), out_aggregate_pubkey48 (may be NULL): copies of what stays resident
+ *   out_tries (may be NULL): the i of the last accepted candidate + 1
+ * Fewer than `size` acceptances within max_tries: PE_ERR_CAPACITY and *out_tries = max_tries; both resident committees and the
+ * other outputs stay as they were.  Needs pubkeys loaded (PE_ERR_STATE).  Synchronous; one GPU: PE_ERR_STATE on a handle with
+ * pe_dist_init* active. */
+int pe_sync_committee_compute(pe_engine* h, const uint8_t seed[32], const uint32_t* active_indices, uint32_t n_active,
+                              uint32_t shuffle_round_count, uint64_t max_effective_balance, uint32_t size, uint32_t max_tries,
+                              uint32_t* out_indices, uint8_t* out_aggregate_pubkey48, uint32_t* out_tries);
+/* Checkpoint / resume and genesis: `which` = PE_SYNC_CURRENT or PE_SYNC_NEXT.
+ * _set: indices u32[size], 1 <= size <= PE_SYNC_COMMITTEE_MAX, every index below pe_num_validators(h) (else
+ *   PE_ERR_INVALID_ARG, nothing changed); the aggregate key is computed from the registry (PE_ERR_STATE without pubkeys).
+ * _get: *out_size = the committee's size, 0 where none is held (nothing else is written then); out_indices (may be NULL) has
+ *   room for `cap` entries, PE_ERR_CAPACITY where that is fewer than the size; out_aggregate_pubkey48 may be NULL. */
+int pe_sync_committee_set(pe_engine* h, int which, const uint32_t* indices, uint32_t size);
+int pe_sync_committee_get(pe_engine* h, int which, uint32_t* out_indices, uint32_t cap, uint32_t* out_size,
+                          uint8_t* out_aggregate_pubkey48);
+/* process_sync_committee_updates' move at a period boundary: current = next, and there is no next until the caller computes
+ * or sets one.  PE_ERR_STATE without a next committee. */
+int pe_sync_committee_rotate(pe_engine* h);
+
+/* SyncAggregate of one block with what process_sync_aggregate reads beside it.  The engine reads neither state.block_roots nor
+ * the forks (as with pe_attester_domains): the caller supplies get_block_root_at_slot(state, previous_slot) and
+ * get_domain(state, DOMAIN_SYNC_COMMITTEE, compute_epoch_at_slot(previous_slot)). */
+typedef struct pe_sync_aggregate {
+    uint8_t  bits[64];         /* sync_committee_bits: bit p is (bits[p / 8] >> (p % 8)) & 1 */
+    uint8_t  signature[96];    /* sync_committee_signature, compressed */
+    uint8_t  block_root[32];
+    uint8_t  domain[32];
+    uint32_t proposer_index;   /* get_beacon_proposer_index(state) of the block */
+    uint32_t reserved0;
+} pe_sync_aggregate;           /* 232 bytes */
+typedef struct pe_sync_params {
+    uint64_t total_active_balance;   /* get_total_active_balance(state), as pe_active_set returns it */
+    uint64_t base_reward_factor;     /* BASE_REWARD_FACTOR */
+} pe_sync_params;
+void pe_sync_params_default(pe_sync_params* out);   /* base_reward_factor 64; total_active_balance 0: the caller's */
+typedef struct pe_sync_stats {
+    uint64_t participant_reward;   /* per set bit; also the penalty per clear bit */
+    uint64_t proposer_reward;      /* per set bit, to the aggregate's proposer */
+    uint64_t n_participants;       /* set bits over all aggregates */
+    uint64_t credited;             /* Gwei added to balances */
+    uint64_t debited;              /* Gwei actually taken off balances (decrease_balance stops at 0) */
+    uint64_t n_saturated;          /* decreases that stopped at 0 */
+    uint64_t applied;              /* 1: the balances were changed */
+} pe_sync_stats;
+#define PE_SYNC_VERIFY 0x1u
+#define PE_SYNC_APPLY  0x2u
+/* process_sync_aggregate for the aggregates of n consecutive blocks, n <= PE_SYNC_MAX_BATCH, all over the resident CURRENT
+ * committee (size S).  Per aggregate: the participants' indices in committee order and the signing root
+ * sha256(block_root || domain) = hash_tree_root(SigningData) on the device (k_sync_members), then
+ * PE_SYNC_VERIFY   verdict[b] = eth_fast_aggregate_verify(participants' pubkeys, signing root, signature): 1 valid, 0 invalid,
+ *                  2 a point off its curve.  No participant AND the compressed infinity signature (0xC0, 95 zero bytes): 1.
+ *                  Otherwise FastAggregateVerify: no participant, an identity signature or an identity aggregate key: 0.  A
+ *                  signature that does not decode or lies outside G2: 0, and sig_status[b] (nullable; else 0) says why: 1
+ *                  malformed, 2 not on the curve, 3 not in the subgroup.  The keys are summed by pe_g1_sum's route (a member
+ *                  listed twice and participating twice counts twice), the root hashed by pe_hash_to_g2 under PE_ETH2_DST.
+ *                  Without this flag verdict and sig_status are not touched and may be NULL.
+ * PE_SYNC_APPLY    with participant_reward and proposer_reward from
+ *                      per_increment = increment * base_reward_factor / isqrt(total_active_balance)
+ *                      total_base = per_increment * (total_active_balance / increment)
+ *                      participant_reward = total_base * 2 / 64 / slots_per_epoch / S;  proposer_reward = participant_reward * 8 / 56
+ *                  (increment and slots_per_epoch are the handle's cfg), aggregate by aggregate and in committee order p = 0 .. S-1:
+ *                  bit set: balance[member[p]] += participant_reward, balance[proposer] += proposer_reward; bit clear:
+ *                  balance[member[p]] -= min(balance, participant_reward) -- onto the resident balances (pe_state_set_balances),
+ *                  exactly as the sequential loop leaves them (k_sync_rewards).  Additions wrap, as in pe_rewards_and_penalties.
+ *                  With both flags the balances change only when every verdict is 1 (out->applied says which).
+ * out (may be NULL): the scalars and what was done; credited .. n_saturated are 0 where nothing was applied.
+ * PE_ERR_STATE: no current committee; PE_SYNC_APPLY without resident balances; PE_SYNC_VERIFY without pubkeys; pe_dist_init*.
+ * PE_ERR_INVALID_ARG: flags 0 or with other bits; n > PE_SYNC_MAX_BATCH; a set bit at a position >= S; a proposer_index
+ *   outside the registry; total_active_balance below the increment; a step of the scalar chain above that exceeds 64 bits
+ *   (decided on the host in 128 bits).  A failing call changes nothing.  n == 0 returns PE_OK.
+ * Synchronous (completes open pipelines first); one GPU. */
+int pe_process_sync_aggregate(pe_engine* h, const pe_sync_aggregate* aggs, uint32_t n, const pe_sync_params* params,
+                              uint32_t flags, int32_t* verdict, int32_t* sig_status, pe_sync_stats* out);
+
 /* ---- multi-GPU exchange (validator-range shards) ----------- */
 /* Each rank owns a contiguous validator range and the whole (small) block table.
  * get_head splits at the one exchange point:

@@ -162,6 +162,29 @@ class pe_attester_domains(C.Structure):
 
 assert C.sizeof(pe_attester_domains) == 72
 
+class pe_sync_aggregate(C.Structure):
+    """struct pe_sync_aggregate (include/posevo.h): a block's SyncAggregate with its block root, domain and proposer, 232 bytes."""
+    _fields_ = [("bits", C.c_uint8 * 64), ("signature", C.c_uint8 * 96), ("block_root", C.c_uint8 * 32), ("domain", C.c_uint8 * 32),
+                ("proposer_index", C.c_uint32), ("reserved0", C.c_uint32)]
+
+
+assert C.sizeof(pe_sync_aggregate) == 232
+
+
+class pe_sync_params(C.Structure):
+    """struct pe_sync_params (include/posevo.h): what process_sync_aggregate's scalars are made of."""
+    _fields_ = [("total_active_balance", C.c_uint64), ("base_reward_factor", C.c_uint64)]
+
+
+class pe_sync_stats(C.Structure):
+    """struct pe_sync_stats (include/posevo.h): the scalars of one pe_process_sync_aggregate and what it did."""
+    _fields_ = [("participant_reward", C.c_uint64), ("proposer_reward", C.c_uint64), ("n_participants", C.c_uint64),
+                ("credited", C.c_uint64), ("debited", C.c_uint64), ("n_saturated", C.c_uint64), ("applied", C.c_uint64)]
+
+
+PE_SYNC_COMMITTEE_MAX, PE_SYNC_MAX_BATCH = 512, 64
+PE_SYNC_CURRENT, PE_SYNC_NEXT = 0, 1
+PE_SYNC_VERIFY, PE_SYNC_APPLY = 1, 2
 PE_DEP_APPENDED, PE_DEP_TOPUP, PE_DEP_IGNORED_BAD_SIGNATURE, PE_DEP_BAD_PROOF = 0, 1, 2, 3
 PE_REWARDS_INACTIVITY, PE_REWARDS_DELTAS = 1, 2
 PE_ROOT_BALANCES, PE_ROOT_INACTIVITY, PE_ROOT_PART_PREV, PE_ROOT_PART_CUR, PE_ROOT_VALIDATORS = 1, 2, 4, 8, 16
@@ -264,6 +287,13 @@ SIGNATURES = {
     "pe_map_to_g2": (C.c_int, [_H, _u8p, C.c_uint32, _u8p]),
     "pe_attestation_signing_roots": (C.c_int, [_H, _attp, C.c_uint32, _P(pe_attester_domains), _u8p]),
     "pe_verify_resident_data": (C.c_int, [_H, _P(pe_attester_domains), C.c_uint32, C.c_uint32, _i32p, _u8p]),
+    "pe_sync_committee_compute": (C.c_int, [_H, _u8p, _u32p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _u32p, _u8p,
+                                            C.c_void_p]),
+    "pe_sync_committee_set": (C.c_int, [_H, C.c_int, _u32p, C.c_uint32]),
+    "pe_sync_committee_get": (C.c_int, [_H, C.c_int, _u32p, C.c_uint32, C.c_void_p, _u8p]),
+    "pe_sync_committee_rotate": (C.c_int, [_H]),
+    "pe_sync_params_default": (None, [_P(pe_sync_params)]),
+    "pe_process_sync_aggregate": (C.c_int, [_H, _u8p, C.c_uint32, _P(pe_sync_params), C.c_uint32, _i32p, _i32p, _P(pe_sync_stats)]),
     "pe_g1_sum": (C.c_int, [_H, _u8p, C.c_uint64, _u32p, _u32p, C.c_uint32, _u8p]),
     "pe_prune": (C.c_int, [_H, C.c_void_p]),
     "pe_set_block_checkpoints": (C.c_int, [_H, C.c_uint32, C.c_uint64, _u8p, C.c_uint64, _u8p]),

@@ -550,7 +550,7 @@ void pe_engine_destroy(pe_engine* h)
                       &h->d_partials, &h->d_lane_partials, &h->d_out96, &h->d_tmp_points, &h->d_tmp_be, &h->d_tmp_points30,
                       &h->d_active, &h->d_active_wg, &h->d_registry_wg, &h->d_ssz_zero,
                       &h->d_ssz_validator_roots, &h->d_ssz_level[0], &h->d_ssz_level[1], &h->d_ssz_chunks, &h->d_bls, &h->d_batch, &h->d_verify,
-                      &h->d_dep_index, &h->d_deposit})
+                      &h->d_dep_index, &h->d_deposit, &h->d_sync_members[0], &h->d_sync_members[1], &h->d_sync})
         b->release();
     if (h->ev_active_read) (void)hipEventDestroy(h->ev_active_read);
     for (auto& t : h->tables) {

@@ -471,6 +471,7 @@ int pe_set_pubkeys_compressed(pe_engine* h, uint64_t n, const uint8_t* pubkeys48
     h->have_points = false;
     h->points30_valid = false;
     committee_sums_drop(h);
+    sync_committees_drop(h);  // their aggregate keys are sums of the old points
     uint64_t n_bad = 0;
     int rc = g1_decompress_common(h, pubkeys48, n, h->d_points.as<uint32_t>(), nullptr, status, &n_bad);
     if (rc) return rc;

@@ -320,6 +320,16 @@ struct pe_engine {
     DevBuf d_deposit;              // one call's workspace: the Layout of pe_process_deposits
     uint64_t reg_capacity = 0;     // validators registry_grow last sized every held column for (it doubles it: reg_grown_capacity);
                                    // the setters size a column for the registry alone, and no column ever shrinks
+    // ---- sync committees (engine_sync.cpp) ----
+    // [PE_SYNC_CURRENT] and [PE_SYNC_NEXT]: the members as u32[size] in device memory (d_sync_members, room for
+    // PE_SYNC_COMMITTEE_MAX) with a host copy, and the compressed aggregate pubkey.  size = 0: none held.
+    struct SyncCommittee {
+        uint32_t size = 0;
+        std::vector<uint32_t> members;
+        uint8_t aggregate_pubkey[48] = {};
+    } sync_committee[2];
+    DevBuf d_sync_members[2];
+    DevBuf d_sync;  // one call's workspace: the Layout of pe_sync_committee_compute or of pe_process_sync_aggregate
     // ---- pe_verify_resident (engine_resident_verify.cpp) ----
     // which aggregate the arena's d_res_points belong to: valid while that is still the handle's last aggregate of either kind
     struct ResidentVerify {
@@ -814,6 +824,8 @@ void registry_epochs_drop(pe_engine* h);
 void resident_balances_drop(pe_engine* h);
 // ... nor the static part of the validators (engine_ssz.cpp)
 void registry_static_drop(pe_engine* h);
+// ... nor the sync committees, which a changed pubkey also invalidates: their aggregate keys (engine_sync.cpp)
+void sync_committees_drop(pe_engine* h);
 // a working-state view that still mirrors the registry becomes a view of its own, flags included (engine_epoch.cpp)
 int materialise_state_view(pe_engine* h);
 // Every column the handle holds (reg_columns.h) gets room for n_new validators with its contents kept (capacity doubling), the

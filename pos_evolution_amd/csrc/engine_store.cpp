@@ -353,6 +353,7 @@ int pe_store_init(pe_engine* h, uint64_t genesis_time, uint64_t anchor_slot, con
     registry_epochs_drop(h);
     resident_balances_drop(h);
     registry_static_drop(h);
+    sync_committees_drop(h);
     h->res_valid = false;
     h->rr.valid = false;
     PE_TRY(slasher_reset(h));  // what the validators of the previous store attested says nothing about this one
@@ -413,6 +414,7 @@ int pe_set_validators(pe_engine* h, uint64_t n, const uint8_t* pubkeys96, const 
         }
         HIP_TRY(h, hipGetLastError());
         h->have_points = true;
+        sync_committees_drop(h);  // their aggregate keys are sums of the old points
         PE_TRY(build_points30(h, n));  // the registry in the accumulation's field form, now: never inside a G1 launch
     } else if (!pubkeys96) {
         h->have_points = h->have_points && n <= old_n;
@@ -424,6 +426,7 @@ int pe_set_validators(pe_engine* h, uint64_t n, const uint8_t* pubkeys96, const 
         registry_epochs_drop(h);
         resident_balances_drop(h);
         registry_static_drop(h);
+        sync_committees_drop(h);
     }
     h->n_val = n;
     return PE_OK;

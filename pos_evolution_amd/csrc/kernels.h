@@ -815,4 +815,32 @@ struct AttDomains;
 void launch_att_signing_roots(hipStream_t s, const void* rows, uint32_t n_rows, const AttGroup* grp, const AttPlan* plan,
                               uint32_t n, const AttDomains& dom, uint8_t* out_roots32);
 
+// ---- sync committees (sync_kernels.hip; host side: engine_sync.cpp)
+constexpr int SYNC_COMMITTEE_MAX = 512;  // PE_SYNC_COMMITTEE_MAX: positions of a committee, lanes of k_sync_members' workgroup
+constexpr int SYNC_MAX_BATCH = 64;       // PE_SYNC_MAX_BATCH: aggregates of one call
+constexpr int SYNC_AGG_WORDS = 58;       // sizeof(pe_sync_aggregate) / 4
+constexpr int SYNC_SAMPLE_WG = 256;      // candidates per workgroup of k_sync_sample, one lane each
+// Candidates one launch examines: 64 workgroups, whose counts one wave scans.  A launch costs a candidate's 91 dependent
+// compressions whatever its width until the lanes fill the chip, so the width only has to cover the common cases in one or two
+// launches: 512 acceptances at 1 ETH against 32 need 16 384 +- 700 candidates, at full balances 512.
+constexpr uint32_t SYNC_SAMPLE_BATCH = 16384;
+struct SyncSampleState { uint32_t count, tries; };  // members appended so far | the i of the size-th acceptance + 1
+// One batch of get_next_sync_committee_indices: the candidates i in [base, base + SYNC_SAMPLE_BATCH) below max_tries, those
+// accepted appended to d_members in the order of i behind the d_state->count already there, up to `size` in all; zero *d_state
+// before the first batch.  Arguments as launch_proposer_sample's; d_wg_count: SYNC_SAMPLE_BATCH / SYNC_SAMPLE_WG words,
+// d_wg_entry: 2 * SYNC_SAMPLE_BATCH words (8-byte aligned).  1 <= size <= SYNC_COMMITTEE_MAX.  The three launchers of this
+// section return 0, or -1 where an argument lies outside what the kernel's arrays are sized for: nothing is launched then.
+int launch_sync_sample(hipStream_t s, const uint32_t* d_seed_be, uint32_t total, uint32_t rounds, const uint32_t* d_indices,
+                        const uint64_t* d_eff_balance, uint64_t max_eff, uint64_t base, uint64_t max_tries, uint32_t size,
+                        uint32_t* d_wg_count, uint32_t* d_wg_entry, SyncSampleState* d_state, uint32_t* d_members);
+// d_aggs: n aggregates of SYNC_AGG_WORDS words; d_committee: `size` validator indices.  Per aggregate b: d_lists[b][0 .. d_counts[b])
+// = the participants in committee order, d_bad[b] != 0 where a bit at a position >= size is set, d_roots[b] = its signing root
+// (32 bytes).  1 <= n <= SYNC_MAX_BATCH.
+int launch_sync_members(hipStream_t s, const uint32_t* d_aggs, uint32_t n, const uint32_t* d_committee, uint32_t size,
+                         uint32_t* d_lists, uint32_t* d_counts, uint32_t* d_bad, uint32_t* d_roots);
+// The aggregates' rewards and penalties onto d_balances, aggregate by aggregate, position by position (one workgroup).  Every
+// member and proposer index must lie inside d_balances.  d_stats[3]: Gwei credited | Gwei debited | decreases cut at 0.
+int launch_sync_rewards(hipStream_t s, const uint32_t* d_aggs, uint32_t n, const uint32_t* d_committee, uint32_t size,
+                         uint64_t participant_reward, uint64_t proposer_reward, uint64_t* d_balances, uint64_t* d_stats);
+
 }  // namespace posevo

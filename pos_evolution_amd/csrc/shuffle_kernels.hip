@@ -14,6 +14,7 @@
 // Integer/hash work, no MFMA.  SURVEY.md 8(f) rank 1.
 // Further down: proposer sampling (k_proposer_sample) and the active set the shuffles start from (k_active_compact).
 #include "kernels.h"
+#include "sample_walk.h"
 #include "sha256.h"
 #include "wave64.h"
 
@@ -231,22 +232,7 @@ int launch_shuffle(hipStream_t s, const uint32_t* d_seed_be, uint32_t n, uint32_
 // blocks a table in memory would hold), then the random byte's hash; a ballot picks the lowest accepting lane.  The loop's
 // exit is wave-uniform and bounded by max_tries: a registry that never accepts ends in NONE32.
 constexpr int PROP_WAVE = 64;
-constexpr uint32_t PROP_MAX_ROUNDS = 256;  // shuffle_round_count is a uint8 in the spec
-
-// byte k (0..31) of a digest held as 8 big-endian words, without indexing the array by a run-time value
-__device__ __forceinline__ uint32_t digest_byte(const uint32_t (&dig)[8], uint32_t k)
-{
-    const uint32_t j = k >> 2;
-    uint32_t word = dig[0];
-    word = j == 1 ? dig[1] : word;
-    word = j == 2 ? dig[2] : word;
-    word = j == 3 ? dig[3] : word;
-    word = j == 4 ? dig[4] : word;
-    word = j == 5 ? dig[5] : word;
-    word = j == 6 ? dig[6] : word;
-    word = j == 7 ? dig[7] : word;
-    return (word >> (8 * (3 - (k & 3)))) & 0xffu;
-}
+// (the candidate's walk, its random byte and the acceptance rule: sample_walk.h, shared with k_sync_sample)
 
 __global__ void __launch_bounds__(PROP_WAVE)
 k_proposer_sample(const uint32_t* __restrict__ seeds_be /* [n_seeds][8] big-endian words */, uint32_t total,
@@ -261,54 +247,18 @@ k_proposer_sample(const uint32_t* __restrict__ seeds_be /* [n_seeds][8] big-endi
     uint32_t dig[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) w[k] = seed[k];
-    // ---- phase 1: pivot[r] = bytes_to_uint64(hash(seed + uint8(r))[0:8]) % total   (pe:522)
-    for (uint32_t r = lane; r < rounds; r += PROP_WAVE) {
-        w[8] = (r << 24) | (0x80u << 16);
-#pragma unroll
-        for (int k = 9; k < 15; ++k) w[k] = 0;
-        w[15] = 33 * 8;
-        sha256_one_block(w, dig);
-        const uint64_t lo = __builtin_bswap32(dig[0]), hi = __builtin_bswap32(dig[1]);
-        pivots[r] = (uint32_t)(((hi << 32) | lo) % total);
-    }
+    // ---- phase 1: the round pivots
+    for (uint32_t r = lane; r < rounds; r += PROP_WAVE) pivots[r] = sample_pivot(w, dig, r, total);
     __syncthreads();
     // ---- phase 2
     const uint32_t n_batches = (uint32_t)(((uint64_t)max_tries + PROP_WAVE - 1) / PROP_WAVE);
     for (uint32_t b = 0; b < n_batches; ++b) {
         const uint64_t i = (uint64_t)b * PROP_WAVE + lane;
-        uint32_t index = (uint32_t)(i % total);
-        for (uint32_t r = 0; r < rounds; ++r) {
-            const uint32_t pivot = pivots[r];
-            uint32_t flip = pivot + total - index;  // (pivot + index_count - index) % index_count, operands < total
-            if (flip >= total) flip -= total;
-            const uint32_t position = max(index, flip);
-            const uint32_t blk = position >> 8;
-            // source = hash(seed + uint8(r) + uint32_le(position // 256)): 37 bytes   (pe:525-529)
-            w[8] = (r << 24) | ((blk & 0xffu) << 16) | (((blk >> 8) & 0xffu) << 8) | ((blk >> 16) & 0xffu);
-            w[9] = ((blk >> 24) << 24) | (0x80u << 16);
-#pragma unroll
-            for (int k = 10; k < 15; ++k) w[k] = 0;
-            w[15] = 37 * 8;
-            sha256_one_block(w, dig);
-            const uint32_t byte = digest_byte(dig, (position & 255u) >> 3);
-            index = ((byte >> (position & 7u)) & 1u) ? flip : index;
-        }
-        // random_byte = hash(seed + uint64_le(i // 32))[i % 32]: 40 bytes   (pe:614)
-        const uint64_t q = i >> 5;
-        w[8] = __builtin_bswap32((uint32_t)q);
-        w[9] = __builtin_bswap32((uint32_t)(q >> 32));
-        w[10] = 0x80000000u;
-#pragma unroll
-        for (int k = 11; k < 15; ++k) w[k] = 0;
-        w[15] = 40 * 8;
-        sha256_one_block(w, dig);
-        const unsigned long long random_byte = digest_byte(dig, (uint32_t)(i & 31u));
+        const uint32_t index = sample_walk(w, dig, pivots, rounds, total, i);
+        const unsigned long long random_byte = sample_random_byte(w, dig, i);
         const uint32_t candidate = indices ? indices[index] : index;
         const unsigned long long eb = eff_balance[candidate];
-        // effective_balance * 255 >= MAX_EFFECTIVE_BALANCE * random_byte over the whole u64 range: 128-bit products
-        const unsigned long long l_hi = __umul64hi(eb, 255ull), l_lo = eb * 255ull;
-        const unsigned long long r_hi = __umul64hi(max_eff, random_byte), r_lo = max_eff * random_byte;
-        const bool accept = i < max_tries && (l_hi > r_hi || (l_hi == r_hi && l_lo >= r_lo));
+        const bool accept = i < max_tries && sample_accepts(eb, max_eff, random_byte);
         const unsigned long long ballot = __ballot(accept);
         if (ballot) {  // wave-uniform
             if (lane == (uint32_t)__builtin_ctzll(ballot)) {

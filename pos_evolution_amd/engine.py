@@ -182,6 +182,8 @@ class _BalancesResident:
 BALANCES_RESIDENT = _BalancesResident()
 _BALANCES_RESIDENT_ARG = DeviceArena(_abi.PE_BALANCES_RESIDENT, 0)   # the sentinel address, as _ptr passes it on
 REWARDS_INACTIVITY, REWARDS_DELTAS = _abi.PE_REWARDS_INACTIVITY, _abi.PE_REWARDS_DELTAS
+SYNC_CURRENT, SYNC_NEXT = _abi.PE_SYNC_CURRENT, _abi.PE_SYNC_NEXT
+SYNC_VERIFY, SYNC_APPLY = _abi.PE_SYNC_VERIFY, _abi.PE_SYNC_APPLY
 ROOT_BALANCES, ROOT_INACTIVITY, ROOT_PART_PREV, ROOT_PART_CUR, ROOT_VALIDATORS = (
     _abi.PE_ROOT_BALANCES, _abi.PE_ROOT_INACTIVITY, _abi.PE_ROOT_PART_PREV, _abi.PE_ROOT_PART_CUR, _abi.PE_ROOT_VALIDATORS)
 ROOT_ALL = ROOT_BALANCES | ROOT_INACTIVITY | ROOT_PART_PREV | ROOT_PART_CUR | ROOT_VALIDATORS
@@ -1108,6 +1110,75 @@ class Engine:
                                                    int(max_effective_balance), int(max_tries), _ptr(prop, C.c_uint32),
                                                    _ptr(tries, C.c_uint32)))
         return prop[:n_seeds], tries[:n_seeds]
+
+    # -- sync committees ----------------------------------------------------
+    def sync_committee_compute(self, seed: bytes, active_indices, rounds: int = 90, max_effective_balance: int = 32 * 10**9,
+                               size: int = _abi.PE_SYNC_COMMITTEE_MAX, max_tries: int = 0):
+        """get_next_sync_committee on the GPU (pe_sync_committee_compute): sampled over the working-state view's effective
+        balances with compute_proposers' acceptance rule, left resident as the handle's NEXT committee.  active_indices as
+        ``compute_proposers`` takes them.  -> (indices uint32[size], aggregate_pubkey bytes[48], tries: the i of the last accepted
+        candidate + 1).  EngineError PE_ERR_CAPACITY where max_tries candidates (0 = 2^20) did not yield `size` members."""
+        sd = np.frombuffer(bytes(seed), dtype=np.uint8).copy()
+        assert sd.size == 32, "a seed is 32 bytes"
+        act, n_act = self._active_arg(active_indices)
+        idx = np.zeros(_abi.PE_SYNC_COMMITTEE_MAX, dtype=np.uint32)
+        key = np.zeros(48, dtype=np.uint8)
+        tries = C.c_uint32(0)
+        self._check(self._lib.pe_sync_committee_compute(self._h, _ptr(sd, C.c_uint8), _ptr(act, C.c_uint32), n_act, int(rounds),
+                                                        int(max_effective_balance), int(size), int(max_tries),
+                                                        _ptr(idx, C.c_uint32), _ptr(key, C.c_uint8), C.addressof(tries)))
+        return idx[:int(size)], key.tobytes(), int(tries.value)
+
+    def sync_committee_set(self, which: int, indices):
+        """Committee `which` (SYNC_CURRENT / SYNC_NEXT) from a list of validator indices, duplicates allowed; its aggregate
+        pubkey is computed from the registry (pe_sync_committee_set): genesis, checkpoint / resume."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint32)
+        self._check(self._lib.pe_sync_committee_set(self._h, int(which), _ptr(idx if idx.size else None, C.c_uint32), idx.size))
+
+    def sync_committee_get(self, which: int):
+        """-> (indices uint32[size], aggregate_pubkey bytes[48]) of committee `which`, or None where the handle holds none."""
+        idx = np.zeros(_abi.PE_SYNC_COMMITTEE_MAX, dtype=np.uint32)
+        key = np.zeros(48, dtype=np.uint8)
+        size = C.c_uint32(0)
+        self._check(self._lib.pe_sync_committee_get(self._h, int(which), _ptr(idx, C.c_uint32), idx.size, C.addressof(size),
+                                                    _ptr(key, C.c_uint8)))
+        return (idx[:size.value], key.tobytes()) if size.value else None
+
+    def sync_committee_rotate(self):
+        """process_sync_committee_updates' move: current = next, no next (pe_sync_committee_rotate)."""
+        self._check(self._lib.pe_sync_committee_rotate(self._h))
+
+    def process_sync_aggregate(self, aggregates, total_active_balance: int, flags: int = SYNC_VERIFY | SYNC_APPLY,
+                               base_reward_factor: int = 64) -> dict:
+        """process_sync_aggregate for the blocks' aggregates in order, over the resident CURRENT committee
+        (pe_process_sync_aggregate).  aggregates: a sequence of dicts / tuples (bits: 64 bytes, signature: 96 bytes,
+        block_root, domain: 32 bytes each, proposer_index), or an array of _abi.pe_sync_aggregate.
+        -> pe_sync_stats as a dict, with "verdict" int32[n] and "sig_status" int32[n] under SYNC_VERIFY."""
+        if isinstance(aggregates, C.Array):
+            rows = aggregates
+        else:
+            rows = (_abi.pe_sync_aggregate * max(len(aggregates), 1))()
+            for r, a in zip(rows, aggregates):
+                bits, sig, root, dom, prop = (a[k] for k in ("bits", "signature", "block_root", "domain", "proposer_index")) \
+                    if isinstance(a, dict) else a
+                for name, val, size in (("bits", bits, 64), ("signature", sig, 96), ("block_root", root, 32), ("domain", dom, 32)):
+                    val = bytes(val)
+                    assert len(val) == size, (name, len(val))
+                    C.memmove(getattr(r, name), val, size)
+                r.proposer_index = int(prop)
+        n = len(aggregates)
+        p = _abi.pe_sync_params()
+        self._lib.pe_sync_params_default(C.byref(p))
+        p.total_active_balance, p.base_reward_factor = int(total_active_balance), int(base_reward_factor)
+        verdict = np.zeros(max(n, 1), dtype=np.int32)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        st = _abi.pe_sync_stats()
+        self._check(self._lib.pe_process_sync_aggregate(self._h, C.addressof(rows), n, C.byref(p), int(flags),
+                                                        _ptr(verdict, C.c_int32), _ptr(status, C.c_int32), C.byref(st)))
+        res = {name: int(getattr(st, name)) for name, _ in _abi.pe_sync_stats._fields_}
+        if flags & SYNC_VERIFY:
+            res["verdict"], res["sig_status"] = verdict[:n], status[:n]
+        return res
 
     def effective_balance_updates(self, balances, max_effective_balance: int = 32 * 10**9, hysteresis_quotient: int = 4,
                                   downward_multiplier: int = 1, upward_multiplier: int = 5, want_result: bool = True):

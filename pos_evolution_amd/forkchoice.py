@@ -833,6 +833,7 @@ MAINNET_PRESET = {
     "SLOTS_PER_EPOCH": 32, "MAX_COMMITTEES_PER_SLOT": 64, "TARGET_COMMITTEE_SIZE": 128,
     "MIN_VALIDATOR_WITHDRAWABILITY_DELAY": 256, "MIN_PER_EPOCH_CHURN_LIMIT": 4, "CHURN_LIMIT_QUOTIENT": 65536,
     "MAX_DEPOSITS": 16, "SAFETY_DECAY": 10, "ETH_TO_GWEI": 10**9, "MAX_EFFECTIVE_BALANCE": MAX_EFFECTIVE_BALANCE,
+    "EPOCHS_PER_SYNC_COMMITTEE_PERIOD": 256,
 }
 
 
@@ -934,3 +935,21 @@ def is_within_weak_subjectivity_period(current_epoch: int, ws_state_epoch: int, 
     current_epoch = the epochs of ws_state.slot and of the store's current slot.  The two asserts before it (pe:1295-1296)
     compare roots and are the caller's."""
     return int(current_epoch) <= int(ws_state_epoch) + int(ws_period)
+
+
+def compute_sync_committee_period(epoch: int, *, preset: Optional[dict] = None) -> int:
+    """pe:586-587."""
+    return int(epoch) // _preset(preset)["EPOCHS_PER_SYNC_COMMITTEE_PERIOD"]
+
+
+def is_assigned_to_sync_committee(current_epoch: int, epoch: int, validator_index: int, current_indices, next_indices, *,
+                                  preset: Optional[dict] = None) -> bool:
+    """pe:564-577 as scalar logic over the two index lists ``Engine.sync_committee_get`` returns (SYNC_CURRENT, SYNC_NEXT).
+    The reference asks whether the validator's PUBKEY is among the committee's pubkeys; that equals membership by index while
+    the registry's pubkeys are distinct, which process_deposit guarantees (a deposit of a known pubkey tops its validator up
+    and appends none).  ``epoch`` must lie in the current or the next period: AssertionError otherwise, as in the reference."""
+    period = compute_sync_committee_period(epoch, preset=preset)
+    current_period = compute_sync_committee_period(current_epoch, preset=preset)
+    assert period in (current_period, current_period + 1)
+    members = current_indices if period == current_period else next_indices
+    return any(int(m) == int(validator_index) for m in members)
