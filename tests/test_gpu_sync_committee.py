@@ -91,21 +91,21 @@ def _active(e, form, n_val, n_active, rng):
     return pea.ACTIVE_RESIDENT, [int(v) for v in chosen]
 
 
-def _check_compute(e, seed, active, indices, bal, rounds, size, refusal=True):
+def _check_compute(e, seed, active, indices, bal, rounds, size, refusal=True, max_eff=MAX_EFF):
     """The engine's committee against the model's, its key, member 0 against compute_proposers, and max_tries at and one
     below the model's tries.  -> (members, tries)"""
-    want, want_tries = M.next_sync_committee_indices(indices, bal, seed, rounds, MAX_EFF, size)
-    got, key, tries = e.sync_committee_compute(seed, active, rounds, MAX_EFF, size)
+    want, want_tries = M.next_sync_committee_indices(indices, bal, seed, rounds, max_eff, size)
+    got, key, tries = e.sync_committee_compute(seed, active, rounds, max_eff, size)
     assert got.tolist() == want and tries == want_tries
     assert key == _key_of(want)
     nxt = e.sync_committee_get(SYNC_NEXT)
     assert nxt[0].tolist() == want and nxt[1] == key
-    prop, prop_tries = e.compute_proposers([seed], active, rounds, MAX_EFF, 1 << 20)
-    first = M.next_sync_committee_indices(indices, bal, seed, rounds, MAX_EFF, 1)[1] - 1   # the i of member 0
+    prop, prop_tries = e.compute_proposers([seed], active, rounds, max_eff, 1 << 20)
+    first = M.next_sync_committee_indices(indices, bal, seed, rounds, max_eff, 1)[1] - 1   # the i of member 0
     assert (int(prop[0]), int(prop_tries[0])) == (want[0], first)
     if refusal:
         before = _snapshot(e)
-        again, key2, tries2 = e.sync_committee_compute(seed, active, rounds, MAX_EFF, size, max_tries=want_tries)
+        again, key2, tries2 = e.sync_committee_compute(seed, active, rounds, max_eff, size, max_tries=want_tries)
         assert (again.tolist(), key2, tries2) == (want, key, want_tries)
         if want_tries > 1:
             idx = np.full(_abi.PE_SYNC_COMMITTEE_MAX, 0xABABABAB, dtype=np.uint32)
@@ -116,7 +116,7 @@ def _check_compute(e, seed, active, indices, bal, rounds, size, refusal=True):
                 act_ptr, n_act = active.ctypes.data, active.size
             else:
                 act_ptr, n_act = (_abi.PE_ACTIVE_RESIDENT, len(indices)) if active is pea.ACTIVE_RESIDENT else (None, active)
-            rc = e._lib.pe_sync_committee_compute(e._h, sd.ctypes.data, act_ptr, n_act, rounds, MAX_EFF, size, want_tries - 1,
+            rc = e._lib.pe_sync_committee_compute(e._h, sd.ctypes.data, act_ptr, n_act, rounds, max_eff, size, want_tries - 1,
                                                   idx.ctypes.data, out_key.ctypes.data, out_tries.ctypes.data)
             assert rc == _abi.PE_ERR_CAPACITY and int(out_tries[0]) == want_tries - 1
             assert (idx == 0xABABABAB).all() and (out_key == 0xAB).all()
