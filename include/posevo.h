@@ -629,6 +629,128 @@ int pe_process_slashings(pe_engine* h, uint64_t current_epoch, uint64_t sum_slas
                          uint64_t proportional_slashing_multiplier, uint64_t epochs_per_slashings_vector,
                          pe_slashings_stats* out);
 
+/* ---- block operations over the resident registry: slashings and exits -------- */
+/* process_proposer_slashing, process_attester_slashing and process_voluntary_exit, with slash_validator and
+ * initiate_validator_exit under them (Altair / Bellatrix; the rule set is restated in tests/block_ops_model.py: the reference
+ * holds the Validator fields, pe:36-45, `slashings`, pe:359/397, and is_slashable_attestation_data, pe:1134-1143, not these
+ * functions' text).  With process_attestation (pe_process_attestation_batch) and process_deposit (pe_process_deposits) this
+ * completes Altair's process_operations over resident state. */
+#define PE_OP_PROPOSER_SLASHING 1u
+#define PE_OP_ATTESTER_SLASHING 2u
+#define PE_OP_VOLUNTARY_EXIT    3u
+#define PE_OP_FLAG_SIGNATURE_VALID 0x1u /* the injected verdict over every signature of the operation (both headers, both
+                                           IndexedAttestations, the SignedVoluntaryExit): the caller computes it with the BLS
+                                           calls, as PE_ATT_FLAG_SIGNATURE_VALID */
+typedef struct pe_block_op {
+    uint32_t kind;                  /* PE_OP_* */
+    uint32_t flags;                 /* PE_OP_FLAG_* */
+    /* PE_OP_ATTESTER_SLASHING: the two AttestationData = the leading 128 bytes of a pe_attestation (as
+     * pe_on_attester_slashing and pe_slasher_get_data use them) and attesting_indices of both sides as ranges of `indices` */
+    uint8_t  data_1[128], data_2[128];
+    uint64_t indices_1_offset, indices_1_length, indices_2_offset, indices_2_length;
+    /* PE_OP_PROPOSER_SLASHING: of the two BeaconBlockHeaders the slot, the proposer index and hash_tree_root(header) */
+    uint64_t header_1_slot, header_1_proposer_index;
+    uint8_t  header_1_root[32];
+    uint64_t header_2_slot, header_2_proposer_index;
+    uint8_t  header_2_root[32];
+    /* PE_OP_VOLUNTARY_EXIT */
+    uint64_t validator_index, exit_epoch;
+} pe_block_op;                      /* 408 bytes */
+
+/* status[i] of pe_process_block_operations: 0 = valid, else the first assert of the operation that fails, in its order */
+typedef enum pe_op_status {
+    PE_OP_OK = 0,
+    PE_OP_NOT_SLASHABLE_DATA = 64,      /* attester: is_slashable_attestation_data false */
+    PE_OP_BAD_INDICES = 65,             /* attester: a list empty, not strictly ascending or with an index >= n; proposer /
+                                           exit: the validator index >= n */
+    PE_OP_BAD_SIGNATURE = 66,           /* the injected verdict is false */
+    PE_OP_NOBODY_SLASHABLE = 67,        /* attester: no validator of the intersection was slashable when visited */
+    PE_OP_HEADER_MISMATCH = 68,         /* proposer: slots or proposer indices differ, or the two roots are equal */
+    PE_OP_PROPOSER_NOT_SLASHABLE = 69,  /* proposer: is_slashable_validator false */
+    PE_OP_NOT_ACTIVE = 70,              /* exit: not active at current_epoch */
+    PE_OP_ALREADY_EXITING = 71,         /* exit: exit_epoch != FAR (before the call, or by an earlier operation of it) */
+    PE_OP_EXIT_EPOCH_FUTURE = 72,       /* exit: current_epoch < exit.epoch */
+    PE_OP_TOO_YOUNG = 73                /* exit: current_epoch < activation_epoch + shard_committee_period */
+} pe_op_status;
+
+typedef struct pe_block_ops_params {
+    uint64_t min_slashing_penalty_quotient;       /* 32: MIN_SLASHING_PENALTY_QUOTIENT_BELLATRIX (Altair's own is 64) */
+    uint64_t whistleblower_reward_quotient;       /* 512 */
+    uint64_t epochs_per_slashings_vector;         /* 8192 */
+    uint64_t shard_committee_period;              /* 256 */
+    uint64_t min_validator_withdrawability_delay; /* 256  -- these four as pe_registry_params */
+    uint64_t max_seed_lookahead;                  /* 4 */
+    uint64_t min_per_epoch_churn_limit;           /* 4 */
+    uint64_t churn_limit_quotient;                /* 65536 */
+} pe_block_ops_params;
+void pe_block_ops_params_default(pe_block_ops_params* out);
+
+typedef struct pe_block_ops_stats {
+    uint64_t n_active;           /* active at current_epoch, before the call */
+    uint64_t churn_limit;        /* get_validator_churn_limit: constant during the call, every exit it writes lies after
+                                    current_epoch */
+    uint64_t n_slashed;
+    uint64_t n_exits_initiated;  /* exit epochs written: voluntary exits and slashed validators without one */
+    uint64_t first_exit_epoch, last_exit_epoch;  /* 0 if none was written */
+    uint64_t slashed_balance;    /* the effective balances slashed: the caller adds it to
+                                    state.slashings[current_epoch % EPOCHS_PER_SLASHINGS_VECTOR] (the vector stays the
+                                    caller's scalar state, as for pe_process_slashings) */
+    uint64_t proposer_rewards;   /* Gwei credited to proposer_index */
+    uint64_t penalties;          /* Gwei actually debited (after decrease_balance's cut at 0) */
+    uint64_t n_saturated;        /* slashed validators whose penalty exceeded the balance */
+    uint64_t n_invalid;          /* operations with a status != 0 */
+} pe_block_ops_stats;
+
+/* An ordered list of block operations applied to the resident registry with the semantics of the sequential pyspec loop:
+ * operations take effect in array order and each sees the effects of the earlier ones (a validator slashed by one is not
+ * slashable in the next; a validator already exiting is slashed without a new exit epoch; an exit after a slashing of the
+ * same validator is invalid).  Comparisons unsigned 64-bit, FAR = 2^64 - 1 an ordinary value:
+ *   initiate_validator_exit(i)   nothing if exit_epoch[i] != FAR; else with E0, c0, (base, fill) as for pe_registry_updates the
+ *                                k-th such validator IN OPERATION ORDER gets exit_epoch = base + (fill + k) / churn_limit and
+ *                                withdrawable_epoch = exit_epoch + min_validator_withdrawability_delay
+ *   slash_validator(i)           whistleblower = the proposer: initiate_validator_exit(i); PE_VAL_SLASHED in the working-state
+ *                                view; withdrawable_epoch = max(withdrawable_epoch, current_epoch + epochs_per_slashings_vector);
+ *                                balance[i] -= min(balance[i], effective_balance[i] / min_slashing_penalty_quotient);
+ *                                balance[proposer_index] += effective_balance[i] / whistleblower_reward_quotient
+ *   is_slashable_validator(i)    not slashed, activation_epoch <= current_epoch < withdrawable_epoch
+ *   attester slashing            valid iff the data are slashable, both lists are non-empty, strictly ascending and < n, the
+ *                                verdict is true and at least one validator of the intersection, visited in ascending order, is
+ *                                slashable when visited; every such validator is slashed
+ *   proposer slashing            valid iff slots and proposer indices are equal, the roots differ, the proposer is slashable
+ *                                and the verdict is true
+ *   voluntary exit               valid iff active at current_epoch, exit_epoch == FAR, current_epoch >= exit.epoch,
+ *                                current_epoch >= activation_epoch + shard_committee_period and the verdict is true
+ * A BLOCK WITH AN INVALID OPERATION IS AN INVALID BLOCK: the call writes every operation's status and, if any is not 0,
+ * CHANGES NOTHING (it still returns PE_OK; out->n_invalid counts them, out->n_active and churn_limit are filled, the rest is
+ * 0).  The statuses behind the first invalid operation are those the operations get on the state the earlier VALID
+ * operations leave; an invalid operation itself leaves nothing.
+ * indices: the attester slashings' attesting_indices, flat; the ranges may overlap or coincide.  The proposer's balance is
+ * the only one several slashings touch: it takes the closed form of the loop -- where the proposer is itself the j-th
+ * slashing of the call its penalty is cut against balance + the rewards of the slashings before it, and the other rewards,
+ * its own slashing's included, arrive afterwards.
+ * Reads and writes the resident epochs (pe_registry_set_epochs), balances and withdrawable epochs (pe_state_set_balances)
+ * and the working-state view (materialised first if it still mirrors pe_set_validators).  PE_VAL_ACTIVE / _PREV are not
+ * touched.  If an exit epoch was written the resident active list is dropped, as pe_registry_updates drops it.
+ * pe_registry_get_epochs, pe_state_get_balances and pe_state_get_validators read the new values back and pe_state_roots
+ * hashes them with no further call.  Read-only passes (k_block_ops_lists, _claim, _resolve, _scan, k_registry_census), a host
+ * step, one writing pass (k_block_ops_apply: one writer per validator and column, no atomic on a balance).
+ * Synchronous (completes open pipelines first); one GPU.  status: n_ops entries; out may be NULL.  A block's operations
+ * run slashings, attestations, deposits, exits: two calls around the other two.  A failing call changes
+ * nothing:
+ *   PE_ERR_STATE        the epochs or the balances are not resident, the view does not cover the registry, or pe_dist_init*
+ *   PE_ERR_INVALID_ARG  an unknown kind; an offset or length past n_indices; proposer_index >= n; a quotient is 0;
+ *                       current_epoch + epochs_per_slashings_vector or current_epoch + 1 + max_seed_lookahead wraps or reaches
+ *                       FAR; the churn limit is 0; the last exit epoch + min_validator_withdrawability_delay wraps or reaches
+ *                       FAR; n_slashed * (the largest slashed effective balance) + balance[proposer_index] exceeds 64 bits
+ *                       (the bound under which no sum of the call can wrap) -- the last three decided on the host, in 128
+ *                       bits, before anything is written
+ *   PE_ERR_CAPACITY     2^31 or more indices, or candidate slots (list elements + single operations) */
+int pe_process_block_operations(pe_engine* h, uint64_t current_epoch, uint32_t proposer_index,
+                                const pe_block_op* ops, uint32_t n_ops,
+                                const uint32_t* indices, uint64_t n_indices,
+                                const pe_block_ops_params* params,
+                                int32_t* status, pe_block_ops_stats* out);
+
 /* ---- SSZ roots of the resident per-validator lists -------------------------- */
 /* hash_tree_root (named at pe:142, 423, 1016; the reference holds no text of it) by the SSZ specification's rules: chunks of
  * 32 bytes; basic values packed little-endian, the last chunk zero-padded; Z[0] = 32 zero bytes, Z[k+1] = H(Z[k] || Z[k]);

@@ -137,6 +137,43 @@ class pe_slashings_stats(C.Structure):
                 ("n_penalised", C.c_uint64), ("penalties", C.c_uint64), ("n_saturated", C.c_uint64)]
 
 
+class pe_block_op(C.Structure):
+    """struct pe_block_op (include/posevo.h): one proposer slashing, attester slashing or voluntary exit, 408 bytes."""
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("data_1", C.c_uint8 * 128), ("data_2", C.c_uint8 * 128),
+                ("indices_1_offset", C.c_uint64), ("indices_1_length", C.c_uint64), ("indices_2_offset", C.c_uint64),
+                ("indices_2_length", C.c_uint64), ("header_1_slot", C.c_uint64), ("header_1_proposer_index", C.c_uint64),
+                ("header_1_root", C.c_uint8 * 32), ("header_2_slot", C.c_uint64), ("header_2_proposer_index", C.c_uint64),
+                ("header_2_root", C.c_uint8 * 32), ("validator_index", C.c_uint64), ("exit_epoch", C.c_uint64)]
+
+
+assert C.sizeof(pe_block_op) == 408
+
+
+class pe_block_ops_params(C.Structure):
+    """struct pe_block_ops_params (include/posevo.h): the constants of pe_process_block_operations."""
+    _fields_ = [("min_slashing_penalty_quotient", C.c_uint64), ("whistleblower_reward_quotient", C.c_uint64),
+                ("epochs_per_slashings_vector", C.c_uint64), ("shard_committee_period", C.c_uint64),
+                ("min_validator_withdrawability_delay", C.c_uint64), ("max_seed_lookahead", C.c_uint64),
+                ("min_per_epoch_churn_limit", C.c_uint64), ("churn_limit_quotient", C.c_uint64)]
+
+
+class pe_block_ops_stats(C.Structure):
+    """struct pe_block_ops_stats (include/posevo.h): what one pe_process_block_operations read and did."""
+    _fields_ = [("n_active", C.c_uint64), ("churn_limit", C.c_uint64), ("n_slashed", C.c_uint64),
+                ("n_exits_initiated", C.c_uint64), ("first_exit_epoch", C.c_uint64), ("last_exit_epoch", C.c_uint64),
+                ("slashed_balance", C.c_uint64), ("proposer_rewards", C.c_uint64), ("penalties", C.c_uint64),
+                ("n_saturated", C.c_uint64), ("n_invalid", C.c_uint64)]
+
+
+PE_OP_PROPOSER_SLASHING, PE_OP_ATTESTER_SLASHING, PE_OP_VOLUNTARY_EXIT = 1, 2, 3
+PE_OP_FLAG_SIGNATURE_VALID = 1
+OP_STATUS_NAMES = {
+    0: "ok", 64: "attestation data not slashable", 65: "bad indices", 66: "bad signature", 67: "nobody slashable",
+    68: "header mismatch", 69: "proposer not slashable", 70: "not active", 71: "already exiting",
+    72: "exit epoch in the future", 73: "too young to exit",
+}
+
+
 class pe_deposit_data(C.Structure):
     """struct pe_deposit_data (include/posevo.h): DepositData as it travels, 184 bytes."""
     _fields_ = [("pubkey", C.c_uint8 * 48), ("withdrawal_credentials", C.c_uint8 * 32), ("amount", C.c_uint64),
@@ -275,6 +312,9 @@ SIGNATURES = {
     "pe_registry_params_default": (None, [_P(pe_registry_params)]),
     "pe_registry_updates": (C.c_int, [_H, C.c_uint64, C.c_uint64, _P(pe_registry_params), _P(pe_registry_stats)]),
     "pe_process_slashings": (C.c_int, [_H, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _P(pe_slashings_stats)]),
+    "pe_block_ops_params_default": (None, [_P(pe_block_ops_params)]),
+    "pe_process_block_operations": (C.c_int, [_H, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, _u32p, C.c_uint64,
+                                              _P(pe_block_ops_params), _i32p, _P(pe_block_ops_stats)]),
     "pe_registry_set_static": (C.c_int, [_H, C.c_uint64, _u8p, _u8p, _u64p]),
     "pe_registry_get_static": (C.c_int, [_H, C.c_uint64, _u8p, _u8p, _u64p, C.c_void_p]),
     "pe_state_roots": (C.c_int, [_H, C.c_uint32, C.c_uint32, _P(pe_state_root_set), _u8p]),

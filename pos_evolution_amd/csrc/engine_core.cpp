@@ -376,6 +376,16 @@ const char* pe_strerror(int status)
         case PE_ERR_INVALID_INDEXED: return "invalid indexed attestation";
         case PE_ERR_STATE: return "call sequence error";
         case PE_ERR_TIMEOUT: return "multi-GPU exchange timed out";
+        case PE_OP_NOT_SLASHABLE_DATA: return "block operation: attestation data not slashable";
+        case PE_OP_BAD_INDICES: return "block operation: an index list is empty, not strictly ascending or leaves the registry";
+        case PE_OP_BAD_SIGNATURE: return "block operation: bad signature";
+        case PE_OP_NOBODY_SLASHABLE: return "block operation: no validator of the intersection is slashable";
+        case PE_OP_HEADER_MISMATCH: return "block operation: the headers' slots or proposers differ, or the headers are equal";
+        case PE_OP_PROPOSER_NOT_SLASHABLE: return "block operation: the proposer is not slashable";
+        case PE_OP_NOT_ACTIVE: return "block operation: the validator is not active";
+        case PE_OP_ALREADY_EXITING: return "block operation: the validator's exit is already initiated";
+        case PE_OP_EXIT_EPOCH_FUTURE: return "block operation: exit.epoch lies in the future";
+        case PE_OP_TOO_YOUNG: return "block operation: the validator has not been active for shard_committee_period epochs";
         default: return "unknown status";
     }
 }
@@ -550,7 +560,8 @@ void pe_engine_destroy(pe_engine* h)
                       &h->d_partials, &h->d_lane_partials, &h->d_out96, &h->d_tmp_points, &h->d_tmp_be, &h->d_tmp_points30,
                       &h->d_active, &h->d_active_wg, &h->d_registry_wg, &h->d_ssz_zero,
                       &h->d_ssz_validator_roots, &h->d_ssz_level[0], &h->d_ssz_level[1], &h->d_ssz_chunks, &h->d_bls, &h->d_batch, &h->d_verify,
-                      &h->d_dep_index, &h->d_deposit, &h->d_sync_members[0], &h->d_sync_members[1], &h->d_sync})
+                      &h->d_dep_index, &h->d_deposit, &h->d_sync_members[0], &h->d_sync_members[1], &h->d_sync,
+                      &h->d_block_ops})
         b->release();
     if (h->ev_active_read) (void)hipEventDestroy(h->ev_active_read);
     for (auto& t : h->tables) {

@@ -16,6 +16,7 @@
 //                      it: the active set, proposer sampling, rewards and penalties over resident balances and the
 //                      effective-balance hysteresis
 //   engine_deposit.cpp process_deposit over the resident registry: the pubkey index, proofs, verdicts of new keys, registry_grow
+//   engine_block_ops.cpp proposer slashings, attester slashings and voluntary exits over the resident registry
 // What host and device share of an attestation row: where its bits and its committee lie (att_row.h) and which status it
 // gets (att_rules.h).  The per-validator device arrays are one table (reg_columns.h), sized, filled and released through it.
 #pragma once
@@ -330,6 +331,7 @@ struct pe_engine {
     } sync_committee[2];
     DevBuf d_sync_members[2];
     DevBuf d_sync;  // one call's workspace: the Layout of pe_sync_committee_compute or of pe_process_sync_aggregate
+    DevBuf d_block_ops;  // one call's workspace: the Layout of pe_process_block_operations (engine_block_ops.cpp)
     // ---- pe_verify_resident (engine_resident_verify.cpp) ----
     // which aggregate the arena's d_res_points belong to: valid while that is still the handle's last aggregate of either kind
     struct ResidentVerify {

@@ -611,6 +611,47 @@ uint32_t launch_slashings_census(hipStream_t s, const uint64_t* eff_balance, con
 uint32_t launch_slashings_apply(hipStream_t s, const SlashingScalars& S, const uint64_t* eff_balance, const uint8_t* sflags,
                                 const uint64_t* withdrawable, uint64_t n_val, uint64_t* balances, uint64_t* partials);
 
+// Proposer slashings, attester slashings and voluntary exits over the resident registry (block_ops_kernels.hip; the rules, the
+// operation as the kernels read it, the scalar block and the totals are block_ops_row.h).  One lane per slot, BLOCK_OPS_WG per
+// workgroup; every launch of a call covers n_slots + 1 lanes = block_ops_workgroups(n_slots) workgroups (the last lane holds
+// no candidate: it carries the proposer's rewards where nobody slashes the proposer).
+//   launch_block_ops_lists    read-only: d_slot_val / d_slot_op[n_slots], d_op_bad[n_ops] (zeroed by the caller) |= a bad list
+//   launch_block_ops_resolve  read-only, three kernels: the two tables (u32[n_val] each, 0xFF-filled by the caller) by minima,
+//                             then d_slot_ev[n_slots], d_op_status[n_ops] of the single operations, d_op_hit[n_ops] (zeroed by
+//                             the caller), the workgroups' partials, their exclusive offsets and *d_totals
+//   launch_block_ops_apply    the writes; d_sums[2] (zeroed by the caller) += Gwei debited, subtractions cut at 0
+struct BlockOpDev;
+struct BlockOpsScalars;
+struct BlockOpsTotals;
+struct U64Div;
+constexpr int BLOCK_OPS_WG = 256;
+struct BlockOpsRegistry {  // the resident columns the read-only passes read
+    const uint64_t *activation_epoch, *exit_epoch, *withdrawable, *eff_balance, *balances;
+    const uint8_t* sflags;
+};
+struct BlockOpsWgPart {
+    uint32_t n_fresh, n_slashed;
+    unsigned long long rewards, slashed_balance, max_eff_slashed;
+};
+struct BlockOpsWgOffset {
+    uint32_t fresh, pad;
+    unsigned long long rewards;
+};
+uint32_t block_ops_workgroups(uint32_t n_slots);
+void launch_block_ops_lists(hipStream_t s, const BlockOpDev* d_ops, const uint32_t* d_slot_off, uint32_t n_ops,
+                            const uint32_t* d_indices, uint64_t n_val, uint32_t n_slots, uint32_t* d_slot_val, uint32_t* d_slot_op,
+                            uint32_t* d_op_bad);
+void launch_block_ops_resolve(hipStream_t s, const BlockOpDev* d_ops, const uint32_t* d_slot_val, const uint32_t* d_slot_op,
+                              const uint32_t* d_op_bad, uint32_t n_slots, const BlockOpsRegistry& R, uint64_t current_epoch,
+                              uint64_t shard_committee_period, const U64Div& by_reward_quotient, uint32_t* d_first_potent,
+                              uint32_t* d_first_slash, uint8_t* d_slot_ev, uint32_t* d_op_status, uint32_t* d_op_hit,
+                              BlockOpsWgPart* d_wg_part, BlockOpsWgOffset* d_wg_offset, uint32_t proposer_index,
+                              BlockOpsTotals* d_totals);
+void launch_block_ops_apply(hipStream_t s, const BlockOpsScalars& S, const uint32_t* d_slot_val, const uint8_t* d_slot_ev,
+                            const BlockOpsWgOffset* d_wg_offset, const uint32_t* d_first_slash, const uint64_t* d_eff_balance,
+                            uint64_t* d_exit_epoch, uint64_t* d_withdrawable, uint8_t* d_sflags, uint64_t* d_balances,
+                            uint64_t* d_sums);
+
 // compute_committee / compute_shuffled_index (pe:495-534) for a whole list: members[i] = indices[shuffled(i)].
 // d_source: rounds * ceil(n/256) * 8 words scratch; d_pivots: rounds words; d_indices null = identity.
 int launch_shuffle(hipStream_t s, const uint32_t* d_seed_be, uint32_t n, uint32_t rounds, uint32_t* d_source,

@@ -123,6 +123,68 @@ def pack_attestations(rows: Sequence[AttRow]):
     return arr, np.ascontiguousarray(arena)
 
 
+# -- block operations (pe_block_op): plain dicts, one constructor per kind ----
+def attestation_data_bytes(row) -> bytes:
+    """AttestationData as a pe_block_op carries it: the leading 128 bytes of the row's pe_attestation.  row: an AttRow, a
+    pe_attestation, a row of a structured array (144 bytes) or 128+ bytes."""
+    if isinstance(row, AttRow):
+        row = pack_attestations([row])[0][0]
+    if isinstance(row, pe_attestation):
+        return bytes(C.string_at(C.addressof(row), 128))
+    b = row.tobytes() if hasattr(row, "tobytes") else bytes(row)
+    assert len(b) >= 128, "AttestationData is the leading 128 bytes of a pe_attestation"
+    return b[:128]
+
+
+def attester_slashing_op(data_1, indices_1, data_2, indices_2, signature_valid: bool = True) -> dict:
+    """AttesterSlashing: two IndexedAttestations as (AttestationData, attesting_indices); signature_valid: the verdict over
+    both aggregate signatures."""
+    return dict(kind=_abi.PE_OP_ATTESTER_SLASHING, d1=attestation_data_bytes(data_1), d2=attestation_data_bytes(data_2),
+                i1=[int(x) for x in indices_1], i2=[int(x) for x in indices_2], sig=bool(signature_valid))
+
+
+def proposer_slashing_op(slot_1: int, proposer_index_1: int, root_1: bytes, slot_2: int, proposer_index_2: int, root_2: bytes,
+                         signature_valid: bool = True) -> dict:
+    """ProposerSlashing: of each signed header its slot, proposer index and hash_tree_root; signature_valid: both verdicts."""
+    return dict(kind=_abi.PE_OP_PROPOSER_SLASHING, slot1=int(slot_1), prop1=int(proposer_index_1), root1=bytes(root_1),
+                slot2=int(slot_2), prop2=int(proposer_index_2), root2=bytes(root_2), sig=bool(signature_valid))
+
+
+def voluntary_exit_op(validator_index: int, epoch: int, signature_valid: bool = True) -> dict:
+    """SignedVoluntaryExit: message.validator_index, message.epoch and the verdict over its signature."""
+    return dict(kind=_abi.PE_OP_VOLUNTARY_EXIT, index=int(validator_index), epoch=int(epoch), sig=bool(signature_valid))
+
+
+def pack_block_ops(ops):
+    """-> (ctypes array of pe_block_op, the attester slashings' lists as one flat uint32 array)."""
+    arr = (_abi.pe_block_op * max(len(ops), 1))()
+    lists, off = [], 0
+    for i, op in enumerate(ops):
+        a = arr[i]
+        a.kind = int(op["kind"])
+        a.flags = _abi.PE_OP_FLAG_SIGNATURE_VALID if op["sig"] else 0
+        if a.kind == _abi.PE_OP_ATTESTER_SLASHING:
+            C.memmove(a.data_1, op["d1"], 128)
+            C.memmove(a.data_2, op["d2"], 128)
+            for name, idx in (("indices_1", op["i1"]), ("indices_2", op["i2"])):
+                idx = np.asarray(idx, dtype=np.uint64)
+                assert idx.size == 0 or int(idx.max()) < 2**32, "a validator index beyond 32 bits"
+                setattr(a, name + "_offset", off)
+                setattr(a, name + "_length", idx.size)
+                lists.append(idx.astype(np.uint32))
+                off += idx.size
+        elif a.kind == _abi.PE_OP_PROPOSER_SLASHING:
+            a.header_1_slot, a.header_1_proposer_index = op["slot1"], op["prop1"]
+            a.header_2_slot, a.header_2_proposer_index = op["slot2"], op["prop2"]
+            assert len(op["root1"]) == 32 and len(op["root2"]) == 32, "roots are 32 bytes"
+            C.memmove(a.header_1_root, op["root1"], 32)
+            C.memmove(a.header_2_root, op["root2"], 32)
+        else:
+            a.validator_index, a.exit_epoch = op["index"], op["epoch"]
+    flat = np.ascontiguousarray(np.concatenate(lists)) if lists else np.zeros(0, dtype=np.uint32)
+    return arr, flat
+
+
 _ATT_DTYPE = np.dtype([
     ("slot", "<u8"), ("index", "<u8"), ("beacon_block_root", "u1", (32,)),
     ("source_epoch", "<u8"), ("source_root", "u1", (32,)),
@@ -1278,6 +1340,35 @@ class Engine:
                                                    int(proportional_slashing_multiplier), int(epochs_per_slashings_vector),
                                                    C.byref(st)))
         return {name: int(getattr(st, name)) for name, _ in _abi.pe_slashings_stats._fields_}
+
+    # -- block operations over the resident registry: slashings and exits ----
+    def block_ops_params(self, **overrides):
+        """pe_block_ops_params_default with fields replaced by keyword (min_slashing_penalty_quotient,
+        whistleblower_reward_quotient, epochs_per_slashings_vector, shard_committee_period,
+        min_validator_withdrawability_delay, max_seed_lookahead, min_per_epoch_churn_limit, churn_limit_quotient)."""
+        p = _abi.pe_block_ops_params()
+        self._lib.pe_block_ops_params_default(C.byref(p))
+        for k, v in overrides.items():
+            assert hasattr(p, k), k
+            setattr(p, k, int(v))
+        return p
+
+    def process_block_operations(self, current_epoch: int, proposer_index: int, ops, params=None):
+        """process_proposer_slashing / process_attester_slashing / process_voluntary_exit over the resident registry, in
+        array order, each on what the earlier ones left (pe_process_block_operations).  ops: ``attester_slashing_op``,
+        ``proposer_slashing_op`` and ``voluntary_exit_op`` dicts.  params: ``block_ops_params(...)``, a dict of its
+        overrides, or None for the defaults.  -> (status int32[n_ops], pe_block_ops_stats as a dict).  If any status is
+        not 0 the block is invalid and NOTHING was changed (stats["n_invalid"] counts them); the caller adds
+        stats["slashed_balance"] to state.slashings[current_epoch % EPOCHS_PER_SLASHINGS_VECTOR]."""
+        if params is None or isinstance(params, dict):
+            params = self.block_ops_params(**(params or {}))
+        arr, flat = pack_block_ops(ops)
+        status = np.zeros(max(len(ops), 1), dtype=np.int32)
+        st = _abi.pe_block_ops_stats()
+        self._check(self._lib.pe_process_block_operations(self._h, int(current_epoch), int(proposer_index), C.addressof(arr),
+                                                          len(ops), _ptr(flat if flat.size else None, C.c_uint32), flat.size,
+                                                          C.byref(params), _ptr(status), C.byref(st)))
+        return status[:len(ops)], {name: int(getattr(st, name)) for name, _ in _abi.pe_block_ops_stats._fields_}
 
     # -- SSZ roots of the resident lists ------------------------------------
     def registry_set_static(self, pubkeys48, withdrawal_credentials, activation_eligibility_epoch):

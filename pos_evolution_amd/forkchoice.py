@@ -19,6 +19,10 @@ pos-evolution.md (``pe:N``):
     process_rewards_and_penalties(state)                    Altair; fields pe:112, pe:45 (state bound with bind_state)
     process_registry_updates(state)                         fields pe:36-45; churn limit pe:1261 (state bound with bind_state)
     process_slashings(state)                                fields pe:359/397 (state bound with bind_state)
+    process_proposer_slashing(state, proposer_slashing)     fields pe:36-45, pe:359/397 (state bound with bind_state)
+    process_attester_slashing(state, attester_slashing)     pe:1134-1143 and the same fields (state bound with bind_state)
+    process_voluntary_exit(state, signed_voluntary_exit)    fields pe:43-45 (state bound with bind_state)
+    attester_slashing_ops_from_evidence(evidence)           find_attester_slashings' output as operations of the three above
     get_active_validator_indices(state, epoch)              named at pe:467 (state bound with bind_state)
     get_committee_count_per_slot(state, epoch)              pe:461-468
     compute_weak_subjectivity_period(state)                 pe:1257-1287
@@ -46,7 +50,8 @@ from typing import Callable, Dict, Iterable, List, Optional, Sequence
 import numpy as np
 
 from . import _abi
-from .engine import ROWS_RESIDENT, AttRow, Engine, EngineError, ZERO_ROOT
+from .engine import (ROWS_RESIDENT, AttRow, Engine, EngineError, ZERO_ROOT, attester_slashing_op, proposer_slashing_op,
+                     voluntary_exit_op)
 from ._abi import pe_state_ctx
 
 GENESIS_EPOCH = 0
@@ -768,6 +773,100 @@ def process_slashings(state, *, proportional_slashing_multiplier: int = 3, epoch
     state._last_slashings_stats = e.process_slashings(current_epoch, sum(int(x) for x in state.slashings),
                                                       proportional_slashing_multiplier, epochs_per_slashings_vector)
     state.balances[:] = [int(x) for x in e.state_get_balances()[0]]
+
+
+# ----------------------------------------------------------------------------- block operations: slashings and exits
+def _block_operations(state, ops, proposer_index: int, params: dict, who: str) -> dict:
+    """One pe_process_block_operations over a bound state: the epochs, balances and withdrawable epochs go up, and -- only
+    if every operation is valid -- the exit and withdrawable epochs, the balances and the slashed flags come back and
+    ``slashed_balance`` joins ``state.slashings`` where the state has one.  An invalid operation raises AssertionError, as the
+    pyspec's assert would, and the state is untouched.  The path without any transfer is ``Engine.process_block_operations``
+    over arrays that stay resident."""
+    b = _binding(state)
+    assert b is not None, who + ": bind_state(engine, state, ...) first"
+    vals, n, e = state.validators, len(state.validators), b.engine
+    e.registry_set_epochs(_u64_of((v.activation_epoch for v in vals), n), _u64_of((v.exit_epoch for v in vals), n))
+    scores = getattr(state, "inactivity_scores", None)
+    e.state_set_balances(_u64_of(state.balances, n), None if scores is None else _u64_of(scores, n),
+                         _u64_of((v.withdrawable_epoch for v in vals), n))
+    current_epoch = int(state.slot) // int(e.cfg.slots_per_epoch)
+    status, stats = e.process_block_operations(current_epoch, int(proposer_index), ops, params)
+    state._last_block_ops_stats = stats
+    bad = [(i, int(s)) for i, s in enumerate(status) if s != 0]
+    assert not bad, who + ": " + ", ".join(f"operation {i}: {_abi.OP_STATUS_NAMES.get(s, s)}" for i, s in bad)
+    _, ext, _ = e.registry_get_epochs()
+    bal, _, wdr, _ = e.state_get_balances()
+    _, flags, _ = e.state_validators()
+    for v, x, w, f in zip(vals, ext, wdr, flags):
+        v.exit_epoch, v.withdrawable_epoch, v.slashed = int(x), int(w), bool(f & _abi.PE_VAL_SLASHED)
+    state.balances[:] = [int(x) for x in bal]
+    slashings = getattr(state, "slashings", None)
+    if slashings is not None and len(slashings) and stats["slashed_balance"]:
+        k = current_epoch % int((params or {}).get("epochs_per_slashings_vector", 8192)) % len(slashings)
+        slashings[k] = int(slashings[k]) + stats["slashed_balance"]
+    return stats
+
+
+def _proposer_of(state, proposer_index, get_beacon_proposer_index, who: str) -> int:
+    if proposer_index is None:
+        assert get_beacon_proposer_index is not None, who + ": pass proposer_index or get_beacon_proposer_index"
+        proposer_index = get_beacon_proposer_index(state)
+    return int(proposer_index)
+
+
+def _data_row(d) -> AttRow:
+    return AttRow(int(d.slot), int(d.index), bytes(d.beacon_block_root), int(d.source.epoch), bytes(d.source.root),
+                  int(d.target.epoch), bytes(d.target.root), np.zeros(0, dtype=np.uint8))
+
+
+def _attester_slashing_op(attester_slashing, signature_valid: bool) -> dict:
+    a1, a2 = attester_slashing.attestation_1, attester_slashing.attestation_2
+    valid = bool(signature_valid) and bool(getattr(a1, "signature_valid", True)) and bool(getattr(a2, "signature_valid", True))
+    return attester_slashing_op(_data_row(a1.data), list(a1.attesting_indices), _data_row(a2.data), list(a2.attesting_indices), valid)
+
+
+def process_attester_slashing(state, attester_slashing, *, signature_valid: bool = True, proposer_index: Optional[int] = None,
+                              get_beacon_proposer_index: Optional[Callable] = None, **params) -> None:
+    """process_attester_slashing over a state bound with ``bind_state`` (pe_process_block_operations): every slashable
+    validator of the two lists' intersection is slashed.  ``signature_valid``: the verdict over both aggregate signatures
+    (AND-ed with the attestations' own ``signature_valid`` where they carry one).  Keywords replace fields of
+    pe_block_ops_params.  Raises AssertionError on an invalid operation; the state is then untouched."""
+    who = "process_attester_slashing"
+    _block_operations(state, [_attester_slashing_op(attester_slashing, signature_valid)],
+                      _proposer_of(state, proposer_index, get_beacon_proposer_index, who), params, who)
+
+
+def process_proposer_slashing(state, proposer_slashing, *, hash_tree_root: Callable, signature_valid: bool = True,
+                              proposer_index: Optional[int] = None, get_beacon_proposer_index: Optional[Callable] = None,
+                              **params) -> None:
+    """process_proposer_slashing over a bound state: ``proposer_slashing.signed_header_1 / _2 .message`` are the two
+    BeaconBlockHeaders, compared by slot, proposer index and ``hash_tree_root``.  ``proposer_index``: the proposer of the
+    block that carries the operation (it earns the whistleblower reward)."""
+    who = "process_proposer_slashing"
+    h1, h2 = proposer_slashing.signed_header_1.message, proposer_slashing.signed_header_2.message
+    op = proposer_slashing_op(int(h1.slot), int(h1.proposer_index), bytes(hash_tree_root(h1)), int(h2.slot), int(h2.proposer_index),
+                              bytes(hash_tree_root(h2)), signature_valid)
+    _block_operations(state, [op], _proposer_of(state, proposer_index, get_beacon_proposer_index, who), params, who)
+
+
+def process_voluntary_exit(state, signed_voluntary_exit, *, signature_valid: bool = True, **params) -> None:
+    """process_voluntary_exit over a bound state: ``signed_voluntary_exit.message`` names validator_index and epoch."""
+    m = signed_voluntary_exit.message
+    # no slashing, no reward: the proposer is not read, any validator stands in
+    _block_operations(state, [voluntary_exit_op(int(m.validator_index), int(m.epoch), signature_valid)], 0, params,
+                      "process_voluntary_exit")
+
+
+def attester_slashing_ops_from_evidence(evidence: Iterable, signature_valid: bool = True) -> List[dict]:
+    """``find_attester_slashings`` output -> single-validator operations for ``Engine.process_block_operations``, by the
+    slasher's own convention (include/posevo.h: on_attester_slashing with attesting_indices = [v] on both sides): one
+    operation per (pair of AttestationData, validator), in the evidence's order and ascending validators."""
+    ops = []
+    for s in evidence:
+        both = sorted(set(s.attestation_1.attesting_indices) & set(s.attestation_2.attesting_indices))
+        ops += [attester_slashing_op(_data_row(s.attestation_1.data), [v], _data_row(s.attestation_2.data), [v], signature_valid)
+                for v in both]
+    return ops
 
 
 # ----------------------------------------------------------------------------- deposits
