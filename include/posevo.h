@@ -751,6 +751,131 @@ int pe_process_block_operations(pe_engine* h, uint64_t current_epoch, uint32_t p
                                 const pe_block_ops_params* params,
                                 int32_t* status, pe_block_ops_stats* out);
 
+/* ---- Capella: withdrawals and BLS-to-execution changes over the resident registry -------- */
+/* process_withdrawals (with get_expected_withdrawals, is_fully_withdrawable_validator, is_partially_withdrawable_validator and
+ * has_eth1_withdrawal_credential under it) and process_bls_to_execution_change (Capella; the rule set is restated in
+ * tests/withdrawals_model.py: the reference holds the Validator fields, pe:36-45, and `balances`, pe:112, not these
+ * functions' text). */
+#pragma pack(push, 1)
+typedef struct pe_withdrawal {      /* Withdrawal as it travels: 44 bytes, no padding */
+    uint64_t index;
+    uint64_t validator_index;
+    uint8_t  address[20];
+    uint64_t amount;
+} pe_withdrawal;
+#pragma pack(pop)
+
+typedef struct pe_withdrawals_params {
+    uint64_t max_effective_balance;        /* 32 * 10^9 */
+    uint64_t max_withdrawals_per_payload;  /* 16 (minimal preset: 4); at most 64 */
+    uint64_t max_validators_per_sweep;     /* 16384 (minimal preset: 16); may exceed the registry */
+    uint64_t eth1_prefix;                  /* 0x01: ETH1_ADDRESS_WITHDRAWAL_PREFIX, one byte */
+} pe_withdrawals_params;
+void pe_withdrawals_params_default(pe_withdrawals_params* out);
+
+#define PE_WD_APPLY   0x1u  /* debit the balances: process_withdrawals.  Needs PE_WD_PAYLOAD.  Without it the call only computes:
+                               get_expected_withdrawals, what a proposer building a payload needs */
+#define PE_WD_PAYLOAD 0x2u  /* payload / n_payload are the execution payload's withdrawals (n_payload may be 0) */
+
+/* pe_withdrawals_result.status: 0, or process_withdrawals' first failing assert over the payload */
+typedef enum pe_wd_status {
+    PE_WD_OK = 0,
+    PE_WD_COUNT_MISMATCH = 80,      /* len(payload.withdrawals) != len(expected_withdrawals) */
+    PE_WD_INDEX_MISMATCH = 81,      /* the first differing entry differs in its index, ... */
+    PE_WD_VALIDATOR_MISMATCH = 82,  /* ... else in its validator_index, ... */
+    PE_WD_ADDRESS_MISMATCH = 83,    /* ... else in its address, ... */
+    PE_WD_AMOUNT_MISMATCH = 84      /* ... else in its amount */
+} pe_wd_status;
+
+typedef struct pe_withdrawals_result {
+    uint64_t next_withdrawal_index;            /* behind the last expected withdrawal; unchanged if there is none */
+    uint64_t next_withdrawal_validator_index;  /* (the last withdrawal's validator + 1) mod n where the list is full, else
+                                                  (start + max_validators_per_sweep) mod n -- the parameter, not the bound */
+    uint64_t n_full, n_partial;                /* expected withdrawals of either kind */
+    uint64_t total_gwei;                       /* their amounts, cut at 2^64 - 1 */
+    uint32_t n_withdrawals;                    /* entries written to out_withdrawals */
+    int32_t  status;                           /* pe_wd_status */
+    uint32_t first_mismatch;                   /* status != 0: the first differing entry (the shorter length where the
+                                                  lengths differ) */
+    uint32_t applied;                          /* 1: the balances were debited */
+    uint8_t  withdrawals_root[32];             /* hash_tree_root(List[Withdrawal, max_withdrawals_per_payload]) of the
+                                                  expected list */
+} pe_withdrawals_result;
+
+/* The withdrawal sweep over the resident registry, exactly the sequential loop: bound = min(n, max_validators_per_sweep)
+ * positions, position j visits validator (next_withdrawal_validator_index + j) mod n.  A visited validator yields
+ *   a full withdrawal of balance                           if credentials[0] == eth1_prefix, withdrawable_epoch <=
+ *                                                          current_epoch and balance > 0;
+ *   else a partial one of balance - max_effective_balance  if credentials[0] == eth1_prefix, effective_balance ==
+ *                                                          max_effective_balance and balance > max_effective_balance,
+ * to the address credentials[12:32], with consecutive indices from next_withdrawal_index; the loop stops at the
+ * max_withdrawals_per_payload-th hit.  bound <= n: no validator is visited twice, the positions behind the last hit taken are
+ * not touched.  Comparisons unsigned 64-bit.
+ * out_withdrawals (room for max_withdrawals_per_payload entries; may be NULL) takes the expected list, *out the rest.
+ * With PE_WD_PAYLOAD the payload must equal the expected list in length and in every field; else THE BLOCK IS INVALID: the
+ * call returns PE_OK, out->status and out->first_mismatch say where, and NOTHING CHANGES (out still describes the expected
+ * list).  With PE_WD_APPLY and a matching payload the balances of the expected withdrawals' validators are debited.
+ * Reads the credentials (pe_registry_set_static), the withdrawable epochs and balances (pe_state_set_balances) and the
+ * working-state view's effective balances (the pe_set_validators data while the view mirrors it; the view is not
+ * materialised); writes the balances alone.  pe_state_get_balances reads them back, pe_state_roots hashes them with no
+ * further call.  Read-only passes (k_withdrawals_flag, _scan, _select: the first hits in position order by wave ballots and
+ * an ordered scan of per-workgroup counts), a host step (the comparison, the next indices, the list root), one writing pass
+ * (k_withdrawals_apply: one writer per balance, no atomic).  Synchronous (completes open pipelines first); one GPU.  A
+ * block runs this call before pe_process_block_operations.  A failing call changes nothing:
+ *   PE_ERR_STATE        the epochs, the balances or the static part are not resident, the view does not cover the registry,
+ *                       or pe_dist_init* active
+ *   PE_ERR_INVALID_ARG  the registry is empty; next_withdrawal_validator_index >= n; a parameter is 0; eth1_prefix above
+ *                       0xFF; max_withdrawals_per_payload above 64; n_payload above it; next_withdrawal_index +
+ *                       max_withdrawals_per_payload wraps; PE_WD_APPLY without PE_WD_PAYLOAD; unknown flag bits */
+int pe_process_withdrawals(pe_engine* h, uint64_t current_epoch, uint64_t next_withdrawal_index,
+                           uint64_t next_withdrawal_validator_index, const pe_withdrawals_params* params,
+                           const pe_withdrawal* payload, uint32_t n_payload, uint32_t flags,
+                           pe_withdrawal* out_withdrawals, pe_withdrawals_result* out);
+
+#define PE_CRED_FLAG_SIGNATURE_VALID 0x1u /* the injected verdict over the SignedBLSToExecutionChange's signature: the caller
+                                             computes it with the BLS calls from pe_bls_change_signing_roots, as
+                                             PE_OP_FLAG_SIGNATURE_VALID */
+typedef struct pe_bls_change {      /* BLSToExecutionChange and its verdict: 80 bytes */
+    uint64_t validator_index;
+    uint8_t  from_bls_pubkey[48];
+    uint8_t  to_execution_address[20];
+    uint32_t flags;                 /* PE_CRED_FLAG_* */
+} pe_bls_change;
+
+/* status[i] of pe_process_bls_to_execution_changes: 0 = valid, else the first assert of the change that fails, in its order */
+typedef enum pe_cred_status {
+    PE_CRED_OK = 0,
+    PE_CRED_BAD_INDEX = 96,         /* validator_index >= n */
+    PE_CRED_NOT_BLS = 97,           /* credentials[0] != 0x00 (before the call, or by an earlier change of it) */
+    PE_CRED_PUBKEY_MISMATCH = 98,   /* credentials[1:] != SHA-256(from_bls_pubkey)[1:] */
+    PE_CRED_BAD_SIGNATURE = 99      /* the injected verdict is false */
+} pe_cred_status;
+
+typedef struct pe_bls_changes_stats {
+    uint64_t n_applied;             /* credentials written */
+    uint64_t n_invalid;             /* changes with a status != 0 */
+} pe_bls_changes_stats;
+
+/* An ordered list of address changes applied to the resident withdrawal credentials with the semantics of the sequential
+ * loop: a valid change writes 0x01 || 0^11 || to_execution_address; of two changes that name one validator the first that
+ * passes every check takes effect and the second then fails the prefix check.  The hash is the plain SHA-256 of the 48 key
+ * bytes, computed on the device from the change (not the SSZ leaf the static part keeps).
+ * A BLOCK WITH AN INVALID CHANGE IS AN INVALID BLOCK: the call writes every status and, if any is not 0, CHANGES NOTHING (it
+ * still returns PE_OK; out->n_invalid counts them).  Writes the credentials (pe_registry_set_static) alone;
+ * pe_registry_get_static reads them back, pe_state_roots hashes them.  Read-only passes (k_bls_changes_claim, _resolve: the
+ * first potent change per validator by a minimum over positions), one writing pass (k_bls_changes_apply: one writer per
+ * validator).  Synchronous (completes open pipelines first); one GPU.  status: n_changes entries; out may be NULL.  A block
+ * runs this call after its voluntary exits.  A failing call changes nothing:
+ *   PE_ERR_STATE        the static part is not resident, or pe_dist_init* active
+ *   PE_ERR_CAPACITY     the registry holds 2^32 or more validators */
+int pe_process_bls_to_execution_changes(pe_engine* h, const pe_bls_change* changes, uint32_t n_changes, int32_t* status,
+                                        pe_bls_changes_stats* out);
+/* out_roots32[32 i ..] = compute_signing_root(BLSToExecutionChange(change i), domain), hashed on the device; the flags are not
+ * read.  pe_hash_to_g2 of these and pe_pairing_check / pe_batch_verify against from_bls_pubkey give the verdicts.
+ * Synchronous; needs no registry. */
+int pe_bls_change_signing_roots(pe_engine* h, const pe_bls_change* changes, uint32_t n, const uint8_t domain[32],
+                                uint8_t* out_roots32);
+
 /* ---- SSZ roots of the resident per-validator lists -------------------------- */
 /* hash_tree_root (named at pe:142, 423, 1016; the reference holds no text of it) by the SSZ specification's rules: chunks of
  * 32 bytes; basic values packed little-endian, the last chunk zero-padded; Z[0] = 32 zero bytes, Z[k+1] = H(Z[k] || Z[k]);

@@ -174,6 +174,52 @@ OP_STATUS_NAMES = {
 }
 
 
+class pe_withdrawal(C.Structure):
+    """struct pe_withdrawal (include/posevo.h): Withdrawal as it travels, 44 bytes packed."""
+    _pack_ = 1
+    _fields_ = [("index", C.c_uint64), ("validator_index", C.c_uint64), ("address", C.c_uint8 * 20), ("amount", C.c_uint64)]
+
+
+assert C.sizeof(pe_withdrawal) == 44
+
+
+class pe_withdrawals_params(C.Structure):
+    """struct pe_withdrawals_params (include/posevo.h): the constants of pe_process_withdrawals."""
+    _fields_ = [("max_effective_balance", C.c_uint64), ("max_withdrawals_per_payload", C.c_uint64),
+                ("max_validators_per_sweep", C.c_uint64), ("eth1_prefix", C.c_uint64)]
+
+
+class pe_withdrawals_result(C.Structure):
+    """struct pe_withdrawals_result (include/posevo.h): what one pe_process_withdrawals found and did."""
+    _fields_ = [("next_withdrawal_index", C.c_uint64), ("next_withdrawal_validator_index", C.c_uint64), ("n_full", C.c_uint64),
+                ("n_partial", C.c_uint64), ("total_gwei", C.c_uint64), ("n_withdrawals", C.c_uint32), ("status", C.c_int32),
+                ("first_mismatch", C.c_uint32), ("applied", C.c_uint32), ("withdrawals_root", C.c_uint8 * 32)]
+
+
+class pe_bls_change(C.Structure):
+    """struct pe_bls_change (include/posevo.h): BLSToExecutionChange and its verdict, 80 bytes."""
+    _fields_ = [("validator_index", C.c_uint64), ("from_bls_pubkey", C.c_uint8 * 48), ("to_execution_address", C.c_uint8 * 20),
+                ("flags", C.c_uint32)]
+
+
+assert C.sizeof(pe_bls_change) == 80
+
+
+class pe_bls_changes_stats(C.Structure):
+    """struct pe_bls_changes_stats (include/posevo.h): what one pe_process_bls_to_execution_changes did."""
+    _fields_ = [("n_applied", C.c_uint64), ("n_invalid", C.c_uint64)]
+
+
+PE_WD_APPLY, PE_WD_PAYLOAD = 1, 2
+PE_WD_OK, PE_WD_COUNT_MISMATCH, PE_WD_INDEX_MISMATCH, PE_WD_VALIDATOR_MISMATCH = 0, 80, 81, 82
+PE_WD_ADDRESS_MISMATCH, PE_WD_AMOUNT_MISMATCH = 83, 84
+WD_STATUS_NAMES = {0: "ok", 80: "count mismatch", 81: "index mismatch", 82: "validator mismatch", 83: "address mismatch",
+                   84: "amount mismatch"}
+PE_CRED_FLAG_SIGNATURE_VALID = 1
+PE_CRED_OK, PE_CRED_BAD_INDEX, PE_CRED_NOT_BLS, PE_CRED_PUBKEY_MISMATCH, PE_CRED_BAD_SIGNATURE = 0, 96, 97, 98, 99
+CRED_STATUS_NAMES = {0: "ok", 96: "bad index", 97: "not BLS credentials", 98: "pubkey mismatch", 99: "bad signature"}
+
+
 class pe_deposit_data(C.Structure):
     """struct pe_deposit_data (include/posevo.h): DepositData as it travels, 184 bytes."""
     _fields_ = [("pubkey", C.c_uint8 * 48), ("withdrawal_credentials", C.c_uint8 * 32), ("amount", C.c_uint64),
@@ -315,6 +361,11 @@ SIGNATURES = {
     "pe_block_ops_params_default": (None, [_P(pe_block_ops_params)]),
     "pe_process_block_operations": (C.c_int, [_H, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, _u32p, C.c_uint64,
                                               _P(pe_block_ops_params), _i32p, _P(pe_block_ops_stats)]),
+    "pe_withdrawals_params_default": (None, [_P(pe_withdrawals_params)]),
+    "pe_process_withdrawals": (C.c_int, [_H, C.c_uint64, C.c_uint64, C.c_uint64, _P(pe_withdrawals_params), C.c_void_p,
+                                         C.c_uint32, C.c_uint32, C.c_void_p, _P(pe_withdrawals_result)]),
+    "pe_process_bls_to_execution_changes": (C.c_int, [_H, C.c_void_p, C.c_uint32, _i32p, _P(pe_bls_changes_stats)]),
+    "pe_bls_change_signing_roots": (C.c_int, [_H, C.c_void_p, C.c_uint32, _u8p, _u8p]),
     "pe_registry_set_static": (C.c_int, [_H, C.c_uint64, _u8p, _u8p, _u64p]),
     "pe_registry_get_static": (C.c_int, [_H, C.c_uint64, _u8p, _u8p, _u64p, C.c_void_p]),
     "pe_state_roots": (C.c_int, [_H, C.c_uint32, C.c_uint32, _P(pe_state_root_set), _u8p]),

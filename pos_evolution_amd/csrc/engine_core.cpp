@@ -386,6 +386,15 @@ const char* pe_strerror(int status)
         case PE_OP_ALREADY_EXITING: return "block operation: the validator's exit is already initiated";
         case PE_OP_EXIT_EPOCH_FUTURE: return "block operation: exit.epoch lies in the future";
         case PE_OP_TOO_YOUNG: return "block operation: the validator has not been active for shard_committee_period epochs";
+        case PE_WD_COUNT_MISMATCH: return "withdrawals: the payload's list and the expected list differ in length";
+        case PE_WD_INDEX_MISMATCH: return "withdrawals: a payload withdrawal's index differs from the expected one";
+        case PE_WD_VALIDATOR_MISMATCH: return "withdrawals: a payload withdrawal's validator index differs from the expected one";
+        case PE_WD_ADDRESS_MISMATCH: return "withdrawals: a payload withdrawal's address differs from the expected one";
+        case PE_WD_AMOUNT_MISMATCH: return "withdrawals: a payload withdrawal's amount differs from the expected one";
+        case PE_CRED_BAD_INDEX: return "address change: the validator index lies outside the registry";
+        case PE_CRED_NOT_BLS: return "address change: the withdrawal credentials do not begin with the BLS prefix";
+        case PE_CRED_PUBKEY_MISMATCH: return "address change: the credentials are not the hash of from_bls_pubkey";
+        case PE_CRED_BAD_SIGNATURE: return "address change: bad signature";
         default: return "unknown status";
     }
 }
@@ -561,7 +570,7 @@ void pe_engine_destroy(pe_engine* h)
                       &h->d_active, &h->d_active_wg, &h->d_registry_wg, &h->d_ssz_zero,
                       &h->d_ssz_validator_roots, &h->d_ssz_level[0], &h->d_ssz_level[1], &h->d_ssz_chunks, &h->d_bls, &h->d_batch, &h->d_verify,
                       &h->d_dep_index, &h->d_deposit, &h->d_sync_members[0], &h->d_sync_members[1], &h->d_sync,
-                      &h->d_block_ops})
+                      &h->d_block_ops, &h->d_withdrawals})
         b->release();
     if (h->ev_active_read) (void)hipEventDestroy(h->ev_active_read);
     for (auto& t : h->tables) {

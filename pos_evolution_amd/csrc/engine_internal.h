@@ -17,6 +17,7 @@
 //                      effective-balance hysteresis
 //   engine_deposit.cpp process_deposit over the resident registry: the pubkey index, proofs, verdicts of new keys, registry_grow
 //   engine_block_ops.cpp proposer slashings, attester slashings and voluntary exits over the resident registry
+//   engine_withdrawals.cpp Capella's withdrawal sweep and BLS-to-execution changes over the resident registry
 // What host and device share of an attestation row: where its bits and its committee lie (att_row.h) and which status it
 // gets (att_rules.h).  The per-validator device arrays are one table (reg_columns.h), sized, filled and released through it.
 #pragma once
@@ -332,6 +333,7 @@ struct pe_engine {
     DevBuf d_sync_members[2];
     DevBuf d_sync;  // one call's workspace: the Layout of pe_sync_committee_compute or of pe_process_sync_aggregate
     DevBuf d_block_ops;  // one call's workspace: the Layout of pe_process_block_operations (engine_block_ops.cpp)
+    DevBuf d_withdrawals;  // one call's workspace: the Layouts of engine_withdrawals.cpp's three calls
     // ---- pe_verify_resident (engine_resident_verify.cpp) ----
     // which aggregate the arena's d_res_points belong to: valid while that is still the handle's last aggregate of either kind
     struct ResidentVerify {

@@ -652,6 +652,36 @@ void launch_block_ops_apply(hipStream_t s, const BlockOpsScalars& S, const uint3
                             uint64_t* d_exit_epoch, uint64_t* d_withdrawable, uint8_t* d_sflags, uint64_t* d_balances,
                             uint64_t* d_sums);
 
+// Capella's withdrawal sweep and BLS-to-execution changes over the resident registry (withdrawal_kernels.hip; the rules, the
+// record and the change as the kernels read them are withdrawals_row.h).  The sweep: one lane per position, WD_WG per
+// workgroup, withdrawals_workgroups(bound) workgroups.
+//   launch_withdrawals_sweep   read-only, three kernels: d_pos_kind[bound], d_wg_count / d_wg_offset[workgroups], *d_total
+//                              (every hit of the sweep) and the first min(total, k) records, WD_RECORD_WORDS words each
+//   launch_withdrawals_apply   the write: the balances of `count` records' validators
+//   launch_bls_changes_resolve read-only, two kernels: d_first (u32[n_val], 0xFF-filled by the caller) by minima, d_checks and
+//                              d_status[n_changes]; a change is CRED_CHANGE_WORDS words
+//   launch_bls_changes_apply   the write: the credentials of the valid changes' validators
+//   launch_bls_change_signing_roots  d_roots[32 i ..] = compute_signing_root(change i, domain); domain: big-endian words
+constexpr int WD_WG = 256;
+struct WithdrawalsColumns {  // the resident columns the sweep reads; credentials: 8 words a validator, memory order
+    const uint32_t* credentials;
+    const uint64_t *withdrawable, *eff_balance, *balances;
+};
+struct WithdrawalsSweep {
+    uint64_t n, start, current_epoch, max_effective_balance, next_index;
+    uint32_t bound, k, prefix;  // positions swept | max_withdrawals_per_payload | ETH1_ADDRESS_WITHDRAWAL_PREFIX
+};
+uint32_t withdrawals_workgroups(uint32_t bound);
+void launch_withdrawals_sweep(hipStream_t s, const WithdrawalsColumns& C, const WithdrawalsSweep& S, uint8_t* d_pos_kind,
+                              uint32_t* d_wg_count, uint32_t* d_wg_offset, uint32_t* d_total, uint32_t* d_records);
+void launch_withdrawals_apply(hipStream_t s, const uint32_t* d_records, uint32_t count, uint64_t n, uint64_t* d_balances);
+void launch_bls_changes_resolve(hipStream_t s, const uint32_t* d_changes, uint32_t n_changes, const uint8_t* d_credentials, uint64_t n,
+                                uint32_t* d_first, uint32_t* d_checks, uint32_t* d_status);
+void launch_bls_changes_apply(hipStream_t s, const uint32_t* d_changes, uint32_t n_changes, const uint32_t* d_status, uint64_t n,
+                              uint8_t* d_credentials);
+void launch_bls_change_signing_roots(hipStream_t s, const uint32_t* d_changes, uint32_t n_changes, const uint32_t domain[8],
+                                     uint32_t* d_roots);
+
 // compute_committee / compute_shuffled_index (pe:495-534) for a whole list: members[i] = indices[shuffled(i)].
 // d_source: rounds * ceil(n/256) * 8 words scratch; d_pivots: rounds words; d_indices null = identity.
 int launch_shuffle(hipStream_t s, const uint32_t* d_seed_be, uint32_t n, uint32_t rounds, uint32_t* d_source,

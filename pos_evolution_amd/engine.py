@@ -185,6 +185,39 @@ def pack_block_ops(ops):
     return arr, flat
 
 
+# -- Capella: withdrawals (pe_withdrawal) and address changes (pe_bls_change) ----
+WITHDRAWAL_DTYPE = np.dtype([("index", "<u8"), ("validator_index", "<u8"), ("address", "u1", (20,)),
+                             ("amount", "<u8")])  # == struct pe_withdrawal (44 bytes, packed)
+BLS_CHANGE_DTYPE = np.dtype([("validator_index", "<u8"), ("from_bls_pubkey", "u1", (48,)), ("to_execution_address", "u1", (20,)),
+                             ("flags", "<u4")])  # == struct pe_bls_change (80 bytes)
+assert WITHDRAWAL_DTYPE.itemsize == 44 and BLS_CHANGE_DTYPE.itemsize == 80
+
+
+def pack_withdrawals(withdrawals) -> np.ndarray:
+    """WITHDRAWAL_DTYPE rows, or an iterable of (index, validator_index, address20, amount)."""
+    if isinstance(withdrawals, np.ndarray) and withdrawals.dtype == WITHDRAWAL_DTYPE:
+        return np.ascontiguousarray(withdrawals)
+    items = list(withdrawals)
+    rows = np.zeros(len(items), dtype=WITHDRAWAL_DTYPE)
+    for i, (index, validator, address, amount) in enumerate(items):
+        assert len(address) == 20, "an execution address is 20 bytes"
+        rows[i] = (int(index), int(validator), np.frombuffer(bytes(address), dtype=np.uint8), int(amount))
+    return rows
+
+
+def pack_bls_changes(changes) -> np.ndarray:
+    """BLS_CHANGE_DTYPE rows, or an iterable of (validator_index, from_bls_pubkey48, to_execution_address20, signature_valid)."""
+    if isinstance(changes, np.ndarray) and changes.dtype == BLS_CHANGE_DTYPE:
+        return np.ascontiguousarray(changes)
+    items = list(changes)
+    rows = np.zeros(len(items), dtype=BLS_CHANGE_DTYPE)
+    for i, (validator, pubkey, address, valid) in enumerate(items):
+        assert len(pubkey) == 48 and len(address) == 20, "a BLS pubkey is 48 bytes, an execution address 20"
+        rows[i] = (int(validator), np.frombuffer(bytes(pubkey), dtype=np.uint8), np.frombuffer(bytes(address), dtype=np.uint8),
+                   _abi.PE_CRED_FLAG_SIGNATURE_VALID if valid else 0)
+    return rows
+
+
 _ATT_DTYPE = np.dtype([
     ("slot", "<u8"), ("index", "<u8"), ("beacon_block_root", "u1", (32,)),
     ("source_epoch", "<u8"), ("source_root", "u1", (32,)),
@@ -1369,6 +1402,60 @@ class Engine:
                                                           len(ops), _ptr(flat if flat.size else None, C.c_uint32), flat.size,
                                                           C.byref(params), _ptr(status), C.byref(st)))
         return status[:len(ops)], {name: int(getattr(st, name)) for name, _ in _abi.pe_block_ops_stats._fields_}
+
+    # -- Capella: withdrawals and address changes over the resident registry ----
+    def withdrawals_params(self, **overrides):
+        """pe_withdrawals_params_default with fields replaced by keyword (max_effective_balance, max_withdrawals_per_payload,
+        max_validators_per_sweep, eth1_prefix)."""
+        p = _abi.pe_withdrawals_params()
+        self._lib.pe_withdrawals_params_default(C.byref(p))
+        for k, v in overrides.items():
+            assert hasattr(p, k), k
+            setattr(p, k, int(v))
+        return p
+
+    def process_withdrawals(self, current_epoch: int, next_withdrawal_index: int, next_withdrawal_validator_index: int,
+                            payload=None, apply: bool = False, params=None):
+        """get_expected_withdrawals / process_withdrawals over the resident registry (pe_process_withdrawals).  payload: the
+        execution payload's withdrawals (``pack_withdrawals`` rows or (index, validator_index, address, amount) tuples; None =
+        no payload: the call only computes); apply: debit the balances where the payload matches.  params:
+        ``withdrawals_params(...)``, a dict of its overrides, or None for the defaults.  -> (the expected withdrawals as
+        WITHDRAWAL_DTYPE rows, pe_withdrawals_result as a dict; "status" != 0: the block is invalid and NOTHING was changed)."""
+        if params is None or isinstance(params, dict):
+            params = self.withdrawals_params(**(params or {}))
+        flags = (_abi.PE_WD_APPLY if apply else 0) | (0 if payload is None else _abi.PE_WD_PAYLOAD)
+        rows = None if payload is None else pack_withdrawals(payload)
+        out = np.zeros(64, dtype=WITHDRAWAL_DTYPE)
+        res = _abi.pe_withdrawals_result()
+        self._check(self._lib.pe_process_withdrawals(
+            self._h, int(current_epoch), int(next_withdrawal_index), int(next_withdrawal_validator_index), C.byref(params),
+            _ptr(rows if rows is not None and rows.size else None), 0 if rows is None else rows.size, flags, _ptr(out), C.byref(res)))
+        d = {name: int(getattr(res, name)) for name, _ in _abi.pe_withdrawals_result._fields_ if name != "withdrawals_root"}
+        d["withdrawals_root"] = bytes(res.withdrawals_root)
+        return out[:res.n_withdrawals].copy(), d
+
+    def process_bls_to_execution_changes(self, changes):
+        """process_bls_to_execution_change over the resident withdrawal credentials, in array order, each on what the earlier
+        ones left (pe_process_bls_to_execution_changes).  changes: ``pack_bls_changes`` rows or (validator_index,
+        from_bls_pubkey, to_execution_address, signature_valid) tuples.  -> (status int32[n], pe_bls_changes_stats as a dict).
+        If any status is not 0 the block is invalid and NOTHING was changed."""
+        rows = pack_bls_changes(changes)
+        status = np.zeros(max(rows.size, 1), dtype=np.int32)
+        st = _abi.pe_bls_changes_stats()
+        self._check(self._lib.pe_process_bls_to_execution_changes(self._h, _ptr(rows if rows.size else None), rows.size,
+                                                                  _ptr(status), C.byref(st)))
+        return status[:rows.size], {name: int(getattr(st, name)) for name, _ in _abi.pe_bls_changes_stats._fields_}
+
+    def bls_change_signing_roots(self, changes, domain: bytes) -> np.ndarray:
+        """compute_signing_root(BLSToExecutionChange, domain) of every change, hashed on the GPU
+        (pe_bls_change_signing_roots): uint8[n, 32].  The caller hashes these to the curve and checks them against
+        from_bls_pubkey: the verdicts are ``process_bls_to_execution_changes``' signature_valid."""
+        rows = pack_bls_changes(changes)
+        dom = np.frombuffer(bytes(domain), dtype=np.uint8).copy()
+        assert dom.size == 32
+        out = np.zeros((max(rows.size, 1), 32), dtype=np.uint8)
+        self._check(self._lib.pe_bls_change_signing_roots(self._h, _ptr(rows if rows.size else None), rows.size, _ptr(dom), _ptr(out)))
+        return out[:rows.size]
 
     # -- SSZ roots of the resident lists ------------------------------------
     def registry_set_static(self, pubkeys48, withdrawal_credentials, activation_eligibility_epoch):

@@ -857,6 +857,70 @@ def process_voluntary_exit(state, signed_voluntary_exit, *, signature_valid: boo
                       "process_voluntary_exit")
 
 
+# ----------------------------------------------------------------------------- Capella: withdrawals and address changes
+def _upload_for_withdrawals(state, who: str):
+    """The columns the two Capella calls read, from a bound state: epochs, balances and withdrawable epochs, and the static
+    part (the credentials).  The effective balances are the binding's view."""
+    b = _binding(state)
+    assert b is not None, who + ": bind_state(engine, state, ...) first"
+    vals, n, e = state.validators, len(state.validators), b.engine
+    e.registry_set_epochs(_u64_of((v.activation_epoch for v in vals), n), _u64_of((v.exit_epoch for v in vals), n))
+    scores = getattr(state, "inactivity_scores", None)
+    e.state_set_balances(_u64_of(state.balances, n), None if scores is None else _u64_of(scores, n),
+                         _u64_of((v.withdrawable_epoch for v in vals), n))
+    e.registry_set_static(np.frombuffer(b"".join(bytes(v.pubkey) for v in vals), dtype=np.uint8).reshape(n, 48),
+                          np.frombuffer(b"".join(bytes(v.withdrawal_credentials) for v in vals), dtype=np.uint8).reshape(n, 32),
+                          _u64_of((v.activation_eligibility_epoch for v in vals), n))
+    return e
+
+
+def _withdrawal_rows(withdrawals):
+    return [(int(w.index), int(w.validator_index), bytes(w.address), int(w.amount)) for w in withdrawals]
+
+
+def get_expected_withdrawals(state, **params):
+    """get_expected_withdrawals over a state bound with ``bind_state`` (pe_process_withdrawals without PE_WD_APPLY): reads
+    ``state.next_withdrawal_index`` and ``state.next_withdrawal_validator_index``.  Keywords replace fields of
+    pe_withdrawals_params.  -> the expected withdrawals as WITHDRAWAL_DTYPE rows."""
+    e = _upload_for_withdrawals(state, "get_expected_withdrawals")
+    rows, _ = e.process_withdrawals(int(state.slot) // int(e.cfg.slots_per_epoch), int(state.next_withdrawal_index),
+                                    int(state.next_withdrawal_validator_index), None, False, params)
+    return rows
+
+
+def process_withdrawals(state, payload, **params) -> None:
+    """process_withdrawals over a bound state: ``payload.withdrawals`` must be the expected withdrawals; their balances are
+    debited and the state's two next-indices move.  Raises AssertionError where the payload differs, as the pyspec's assert
+    would; the state is then untouched.  The path without any transfer is ``Engine.process_withdrawals`` over arrays that stay
+    resident."""
+    who = "process_withdrawals"
+    e = _upload_for_withdrawals(state, who)
+    _, res = e.process_withdrawals(int(state.slot) // int(e.cfg.slots_per_epoch), int(state.next_withdrawal_index),
+                                   int(state.next_withdrawal_validator_index), _withdrawal_rows(payload.withdrawals), True, params)
+    state._last_withdrawals_result = res
+    assert res["status"] == 0, f"{who}: withdrawal {res['first_mismatch']}: {_abi.WD_STATUS_NAMES.get(res['status'], res['status'])}"
+    bal, _, _, _ = e.state_get_balances()
+    state.balances[:] = [int(x) for x in bal]
+    state.next_withdrawal_index = res["next_withdrawal_index"]
+    state.next_withdrawal_validator_index = res["next_withdrawal_validator_index"]
+
+
+def process_bls_to_execution_change(state, signed_address_change, *, signature_valid: bool = True) -> None:
+    """process_bls_to_execution_change over a bound state: ``signed_address_change.message`` names validator_index,
+    from_bls_pubkey and to_execution_address; ``signature_valid`` is the verdict over its signature
+    (``Engine.bls_change_signing_roots`` gives the root to verify).  Raises AssertionError on an invalid change; the state is
+    then untouched."""
+    who = "process_bls_to_execution_change"
+    e = _upload_for_withdrawals(state, who)
+    m = signed_address_change.message
+    status, _ = e.process_bls_to_execution_changes([(int(m.validator_index), bytes(m.from_bls_pubkey), bytes(m.to_execution_address),
+                                                     bool(signature_valid))])
+    assert status[0] == 0, f"{who}: {_abi.CRED_STATUS_NAMES.get(int(status[0]), int(status[0]))}"
+    _, cred, _, _ = e.registry_static()
+    v = state.validators[int(m.validator_index)]
+    v.withdrawal_credentials = cred[int(m.validator_index)].tobytes()
+
+
 def attester_slashing_ops_from_evidence(evidence: Iterable, signature_valid: bool = True) -> List[dict]:
     """``find_attester_slashings`` output -> single-validator operations for ``Engine.process_block_operations``, by the
     slasher's own convention (include/posevo.h: on_attester_slashing with attesting_indices = [v] on both sides): one
