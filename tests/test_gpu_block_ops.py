@@ -1,7 +1,10 @@
 """-m gpu: pe_process_block_operations (block_ops_kernels.hip) against the sequential loop of tests/block_ops_model.py, bit
 for bit: every resident array read back (exit and withdrawable epochs, balances, the view's flags), every status and every
 word of the stats.  There is no tolerance anywhere in this file.  256 = the slots of one workgroup (BLOCK_OPS_WG), 64 = a
-wave; the registries hold 5, 257 or 2049 validators and the churn limit is 4, so that a handful of exits moves the queue."""
+wave; the registries hold 5, 257 or 2049 validators and the churn limit is 4, so that a handful of exits moves the queue.  At
+most 17 workgroups: k_block_ops_scan sees one wave of partials here.  A block of 516 workgroups (the scan's cross-wave term, its
+tile loop and the ragged last tile), n_slots at 255, 256, 257 and 512 for the call's last lane, and 300 operations for the search
+over the slot offsets are tests/test_gpu_scan_tiles.py, with this file's helpers."""
 import ctypes as C
 from types import SimpleNamespace
 

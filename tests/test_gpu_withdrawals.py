@@ -2,7 +2,8 @@
 against the sequential loops of tests/withdrawals_model.py, bit for bit: the expected withdrawals, every word of the result, the
 balances, withdrawable epochs and credentials read back, and the balances' and validators' SSZ roots against tests/ssz_model.py.
 There is no tolerance anywhere in this file.  256 = the positions of one workgroup (WD_WG), 64 = a wave; the registries hold 1 to
-600 validators."""
+600 validators, at most 3 workgroups: k_withdrawals_scan sees one wave of counts here.  Sweeps of 64, 65 and 259 workgroups (the
+scan's cross-wave term, its tile loop and the ragged last tile) are tests/test_gpu_scan_tiles.py, with this file's helpers."""
 from types import SimpleNamespace
 
 import numpy as np
